@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the sampling + meshing hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs if asked and prints the headline line (`value`,
+`ms_per_step`, the workload and the counts of its last step); nothing else runs.  `--full` adds every other section described below
+(parity against the reference's hash, isolated calls, end to end, sustained run, roofline, CPU baselines, the other
+configurations).  `--dump-outputs DIR` writes what the last timed step computed as float64 .npy files (dump_outputs).
 
 N > 1: one rank per GPU.  Launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 the ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; started plainly (`python bench.py
@@ -16,7 +21,7 @@ the same ordered soup on every rank).  The axes are the only input (3 x 512 floa
 inside the timed region (the PCIe-inclusive rate is reported separately as `value_incl_d2h`).  float64 sampling =
 the reference's NumPy precision.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` for the dominant kernel (k_mesh), `cpu_baseline` = the CPU path
+Prints ONE JSON line (rank 0).  Extra objects (--full): `roofline` for the dominant kernel (k_mesh), `cpu_baseline` = the CPU path
 TIMED ON THIS BOX IN THIS RUN: the reference's own (NumPy thread pool + skimage; kind "reference") where it is installed, else the C
 port of its algorithm that serves as checker, on one host core (kind "port": the GPU boxes have no reference);
 `cpu_reference_recorded` = the reference's numbers from the build container where it could not be timed here (another machine: said
@@ -225,6 +230,33 @@ def stats3(v):
     return {'min': round(float(v.min()), 4), 'median': round(float(np.median(v)), 4), 'max': round(float(v.max()), 4), 'n': int(len(v))}
 
 
+# --dump-outputs: triangles of the soup's seeded sample (2**19 x 72 B = 38 MB of float64; the files come to 42 MB in all)
+DUMP_TRIANGLES = 1 << 19
+DUMP_SEED = 2027
+
+
+def dump_outputs(outdir, soup, tris, st):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the ordered float64 soup (flat torch tensor of 9 * tris
+    values) and the step's counts -- as float64 .npy files, so that two builds can be compared output for output:
+    counts.npy          [triangles, batches, skipped, empty, nonempty]
+    soup_sample.npy     (S, 3, 3) triangles of the soup at the indices of soup_sample_index.npy (S = min(tris, DUMP_TRIANGLES),
+                        drawn without replacement by a fixed seed: the same indices wherever the triangle count is the same)
+    soup_extent.npy     (3, 3) per-axis min, max and mean over every vertex of the whole soup"""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    counts = [tris, st['batches'], st['skipped'], st['empty'], st['nonempty']]
+    np.save(os.path.join(outdir, 'counts.npy'), np.array(counts, dtype=np.float64))
+    n = min(tris, DUMP_TRIANGLES)
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(tris, n, replace=False)) if n else np.zeros(0, dtype=np.int64)
+    tri = soup[:9 * tris].view(tris, 9)
+    sample = tri.index_select(0, torch.from_numpy(idx).to(soup.device)).cpu().numpy().reshape(n, 3, 3)
+    np.save(os.path.join(outdir, 'soup_sample.npy'), sample.astype(np.float64, copy=False))
+    np.save(os.path.join(outdir, 'soup_sample_index.npy'), idx.astype(np.float64))
+    v = soup[:9 * tris].view(-1, 3)
+    extent = torch.stack([v.amin(0), v.amax(0), v.mean(0)]).cpu().numpy() if tris else np.full((3, 3), np.nan)
+    np.save(os.path.join(outdir, 'soup_extent.npy'), extent.astype(np.float64, copy=False))
+
+
 def _oracle_worker(jobs, order, outdir, wid):
     """worker of whole_soup_vs_oracle (its own process, no GPU): the checker's soup of the pieces `order` names, each left as a file of
     its own (written under another name, then renamed: the parent only ever sees whole files)"""
@@ -343,7 +375,12 @@ def main():
     ap.add_argument('--sync', action='store_true', help='one step in flight: every call synchronises before the next is submitted')
     ap.add_argument('--inflight', type=int, default=6, help='steps in flight on a single GPU (each on a lane of its own; at most 8)')
     ap.add_argument('--chunks', type=int, default=None, help='N > 1: shards per rank and step (default 1: one all-gather per step)')
+    ap.add_argument('--full', action='store_true', help='also run every section behind the headline: parity against the reference, '
+                    'isolated calls, end to end, sustained run, roofline, CPU baselines, other configs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/<name>.npy (float64)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -377,7 +414,7 @@ def main():
     dev = torch.device('cuda', local_rank)
     comm_dev = dev if (backend == 'nccl' or os.environ.get('SDF_BENCH_COMM_DEVICE') == 'cuda') else torch.device('cpu')
     stat_dev = dev if backend == 'nccl' else torch.device('cpu')      # (the few scalars the ranks exchange about the run itself)
-    clocks_idle = read_clocks() if rank == 0 else None
+    clocks_idle = read_clocks() if rank == 0 and args.full else None
 
     def soup_sha(soup, tris):
         """sha256 of the first `tris` triangles of a soup on the device (torch tensor), copied out in pieces"""
@@ -509,7 +546,7 @@ def main():
     res = measure(args.model, args.samples_log2, args.steps, args.warmup, DEPTH)
     if headline_timer is not None:
         headline_timer.cancel()
-    clocks_busy = read_clocks() if rank == 0 else None       # (right behind the timed region)
+    clocks_busy = read_clocks() if rank == 0 and args.full else None       # (right behind the timed region)
     f, tape, X, Y, Z, dt, state = res['f'], res['tape'], res['X'], res['Y'], res['Z'], res['dt'], res['state']
     grid_voxels = res['grid_voxels']
     mesh_ms, exch_ms = res['mesh_ms'], res['exch_ms']
@@ -518,6 +555,40 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     value = grid_voxels * args.steps / dt
     per_rank = None
+
+    def leave():
+        """every rank tears the process group down at the same point (a rank that closes its connections while another is
+        still alive has been seen to abort the survivor under gloo)"""
+        if td is not None:
+            td.barrier()
+            td.destroy_process_group()
+
+    # the line of a plain run: what the timed steps measured and the counts of the last one (--full adds its sections to it)
+    head = {
+        'metric': 'grid voxels/sec (sampled + meshed), canonical CSG example',
+        'value': round(value, 1), 'unit': 'voxels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
+        'scaling': 'strong', 'vs_baseline': None, 'dtype': args.precision, 'data': 'synthetic',
+        'config': {'workload': '%s @ samples=2**%d -> %dx%dx%d grid, sparse=True, batch_size=32'
+                               % (args.model, args.samples_log2, len(X), len(Y), len(Z)),
+                   'batches': int(st['batches']), 'skipped': int(st['skipped']), 'empty': int(st['empty']),
+                   'nonempty': int(st['nonempty']), 'triangles': tris,
+                   'parallelism': 'work-list shards x%d + one RCCL all-gather of the slabs per step' % world if world > 1 else 'single GPU'},
+        'triangles_per_sec': round(tris * args.steps / dt, 1),
+        'eval_voxels_per_sec': round(int(st['n_eval_voxels']) * args.steps / dt, 1),
+        # (`value` counts every voxel of the grid -- the reference's unit of work; of those the skip test and the interval passes decide
+        # all but these, which are the ones that go through the tape interpreter)
+        'interpreted_voxels_per_sec': round(int(st.get('n_sampled_voxels', 0)) * args.steps / dt, 1),
+        'interpreted_share_of_grid': round(int(st.get('n_sampled_voxels', 0)) / max(grid_voxels, 1), 5),
+        'steps_in_flight': DEPTH,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state.get('soup'), tris, st)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        leave()
+        return
     # ---- the headline is measured: from here on nothing may keep its line from being printed (one GPU; N > 1: the headline's own
     # watchdog above and `watchdog` below).  If the sections that follow -- isolated calls, end to end, sustained run, CPU baselines,
     # the other configurations -- have not led to the full line after SDF_BENCH_TOTAL_TIMEOUT_S seconds (default 480), the line is
@@ -751,13 +822,6 @@ def main():
                 td.barrier()
         return others
 
-    def leave():
-        """every rank tears the process group down at the same point (a rank that closes its connections while another is
-        still alive has been seen to abort the survivor under gloo)"""
-        if td is not None:
-            td.barrier()
-            td.destroy_process_group()
-
     want_others = not args.no_other_configs and args.model == 'example' and args.samples_log2 == 27 and args.precision == 'f64'
     if rank != 0:
         if want_others:
@@ -865,26 +929,11 @@ def main():
                                                                          os.cpu_count(), len(r.points) // 3),
                'triangles_per_sec': round(len(r.points) // 3 / cdt, 1)}
 
-    out = {
-        'metric': 'grid voxels/sec (sampled + meshed), canonical CSG example',
-        'value': round(value, 1), 'unit': 'voxels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
-        'scaling': 'strong', 'vs_baseline': None, 'dtype': args.precision, 'data': 'synthetic',
-        'config': {'workload': '%s @ samples=2**%d -> %dx%dx%d grid, sparse=True, batch_size=32'
-                               % (args.model, args.samples_log2, len(X), len(Y), len(Z)),
-                   'batches': int(st['batches']), 'skipped': int(st['skipped']), 'empty': int(st['empty']),
-                   'nonempty': int(st['nonempty']), 'triangles': tris,
-                   'parallelism': 'work-list shards x%d + one RCCL all-gather of the slabs per step' % world if world > 1 else 'single GPU'},
-        'triangles_per_sec': round(tris * args.steps / dt, 1),
-        'eval_voxels_per_sec': round(int(st['n_eval_voxels']) * args.steps / dt, 1),
-        # (`value` counts every voxel of the grid -- the reference's unit of work; of those the skip test and the interval passes decide
-        # all but these, which are the ones that go through the tape interpreter)
-        'interpreted_voxels_per_sec': round(int(st.get('n_sampled_voxels', 0)) * args.steps / dt, 1),
-        'interpreted_share_of_grid': round(int(st.get('n_sampled_voxels', 0)) / max(grid_voxels, 1), 5),
+    out = dict(head)
+    out.update({
         'value_incl_d2h': round(incl, 1) if incl else None,
         'generate_e2e': e2e,
         'sustained': sustained,
-        'steps_in_flight': DEPTH,
         'latency_ms_per_call': iso['wall_ms']['median'] if iso else None,
         'isolated_calls': iso,
         'clocks': {'idle_before': clocks_idle, 'after_timed_region': clocks_busy, 'after_isolated_calls': clocks_iso,
@@ -914,7 +963,7 @@ def main():
         'cpu_baseline_note': "kind 'port' on a GPU box is by the task's rules, not an omission: the reference is Python and may not travel in any form "
                              "(source, bytecode or otherwise), so oracle/_ref cannot hold it; where /root/reference exists (the build container) this object is the live reference",
         'other_configs': None,
-    }
+    })
     if want_others:
         timer = watchdog(out)
         out['other_configs'] = run_other_configs()

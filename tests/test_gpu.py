@@ -492,7 +492,7 @@ def test_bench_two_ranks_on_one_device_exchange_slabs_between_processes(driver, 
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-other-configs'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline', '--no-other-configs'], env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
     rec = json.loads(lines[0])
@@ -565,12 +565,14 @@ def test_image_leaf_on_device(name, ns, oracle_lib, eng):
     assert hashlib.sha256(pts.tobytes()).digest() == TEX['gen_sha_' + name].tobytes()
 
 
-def test_text_leaf_runs_on_device(ns, eng, oracle_lib):
+def test_text_leaf_runs_on_device(ns, eng, oracle_lib, tmp_path):
     """`text(...)`: the glyph raster depends on the FreeType build, so it is checked against the CPU
-    checker on the same texture (not against a golden)"""
-    font = '/usr/share/fonts/truetype/dejavu/DejaVuSans.ttf'
-    if not os.path.exists(font):
-        pytest.skip('no TrueType font on this box')
+    checker on the same texture (not against a golden).  The font is the TrueType font Pillow itself
+    carries (Aileron Regular, ImageFont.load_default), written to a file: no system font needed."""
+    from PIL import ImageFont
+    font = str(tmp_path / 'Aileron-Regular.ttf')
+    with open(font, 'wb') as fp:
+        fp.write(ImageFont.load_default(size=96).font_bytes)
     t = ns['text'](font, 'MI355X', width=4.0, points=96)
     g = t.extrude(0.5)
     rng = np.random.RandomState(3)

@@ -16,8 +16,8 @@ run() { echo "== $1"; shift; env "$@" python tools/modeltime.py --on-only $JOBS 
   echo "== new weave 2^33"; python tools/modeltime.py --on-only weave:33 2>&1 | grep -v Warning
 } > gpurun_out/ab_models.txt 2>&1
 {
-  [ -f "$BASE" ] && { echo "== base"; SDF_HIP_LIB=$BASE python bench.py --no-cpu-baseline 2>&1 | tail -1; }
-  echo "== new"; python bench.py --no-cpu-baseline 2>&1 | tail -1
-  echo "== new, cull block 128"; SDF_CULL_BLOCK=128 python bench.py --no-cpu-baseline 2>&1 | tail -1
-  echo "== new, cull block 64"; SDF_CULL_BLOCK=64 python bench.py --no-cpu-baseline 2>&1 | tail -1
+  [ -f "$BASE" ] && { echo "== base"; SDF_HIP_LIB=$BASE python bench.py --full --no-cpu-baseline 2>&1 | tail -1; }
+  echo "== new"; python bench.py --full --no-cpu-baseline 2>&1 | tail -1
+  echo "== new, cull block 128"; SDF_CULL_BLOCK=128 python bench.py --full --no-cpu-baseline 2>&1 | tail -1
+  echo "== new, cull block 64"; SDF_CULL_BLOCK=64 python bench.py --full --no-cpu-baseline 2>&1 | tail -1
 } > gpurun_out/ab_bench.txt 2>&1

@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 for rep in 1 2; do
   for v in old new; do
-    SDF_HIP_LIB=$PWD/ablibs/lib_$v.so timeout 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_${v}_$rep.txt 2>&1
+    SDF_HIP_LIB=$PWD/ablibs/lib_$v.so timeout 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_${v}_$rep.txt 2>&1
     SDF_HIP_LIB=$PWD/ablibs/lib_$v.so timeout 300 python tools/modeltime.py --on-only example:27 pawn:27 knurling:27 blobby:30 gearlike:30 weave:27 weave:33 > $O/models_${v}_$rep.txt 2>&1
   done
 done

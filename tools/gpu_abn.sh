@@ -9,7 +9,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 for rep in 1 2 3; do
   for v in "$@"; do
-    SDF_HIP_LIB=$PWD/ablibs/lib_$v.so timeout 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-f32-envelope > $O/bench_${v}_$rep.txt 2>&1
+    SDF_HIP_LIB=$PWD/ablibs/lib_$v.so timeout 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-f32-envelope > $O/bench_${v}_$rep.txt 2>&1
   done
 done
 python - "$O" <<'PY'

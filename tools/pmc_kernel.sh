@@ -3,7 +3,7 @@
 REPO=$(pwd); OUT=$REPO/gpurun_out/pmck; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_INSTS_FLAT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_ANY"; do
   n=$(echo $set | cut -c1-12 | tr ' ' '_')
-  timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/$n -o p -- python $REPO/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $OUT/$n.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $OUT/$n -o p -- python $REPO/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $OUT/$n.log 2>&1
 done
 python - "$OUT" "${1:-}" <<'PY'
 import sys, glob, csv

@@ -2,7 +2,7 @@
 # quick HBM traffic check of k_mesh: FETCH_SIZE / WRITE_SIZE
 REPO=$(pwd); OUT=$REPO/gpurun_out/pmcq; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o $c -- python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/$c.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -o $c -- python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/$c.log 2>&1
   python - "$OUT/$c" $c <<'PY'
 import sys, glob, csv
 d, c = sys.argv[1], sys.argv[2]

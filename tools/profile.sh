@@ -9,7 +9,7 @@
 set -u
 TAG=${1:-r01}
 shift || true
-ARGS=${*:---steps 20 --warmup 3 --no-cpu-baseline}
+ARGS="--full ${*:---steps 20 --warmup 3 --no-cpu-baseline}"   # (--full: the roofline and isolated calls the summary quotes)
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
