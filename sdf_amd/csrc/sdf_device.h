@@ -58,15 +58,11 @@ struct MeshCounters {   // zeroed before every k_mesh run
     unsigned long long n_raw;         // compact output: triangles that went to the slab's raw area (sdf_slab.h)
     // written by k_compact (NOT cleared between meshing retries): the surviving-batch work list
     // and this shard's slice of it, so k_mesh can start without a host round trip
-    int nwork, work_begin, work_end;
-    int not_mesh2;                    // k_cull: some tile of this shard is not k_mesh2's (left dense, or more than MESH2_NTL_MAX listed tasks)
+    int nwork, work_begin, work_end, pad_;
 };
 enum { MESH_COUNTERS_RESET_BYTES = 112 };   // the part of MeshCounters cleared before every k_mesh run
-// overflow bits: 1 the soup (or an arena) was too small, 2 a look-back timed out, 16 k_mesh2 met a tile it does not hold (the call is
-// repeated with k_mesh; 4 and 8 are the slab header's own: items, raw area -- k_pack_slab)
-enum { MESH_OVERFLOW_NOT_MESH2 = 16 };
-// k_mesh2 (sdf_mesh2.h) takes tiles of at most this many listed tasks (their samples: 48 KB of its 64 KB region)
-enum { MESH2_NTL_MAX = 192 };
+// overflow bits: 1 the soup (or an arena) was too small, 2 a look-back timed out (4 and 8 are the slab header's own: items, raw
+// area -- k_pack_slab)
 
 struct GridDesc {
     const double *X, *Y, *Z;   // device copies of the np.arange axes

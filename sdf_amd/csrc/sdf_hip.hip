@@ -45,7 +45,6 @@
 #include "../../include/sdf_hip.h"
 #include "mc_table.h"
 #include "sdf_device.h"
-#include "sdf_mesh2.h"
 #include "sdf_prune.h"
 #include "sdf_slab.h"
 #include "sdf_expand_host.h"
@@ -234,8 +233,6 @@ __device__ __forceinline__ void cull_body(const uint32_t *__restrict__ code, con
     const int ntl = cull_tasks<CB, FULL, RARE>(wcode, consts, n_instr_w, lx, ly, lz, axes, ia_state, ia_bytes, scratch, wave_sums, ia_np, ia_nd, prof, levels);
     const long long tw = prof ? clock64() : 0;
     if (tid == 0 && ntl < 0) reinterpret_cast<unsigned short *>(scratch)[0] = (unsigned short)0xFFFF;   // (else: the number of listed units, cull_tasks)
-    // (what the host needs to know before it may hand the NEXT call of this tape on this grid to k_mesh2: rarely written)
-    if (tid == 0 && (ntl > MESH2_NTL_MAX || (ntl < 0 && lx > 1 && ly > 1 && lz > 1))) const_cast<MeshCounters *>(ctr)->not_mesh2 = 1;
     __syncthreads();
     {   // the record: header + the listed units (whole tasks), and the sub-group states
         unsigned *rec = reinterpret_cast<unsigned *>(out + (size_t)w * CULL_RECORD);
@@ -453,10 +450,6 @@ struct sdf_ctx {
     DevBuf scratch_in, scratch_out, rows, rows_off, mc;
     DevBuf ext;                       // closure points / values of sdf_eval_*extern* (L_EXTERN leaves)
     DevBuf field_vals, field_vol, field_tiles;   // sdf_generate_field: a chunk's sampled values (f64), volumes (f32), tile table
-    int mesh2 = 0;                    // SDF_MESH2: k_mesh2 (two workgroups of 512 threads per CU) 0 never (default: measured in r06, bit-identical
-                                      // and 4 - 6 % slower than k_mesh at 512^3, profiles/r06e_two_wg.json) / 1 whenever the tape has a variant
-                                      // (a tile it does not hold is flagged and the call repeated) / -1 when the last call of the tape
-                                      // on the same grid says every tile is its
     DevBuf prof;                      // SDF_MESH_PROF=1: per-phase cycle counters of k_mesh (diagnostics)
     int prune = 1;                    // SDF_PRUNE=0 switches the interval prepass off (diagnostics)
     int parking = 1;                  // SDF_PARK=0: k_mesh waits for its predecessors instead of parking a batch (diagnostics)
@@ -500,10 +493,6 @@ struct sdf_tape {
     bool ia_rare = false;                                // ... one of them a leaf of ia_leaf_rare (the k_cull variant that knows them)
     uint32_t n_extern = 0;                               // user closures the tape reads through L_EXTERN leaves (sdf_eval_points_extern_*)
     unsigned long long hint_key = 0, hint_total_tris = 0;   // arena sizing: last call of this tape
-    // which meshing kernel the next call on the same grid takes (k_mesh2: two workgroups per CU): 0 unknown, 1 every tile of the
-    // last call was k_mesh2's (k_cull's verdict, MeshCounters::not_mesh2), 2 not so, 3 k_mesh2 ran and flagged a tile (sticky)
-    unsigned long long mesh2_key = 0;
-    int mesh2_state = 0;
     unsigned long long content_hash = 0;                    // FNV-1a of the code words and the constants' bits: what identifies the MODEL,
                                                             // on every rank alike and whatever address the tape object lands on (sdf_comm.inc)
 };
@@ -516,7 +505,6 @@ struct sdf_mesh {
     DevBuf desc, cellrecs, trilist;   // two-pass meshing: per work item / per surface cell / per triangle (sdf_device.h ItemDesc)
     DevBuf blockidx;                  // ... and per 256 triangles of the soup: the work item of the first of them
     bool pruned = false;
-    bool used_mesh2 = false;       // the meshing pass was k_mesh2's (two workgroups per CU)
     hipStream_t stream = nullptr;  // the stream the generating call ran on (the context's, or a call slot's lane)
     DevBuf counters;               // this call's MeshCounters block (pooled in the context)
     int work_begin = 0, work_end = 0;
@@ -665,7 +653,6 @@ static int ctx_init(sdf_ctx *c) {
     if (c->mc.ensure(sizeof(t))) return 1;
     HIPCHK(hipMemcpy(c->mc.p, &t, sizeof(t), hipMemcpyHostToDevice));
     if (const char *e = getenv("SDF_BOUNDS_TAG0")) c->bounds_tag0 = (unsigned)atoi(e) & 0xFFFFu;   // (tests: the first tag of the exchange words)
-    if (const char *e = getenv("SDF_MESH2")) c->mesh2 = atoi(e);
     if (const char *e = getenv("SDF_MESH_SLOTS")) c->mesh_slots = atoi(e);
     if (const char *e = getenv("SDF_PRUNE")) c->prune = atoi(e);
     if (const char *e = getenv("SDF_PARK")) c->parking = atoi(e);
@@ -721,12 +708,6 @@ int sdf_ctx_set_cull(sdf_ctx *c, int enabled) {
 int sdf_ctx_set_defer(sdf_ctx *c, int on) {
     if (!c) return fail("sdf_ctx_set_defer: ctx is NULL");
     c->defer = on ? 1 : 0;
-    return 0;
-}
-int sdf_ctx_set_mesh2(sdf_ctx *c, int mode) {
-    if (!c) return fail("sdf_ctx_set_mesh2: ctx is NULL");
-    if (mode < -1 || mode > 1) return fail("sdf_ctx_set_mesh2: -1 (by the previous call), 0 (never) or 1 (whenever the tape has a variant)");
-    c->mesh2 = mode;
     return 0;
 }
 int sdf_ctx_set_cull_levels(sdf_ctx *c, int levels) {
@@ -1090,27 +1071,6 @@ static int launch_mesh(sdf_tape *t, const void *code, int precision, MeshArgs &a
     return 0;
 }
 
-// k_mesh2 (sdf_mesh2.h): the register file of the tape, or -1 when none of its variants holds it
-static int mesh2_slots(const sdf_tape *t) {
-    const uint32_t np = std::max(t->n_p, 1u), nd = std::max(t->n_d, 1u);
-    return (np <= 1 && nd <= 1) ? 0 : ((np <= 2 && nd <= 2) ? 1 : ((np <= 2 && nd <= 4) ? 3 : -1));
-}
-// ... and its launch: two workgroups per compute unit, each with half of the CU's LDS -- the fixed areas and ONE region that the
-// batch being sampled and the batch that waits share from its two ends
-static int launch_mesh2(sdf_tape *t, const void *code, MeshArgs &a, int nb, hipStream_t st) {
-    sdf_ctx *c = t->ctx;
-    const size_t lds = (c->lds_max / 2) & ~(size_t)1023;
-    if (lds < (size_t)M2_REGION + 16384) return fail("k_mesh2: device LDS too small");
-    a.slot_bytes = (int)((lds - M2_REGION) & ~(size_t)15);
-    a.bits_off = a.list_off = a.list_cap = a.stage_off = 0;      // (k_mesh's layout: not used)
-    a.order = nullptr; a.tail = 0; a.park = nullptr; a.park_cap = 0;
-    const int grid = std::min(nb, 2 * c->n_cu);
-    const int rc = t->full ? sdf_launch_mesh2_f64_full(mesh2_slots(t), grid, lds, st, (const uint32_t *)code, t->d_c64, a)
-                           : sdf_launch_mesh2_f64(mesh2_slots(t), grid, lds, st, (const uint32_t *)code, t->d_c64, a);
-    if (rc) return fail(std::string("k_mesh2 launch: ") + (rc < 0 ? "no variant for this tape" : hipGetErrorString((hipError_t)rc)));
-    return 0;
-}
-
 // the skip test (`_skip`, reference sdf/core.py:28-43) of batches [b0, b1) alone, enqueued on `st`: d_kinds[b] = 0 (skipped) or
 // 255 (pending) for those batches; the axes are on the device already (X, then Y, then Z)
 static int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
@@ -1148,7 +1108,7 @@ static void finish_stats(sdf_tape *t, sdf_mesh *m, const MeshCounters &h, int nb
     m->st.t_mesh_first_us = h.t_first_inv ? (double)(~h.t_first_inv) * 0.01 : 0.0;
     m->st.t_mesh_last_us = (double)h.t_last * 0.01;
     m->pruned = pruning;
-    m->st.mesh_kernel = m->used_mesh2 ? 2 : 1;
+    m->st.mesh_kernel = 1;
     m->st.n_batch_instrs = (int64_t)(n_instr - 1) * (h.work_end - h.work_begin);
     t->hint_key = key; t->hint_total_tris = std::max<unsigned long long>(h.total, 1);
     {   // (per MODEL and grid, for sdf_generate_records; a handful of entries per job -- the map is emptied when it grows past 4096)
@@ -1157,7 +1117,6 @@ static void finish_stats(sdf_tape *t, sdf_mesh *m, const MeshCounters &h, int nb
         sdf_ctx::RecHint &e = rh[std::make_pair(t->content_hash, key)];
         e.tris = std::max<unsigned long long>(h.total, 1); e.raw = h.n_raw;
     }
-    if (!(t->mesh2_key == key && t->mesh2_state == 3)) { t->mesh2_key = key; t->mesh2_state = h.not_mesh2 ? 2 : 1; }
     m->st.ms_prepass = ms_prepass;
     m->st.ms_total = ms_total;
 }
@@ -1376,7 +1335,6 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         }
     }
     float ms = 0;
-    bool mesh2_failed = false;
     for (int attempt = 0;; attempt++) {
         MeshArgs a;
         a.compact = 0; a.xf = nullptr; a.xf_cap = 0; a.raw = nullptr; a.raw_cap = 0;
@@ -1418,11 +1376,7 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         const bool twopass = c->twopass >= 0 ? c->twopass != 0 : n_instr > 96;
         DevBuf &park = async_mode ? cs.park : c->park;   // (k_mesh kernels of calls in flight may overlap in time, whichever
                                                          // streams they run on: each call slot has its own staging slots)
-        // k_mesh or k_mesh2?  (k_mesh2 holds sparse tiles only: culled batches of a tape with a variant, one pass; what it meets and
-        // does not hold it flags, and the pass is repeated with k_mesh)
-        const bool use_mesh2 = culling && !twopass && !mesh2_failed && c->defer && c->mesh2 != 0 && mesh2_slots(t) >= 0 &&
-                               !(t->mesh2_key == key && t->mesh2_state >= 2) && (c->mesh2 > 0 || (t->mesh2_key == key && t->mesh2_state == 1));
-        const bool parks = c->parking && !twopass && !use_mesh2;
+        const bool parks = c->parking && !twopass;
         if (parks && !park.p) { quiet = false; if (park.ensure((size_t)c->n_cu * MESH_PARK_DEPTH * SDF_PARK_TRIS * 36)) return 1; }
         a.park = parks ? (float *)park.p : nullptr; a.park_cap = a.park ? SDF_PARK_TRIS : 0;
         a.park_spins = (unsigned)c->park_spins;
@@ -1454,10 +1408,7 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         const int grid = std::min(nb, c->n_cu);   // persistent workgroups; surplus ones find the list empty
         const bool own_start = attempt > 0 || a.prof || !quiet;   // (something was enqueued, or the host waited, since ev[2])
         if (own_start) HIPCHK(hipEventRecord(cs.e3, st));
-        if (use_mesh2 ? launch_mesh2(t, pruning ? m->tapes.p : (const void *)t->d_code, a, nb, st)
-                      : launch_mesh(t, pruning ? m->tapes.p : (const void *)t->d_code, precision, a, grid, bs, st))
-            return 1;
-        m->used_mesh2 = use_mesh2;
+        if (launch_mesh(t, pruning ? m->tapes.p : (const void *)t->d_code, precision, a, grid, bs, st)) return 1;
         if (a.twopass) {
             const unsigned long long emit_blocks = (a.out_cap + 255ull) / 256ull;
             if (emit_blocks > 0x7fffffffull) return fail("sdf_generate: soup capacity too large for one k_emit2 launch");
@@ -1493,7 +1444,6 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
             unsigned long long pc[64];
             HIPCHK(hipMemcpy(pc, c->prof.p, 512, hipMemcpyDeviceToHost));
             {   // timeline of the workgroups: when each ran out of work and when it was done, relative to the first start
-                const int grid = use_mesh2 ? std::min(nb, 2 * c->n_cu) : std::min(nb, c->n_cu);
                 std::vector<unsigned long long> tl((size_t)4 * grid);
                 HIPCHK(hipMemcpy(tl.data(), (unsigned char *)c->prof.p + 512, tl.size() * 8, hipMemcpyDeviceToHost));
                 unsigned long long t0 = ~0ull, t_end = 0;
@@ -1505,8 +1455,8 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
                 }
                 double first_hi = 0;   // the latest start: workgroups that were not resident from the beginning start late
                 for (int i = 0; i < grid; i++) first_hi = std::max(first_hi, (double)(tl[4 * i] - t0) * 0.01);
-                fprintf(stderr, "[k_mesh prof] %d workgroups (kernel %d), last of them started after %.1f us; out of work after min %.1f avg %.1f max %.1f us; done after avg %.1f, last %.1f us\n",
-                        grid, use_mesh2 ? 2 : 1, first_hi, mn_out, s_out / grid, mx_out, s_done / grid, (double)(t_end - t0) * 0.01);
+                fprintf(stderr, "[k_mesh prof] %d workgroups (1 per CU), last of them started after %.1f us; out of work after min %.1f avg %.1f max %.1f us; done after avg %.1f, last %.1f us\n",
+                        grid, first_hi, mn_out, s_out / grid, mx_out, s_done / grid, (double)(t_end - t0) * 0.01);
             }
             fprintf(stderr, "[k_cull prof] work items by listed tasks (of 563; bins of 64, last: not culled): %llu %llu %llu %llu %llu %llu %llu %llu %llu | %llu\n",
                     pc[32], pc[33], pc[34], pc[35], pc[36], pc[37], pc[38], pc[39], pc[40], pc[41]);
@@ -1521,13 +1471,6 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         }
         m->st.n_retries = attempt;
         if (h.overflow & 2u) return fail("sdf_generate: ordered-allocation look-back timed out");
-        if (h.overflow & (unsigned)MESH_OVERFLOW_NOT_MESH2) {   // k_mesh2 met a tile it does not hold: the same pass again, with k_mesh
-            if (!use_mesh2 || attempt >= 3) return fail("sdf_generate: a tile was flagged as not k_mesh2's by a pass that did not run k_mesh2");
-            if (getenv("SDF_MESH2_DEBUG")) fprintf(stderr, "[k_mesh2] flagged: overflow word 0x%x (32 dense tile, 64 tasks, 128 region, 256 cells, 512 list)\n", h.overflow);
-            t->mesh2_key = key; t->mesh2_state = 3;
-            mesh2_failed = true;
-            continue;
-        }
         if (compact) {   // (the synchronous records mode, sdf_generate_records: its caller sizes the slab again and repeats the call)
             const SlabLayout L(slab_items, cap_out);
             const bool raw_over = (long long)h.n_raw > L.raw_cap;
@@ -1993,15 +1936,7 @@ int sdf_mesh_wait(sdf_mesh *m, int *emitted) {
         m->st.ms_mesh = ms;
         cs.busy = false; cs.owner = nullptr;      // (everything the slot held for this mesh has been read)
         if (h.overflow & 2u) return fail("sdf_generate: ordered-allocation look-back timed out");
-        if (h.overflow & (unsigned)MESH_OVERFLOW_NOT_MESH2) { pd.tape->mesh2_key = pd.key; pd.tape->mesh2_state = 3; }   // (the repeat takes k_mesh)
-        if ((h.overflow & (unsigned)MESH_OVERFLOW_NOT_MESH2) && !pd.compact) {
-            // k_mesh2 met a tile it does not hold: the call is repeated synchronously, into the caller's buffer, with k_mesh
-            const double *X = pd.axes.data(), *Y = X + pd.nx, *Z = Y + pd.ny;
-            if (generate_impl(pd.tape, m, X, pd.nx, Y, pd.ny, Z, pd.nz, pd.bs, pd.sparse, pd.shard_index, pd.shard_count, pd.precision,
-                              pd.d_out, pd.cap_out, false))
-                return 1;
-            m->st.n_retries += 1;
-        } else if (h.overflow && pd.compact) {
+        if (h.overflow && pd.compact) {
             // a slab that was too small: the exchange protocol retries with larger slabs on EVERY rank (sdf_amd/dist.py)
             finish_stats(pd.tape, m, h, pd.nb, pd.pruning, pd.n_instr, pd.key, ms_pre, ms_tot);
             m->emitted_to = nullptr;

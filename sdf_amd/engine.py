@@ -68,7 +68,6 @@ ABI = {
     'sdf_ctx_set_twopass': (ctypes.c_int, [_vp, ctypes.c_int]),
     'sdf_ctx_set_tail_order': (ctypes.c_int, [_vp, ctypes.c_int]),
     'sdf_ctx_set_defer': (ctypes.c_int, [_vp, ctypes.c_int]),
-    'sdf_ctx_set_mesh2': (ctypes.c_int, [_vp, ctypes.c_int]),
     'sdf_ctx_set_cull_levels': (ctypes.c_int, [_vp, ctypes.c_int]),
     'sdf_ctx_synchronize': (ctypes.c_int, [_vp]),
     'sdf_ctx_trim': (ctypes.c_int, [_vp]),
@@ -140,7 +139,7 @@ ABI = {
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def build_info():
@@ -527,12 +526,6 @@ class Engine:
     def set_defer(self, on):
         """one-kernel meshing: sparse tiles + deferred emission (default) or dense tiles + parking; same results"""
         _check(self.lib, self.lib.sdf_ctx_set_defer(self.ctx, int(bool(on))))
-
-    def set_mesh2(self, mode):
-        """which fused kernel meshes a call: 0 always k_mesh (default: k_mesh2 measured slower, profiles/r06e_two_wg.json); -1 k_mesh2
-        (two workgroups of 512 threads per CU) when the previous call of the tape on the same grid found every tile to be its; 1 k_mesh2
-        whenever the tape has a variant.  Same results; `stats()['mesh_kernel']` says which ran"""
-        _check(self.lib, self.lib.sdf_ctx_set_mesh2(self.ctx, int(mode)))
 
     def set_cull_levels(self, levels):
         """interval levels of the culling pass: 2, 3 or 0 = the library's choice by the tape (default); same results"""

@@ -1813,62 +1813,6 @@ def test_core_module_seams_are_the_batch_loop(ns, eng):
         core._marching_cubes(np.ones((4, 4)))
 
 
-@pytest.mark.parametrize('name,samples', [('ex_example', 2 ** 24), ('ex_example', 1500000), ('ex_example', 2 ** 27), ('ex_blobby', 2 ** 23),
-                                          ('ex_gearlike', 2 ** 22), ('ex_knurling', 2 ** 21), ('ex_pawn', 2 ** 22), ('ex_weave', 2 ** 20)])
-def test_two_workgroups_per_cu_same_soup(name, samples, ns, eng):
-    """k_mesh2 (csrc/sdf_mesh2.h: the fused kernel as two workgroups of 512 threads per compute unit, sparse tiles in ONE region of LDS
-    shared from its two ends, no parking) against k_mesh: the same soup, per-batch offsets, verdicts and counters bit for bit -- forced
-    (sdf_ctx_set_mesh2(1): a tile the kernel does not hold is flagged on the device and the pass repeated with k_mesh), synchronous,
-    into a caller buffer and asynchronously with calls in flight; and in mode -1 the SECOND call of a tape on a grid takes it when
-    k_cull found every tile to be its.  (Off by default: measured slower, profiles/r06e_two_wg.json.)"""
-    import torch
-    f = fixtures.build(name, ns)
-    X, Y, Z, _ = core.grid_axes(tuple(map(tuple, BOUNDS[name])), samples=samples)
-    keys = ('triangles', 'skipped', 'empty', 'nonempty', 'n_eval_voxels', 'n_ambiguous_cells', 'n_pruned_instrs', 'n_sampled_voxels')
-    try:
-        eng.set_mesh2(0)
-        m = eng.generate(f, X, Y, Z, 32, True)
-        ref = (m.points(), m.kinds(), m.batch_offsets(), m.stats())
-        m.close()
-        assert ref[3]['mesh_kernel'] == 1 and ref[3]['triangles'] > 1000
-        eng.set_mesh2(1)
-        ran2 = 0
-        for rep in range(2):
-            m = eng.generate(f, X, Y, Z, 32, True)
-            got = (m.points(), m.kinds(), m.batch_offsets(), m.stats())
-            m.close()
-            assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2])
-            for k in keys:
-                assert got[3][k] == ref[3][k], (rep, k)
-            ran2 += got[3]['mesh_kernel'] == 2        # (else: k_cull's verdict of the call before, a flagged tile and the pass repeated, or two passes)
-        # calls in flight into caller buffers
-        nt = len(ref[0]) // 3
-        bufs = [torch.full((9 * nt + 9,), -7.0, dtype=torch.float64, device='cuda:0') for _ in range(3)]
-        ms = [eng.generate(f, X, Y, Z, 32, True, out_ptr=b.data_ptr(), out_cap=nt, wait=False) for b in bufs]
-        for m, b in zip(ms, bufs):
-            m.wait()
-            assert m.n_triangles == nt and float(b[-1]) == -7.0
-            host = b[:9 * nt].cpu().numpy().reshape(-1, 3) if m.emitted else m.points()
-            assert np.array_equal(host, ref[0])
-            m.close()
-        # mode -1: the tape's previous call on this grid decides
-        eng.set_mesh2(-1)
-        f2 = fixtures.build(name, ns)                    # (a tape object of its own: no verdict yet)
-        kernels = []
-        for rep in range(3):
-            m = eng.generate(f2, X, Y, Z, 32, True)
-            st = m.stats()
-            assert np.array_equal(m.points(), ref[0]) and np.array_equal(m.batch_offsets(), ref[2])
-            kernels.append(st['mesh_kernel'])
-            m.close()
-        assert kernels[0] == 1 or ran2 == 2              # (the engine caches device tapes by content: f2 may find f's verdict)
-        assert kernels[1] == kernels[2]
-        if ran2 == 2:
-            assert kernels[1] == 2
-    finally:
-        eng.set_mesh2(0)
-
-
 # ---- `generate` for a host caller: 16-byte records over PCIe, the float64 soup made on host threads (sdf_generate_records) ----
 REC_CASES = [('ex_example', 'gen_example_s17'), ('ex_example', 'gen_example_s22'), ('ex_blobby', 'gen_blobby_s20'), ('ex_gearlike', 'gen_gearlike_s20'),
              ('ex_weave', 'gen_weave_s19'), ('ex_pawn', 'gen_pawn_s16'), ('ex_knurling', 'gen_knurling_s16')]
