@@ -245,8 +245,77 @@ for _k in CUSTOM_FIXTURES:
     CUSTOM_FIXTURES[_k] = _CUSTOM_PRELUDE + CUSTOM_FIXTURES[_k]
 
 
+# ---- models that need many register slots (sdf_amd/tape.py palloc / dalloc): each one is lowered to the register-file variant
+# of k_mesh named in its key -- (saved-point slots, saved-distance slots) of the smallest file that holds the tape, plain or trig
+# family (csrc/sdf_hip.hip launch_mesh, tape_needs_full).  Nested transforms over booleans take saved-point slots, right-nested
+# booleans saved-distance slots.  Kept apart from FIXTURES: values.npz / bounds.npz stay as they are (values_slots.npz,
+# bounds_slots.npz and gen_slots_*.npz are theirs, tools/make_golden.py slots). ----
+SLOT_FIXTURES = {
+    # plain (4,2): 4 point slots, 1 distance slot
+    'slots_plain_4_2': """
+f = box(0.5)
+for i in range(5):
+    f = (f | (sphere(0.25) - box(0.3).translate((0.2, 0, 0)))).translate((-0.1, 0.1, 0.05))
+""",
+    # plain (4,4): 3 + 3
+    'slots_plain_4_4': """
+f = box(0.5)
+for i in range(4):
+    f = (f | (sphere(0.25) - (box(0.3) & (sphere(0.2) | box(0.1)).translate((0.2, 0, 0))))).translate((-0.1, 0.1, 0.05))
+""",
+    # plain (8,8): exactly 8 point slots
+    'slots_plain_8_8_p8': """
+f = sphere(0.6)
+for i in range(9):
+    f = (f | capsule((0, 0, 0), (0.5, 0.2 * (i % 3), 0.1 * i), 0.12)).translate((-0.06, 0.05 * (i % 2), -0.04))
+""",
+    # plain (8,8): exactly 8 distance slots (nested shells; no rotate: its soup is compared bit for bit, gen_slots_*.npz)
+    'slots_plain_8_8_d8': """
+f = sphere(0.35)
+for i in range(9):
+    f = (box(0.8 + 0.3 * i, (0.03 * i, -0.02 * i, 0.01)) if i % 2 else sphere(0.45 + 0.17 * i)) - f
+""",
+    # plain (8,8): 8 + 8, the largest interval state of the prepass (k_skip: 128 KB of LDS) and of the culling pass
+    'slots_plain_8_8_p8d8': """
+f = sphere(0.3)
+for i in range(8):
+    f = box(0.7 + 0.25 * i, (0.02 * i, 0, -0.01 * i)) - (f | sphere(0.12).translate((0.3, 0.1 * (i % 3), 0))).translate((0.03, -0.02, 0.01))
+f = (f | capsule(-X, X, 0.15)).translate((0.05, 0, 0))
+""",
+    # plain (8,8): 5 point slots, one more than the (4,4) file holds
+    'slots_plain_8_8_p5': """
+f = box(0.5)
+for i in range(6):
+    f = (f | sphere(0.25).translate((0.4, 0, 0)).k(0.05)).translate((-0.1, 0.1, 0.05))
+""",
+    # trig (2,4): 1 + 3
+    'slots_trig_2_4': """
+f = box(0.5).twist(1.0)
+for i in range(4):
+    f = box(1.0 + 0.3 * i).twist(0.5) - f
+""",
+    # trig (4,4): 3 + 3
+    'slots_trig_4_4': """
+f = box(0.5)
+for i in range(4):
+    f = (f | (torus(0.5, 0.1) - (box(0.3) & (sphere(0.2) | box(0.1)).translate((0.2, 0, 0))))).twist(0.3).translate((-0.1, 0.1, 0.05))
+""",
+    # trig (8,8): 7 + 4 over more than 96 instructions (the library picks the two-pass scheme on its own)
+    'slots_trig_8_8': """
+f = capsule(-X * 0.2, X * 0.2, 0.1)
+for i in range(4):
+    f = (f | sphere(0.1)).translate((0.15, 0, 0)).circular_array(3, 0)
+""",
+}
+
+
 def build(name, namespace):
     """exec the fixture program in a copy of `namespace` and return its ``f``."""
     ns = dict(namespace)
-    exec(FIXTURES[name] if name in FIXTURES else CUSTOM_FIXTURES[name], ns)
+    for table in (FIXTURES, CUSTOM_FIXTURES, SLOT_FIXTURES):
+        if name in table:
+            exec(table[name], ns)
+            break
+    else:
+        raise KeyError(name)
     return ns['f']

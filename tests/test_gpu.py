@@ -9,7 +9,9 @@ import pytest
 
 import fixtures
 from conftest import GOLDEN, ROOT, value_tolerance
-from sdf_amd import core
+from sdf_amd import core, tape
+from sdf_amd.engine import SdfStats
+from test_register_slots import files_holding, is_trig
 
 pytestmark = pytest.mark.gpu
 
@@ -736,14 +738,23 @@ def _random_array_tree(rng, ns):
 
 
 @pytest.mark.parametrize('seed', range(24))
-def test_interval_passes_with_arrays_and_bends_random(seed, ns, eng):
+def test_interval_passes_with_arrays_and_bends_random(seed, ns, oracle_lib, eng):
+    """on / off identity, and the soup against the tree-walking checker: these trees are what reaches the trig (2,4) and
+    (4,4) register files of k_mesh (tests/test_register_slots.py) among the random models"""
     rng = np.random.default_rng(7000 + seed)
     f = _random_array_tree(rng, ns)
     n = 93 + 5 * (seed % 4)
     X = np.arange(-1.5, 1.5, 3.0 / n); Y = np.arange(-1.5, 1.5, 3.0 / n) + 0.003; Z = np.arange(-1.5, 1.5, 3.0 / n) - 0.001
-    (p1, k1, s1), (p0, k0, s0) = _both_ways(eng, f, X, Y, Z, sparse=seed % 3 != 0)
+    sparse = seed % 3 != 0
+    (p1, k1, s1), (p0, k0, s0) = _both_ways(eng, f, X, Y, Z, sparse=sparse)
     assert s0['n_pruned_instrs'] == 0
     assert np.array_equal(k1, k0) and p1.shape == p0.shape and np.array_equal(p1, p0)
+    o = oracle_lib.generate(f, X, Y, Z, 32, sparse)
+    assert np.array_equal(k1, o.kinds) and s1['n_eval_voxels'] == o.n_eval
+    assert p1.shape == o.points.shape
+    if len(p1):                                                     # north-star tolerance (libm on the way)
+        assert np.abs(p1 - o.points).max() <= 1e-5 * 3.0
+        assert (p1 == o.points).mean() > 0.999
 
 
 # ---- vertex weld on the device (reference sdf/core.py:160-164: np.unique(points, axis=0, return_inverse=True)) ----
@@ -1889,3 +1900,142 @@ def test_generate_drop_in_returns_the_reference_soup_through_records(ns):
         f = fixtures.build('ex_blobby', ns)
         pts = f.generate(samples=2 ** 20, verbose=False)
         assert hashlib.sha256(pts.tobytes()).digest() == d['sha256'].tobytes()
+
+
+# ---- every register file of k_mesh: sdf_mesh_inst.hip is built for the plain and the trig family, each with six register files
+# (saved-point, saved-distance slots) and two schemes (one pass / k_mesh + k_scan_items + k_emit2).  The models of
+# fixtures.SLOT_FIXTURES reach the files the value fixtures do not (tests/test_register_slots.py checks which file each one
+# lowers to); here each is meshed under both schemes and compared with the tree-walking checker. ----
+
+SLOTS = sorted(fixtures.SLOT_FIXTURES)
+BOUNDS_SLOTS = np.load(os.path.join(GOLDEN, 'bounds_slots.npz'))
+VALUES_SLOTS = np.load(os.path.join(GOLDEN, 'values_slots.npz'))
+_SLOT_ORACLE = {}          # (model, batch size, sparse) -> the checker's generate, shared by the two schemes
+
+
+def _slot_grid(name):
+    """about 2^20 samples over the reference's bounds; no axis is a multiple of either batch size (32, 13): the last batch on
+    every axis is ragged"""
+    lo, hi = BOUNDS_SLOTS[name]
+    return tuple(np.linspace(lo[i], hi[i], n) for i, n in enumerate((103, 97, 105)))
+
+
+@pytest.mark.parametrize('scheme', [0, 1], ids=['one_pass', 'two_pass'])
+@pytest.mark.parametrize('name', SLOTS)
+def test_register_files_and_schemes_match_the_checker(name, scheme, ns, oracle_lib, eng):
+    f = fixtures.build(name, ns)
+    trig = is_trig(tape.lower(f))
+    X, Y, Z = _slot_grid(name)
+    extent = max(X[-1] - X[0], Y[-1] - Y[0], Z[-1] - Z[0])
+    eng.set_twopass(scheme)
+    try:
+        soups = {}
+        for bs in (32, 13):
+            for sparse in (True, False):
+                key = (name, bs, sparse)
+                o = _SLOT_ORACLE.pop(key, None) if scheme else _SLOT_ORACLE.get(key)
+                if o is None:
+                    o = oracle_lib.generate(f, X, Y, Z, bs, sparse)
+                    if not scheme:
+                        _SLOT_ORACLE[key] = o
+                m = eng.generate(f, X, Y, Z, bs, sparse)
+                pts, kinds, st, offs = m.points(), m.kinds(), m.stats(), m.batch_offsets()
+                m.close()
+                where = (name, scheme, bs, sparse)
+                assert np.array_equal(kinds, o.kinds), where
+                assert (st['skipped'], st['empty'], st['nonempty']) == tuple(int((o.kinds == k).sum()) for k in (0, 1, 2)), where
+                assert st['n_eval_voxels'] == o.n_eval and st['triangles'] == len(o.points) // 3, where
+                assert offs[0] == 0 and offs[-1] == len(o.points) // 3 and np.array_equal(np.diff(offs) > 0, o.kinds == 2), where
+                assert pts.shape == o.points.shape, where
+                if trig:
+                    assert np.abs(pts - o.points).max() <= 1e-5 * extent, where       # north-star tolerance
+                    assert (pts == o.points).mean() > 0.999, where
+                else:
+                    assert np.array_equal(pts, o.points), where
+                soups[bs, sparse] = pts
+        assert (o.kinds == 2).sum() >= 100                  # (the last one: batch size 13, dense)
+        # the interval passes (prepass at this file's LDS size, culling at its interval state) change no bit
+        (p1, k1, s1), (p0, k0, s0) = _both_ways(eng, f, X, Y, Z)
+        assert s0['n_pruned_instrs'] == 0 and s0['n_sampled_voxels'] == s0['n_eval_voxels']
+        assert np.array_equal(k1, k0) and np.array_equal(p1, p0) and np.array_equal(p1, soups[32, True])
+    finally:
+        eng.set_twopass(-1)
+    if scheme == 0:                # the records path (16-byte records, the soup made on host threads): once per model
+        m = eng.generate(f, X, Y, Z, 32, True, records=True)
+        got = m.points()
+        m.close()
+        assert got.shape == soups[32, True].shape and np.array_equal(got.view(np.uint64), soups[32, True].view(np.uint64))
+    # f(P) on the device (the evaluation kernels, not k_mesh) against the checker and the reference
+    P = VALUES_SLOTS['P']
+    v, o, ref = eng.eval_points(f, P), oracle_lib.evaluate(f, P), VALUES_SLOTS['v_' + name]
+    assert np.array_equal(np.isnan(v), np.isnan(o))
+    ok = ~np.isnan(o)
+    if trig:
+        assert np.all(np.abs(v[ok] - o[ok]) <= value_tolerance(o[ok], P[ok]))
+    else:
+        assert np.array_equal(v, o, equal_nan=True)
+    ok = ~np.isnan(ref)
+    assert np.all(np.abs(v[ok] - ref[ok]) <= value_tolerance(ref[ok], P[ok]))
+
+
+FORCED = ['ex_example', 'ex_gearlike', 'ex_pawn', 'slots_plain_4_2']
+# every count of sdf_stats but the capacity retries (a fresh context has no size hint yet); the times are not compared
+_COUNTS = [k for k, _ in SdfStats._fields_ if k.startswith('n_') and k != 'n_retries'] + ['mesh_kernel']
+
+
+@pytest.mark.parametrize('name', FORCED)
+def test_forced_register_file_gives_the_same_soup(name, ns, eng, monkeypatch):
+    """SDF_MESH_SLOTS (read when a context is created) forces any register file that holds the tape: which one meshes is a
+    register-allocation choice and must not change a bit -- soup, classification, batch offsets and every count, under both
+    schemes, are the session engine's (which takes the smallest file)"""
+    from sdf_amd import engine
+    f = fixtures.build(name, ns)
+    t = tape.lower(f)
+    files = files_holding(t)
+    assert len(files) >= 3, (name, files)
+    bounds = BOUNDS[name] if name in BOUNDS.files else BOUNDS_SLOTS[name]
+    X, Y, Z, _ = core.grid_axes(tuple(map(tuple, bounds)), samples=2 ** 18)
+    m = eng.generate(f, X, Y, Z, 32, True)
+    want = (m.points(), m.kinds(), m.batch_offsets(), m.stats())
+    m.close()
+    assert want[3]['nonempty'] > 0
+    for k in files:
+        monkeypatch.setenv('SDF_MESH_SLOTS', str(k))
+        for scheme in (0, 1):
+            e = engine.Engine(0)
+            dt = engine.DeviceTape(e, t)
+            try:
+                e.set_twopass(scheme)
+                m = e.generate(dt, X, Y, Z, 32, True)
+                got = (m.points(), m.kinds(), m.batch_offsets(), m.stats())
+                m.close()
+            finally:
+                dt._fin(); e._fin()
+            where = (name, k, scheme)
+            assert got[0].shape == want[0].shape and np.array_equal(got[0].view(np.uint64), want[0].view(np.uint64)), where
+            assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), where
+            assert [got[3][c] for c in _COUNTS] == [want[3][c] for c in _COUNTS], where
+
+
+def test_device_tape_refuses_a_ninth_slot(ns, oracle_lib, eng):
+    """validate_tape (csrc/sdf_hip.hip) refuses a tape that declares more slots than the (8,8) register file holds; one that
+    declares exactly 8 + 8 is accepted and meshed by that file"""
+    from sdf_amd import engine
+    f = ns['sphere'](1) & ns['box'](1.5)
+    t = tape.lower(f)
+    for n_p, n_d in ((9, 1), (1, 9), (9, 9)):
+        with pytest.raises(engine.SdfHipError, match='more register slots'):
+            engine.DeviceTape(eng, tape.Tape(t.code, t.consts, n_p, n_d, 3))
+    dt = engine.DeviceTape(eng, tape.Tape(t.code, t.consts, 8, 8, 3))
+    X, Y, Z, _ = core.grid_axes(((-0.85, -0.85, -0.85), (0.85, 0.85, 0.85)), samples=2 ** 18)
+    o = oracle_lib.generate(f, X, Y, Z, 32, True)
+    try:
+        for scheme in (0, 1):
+            eng.set_twopass(scheme)
+            m = eng.generate(dt, X, Y, Z, 32, True)
+            pts, kinds = m.points(), m.kinds()
+            m.close()
+            assert np.array_equal(kinds, o.kinds) and np.array_equal(pts, o.points), scheme
+    finally:
+        eng.set_twopass(-1)
+        dt._fin()

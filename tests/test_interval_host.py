@@ -110,3 +110,18 @@ def test_interval_run_of_every_fixture_tape_encloses_the_checker(name, tape_lib,
     import fixtures
     tight = name.startswith('ex_') or name in ('sphere', 'box2', 'torus', 'capsule', 'smooth_union', 'twist', 'bend', 'repeat3', 'circular_array')
     _check_tape_enclosure(name, fixtures.build(name, ns), tape_lib, oracle_lib, golden_values['P'], zlib.crc32(name.encode()), tight=tight)
+
+
+def _slot_fixture_names():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import fixtures
+    return sorted(fixtures.SLOT_FIXTURES)
+
+
+@pytest.mark.parametrize('name', _slot_fixture_names())
+def test_interval_run_of_slot_models_encloses_the_checker(name, tape_lib, ns, golden_values, oracle_lib):
+    """the same on the models that need up to 8 saved-point / saved-distance slots (fixtures.SLOT_FIXTURES): the tape's slot
+    numbering against the tree-walking checker, through every slot of ia_run_tape's state"""
+    import fixtures
+    _check_tape_enclosure(name, fixtures.build(name, ns), tape_lib, oracle_lib, golden_values['P'], zlib.crc32(name.encode()), tight=True)

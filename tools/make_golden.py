@@ -22,6 +22,9 @@ What is recorded:
   mc_classic_probe.npz  the per-configuration triangle lists skimage emits for the 256 sign
                  configurations of one cell (method='lorensen' and 'lewiner'), from which
                  tools/derive_mc_tables.py builds the lookup table used by oracle and kernels
+  values_slots.npz, bounds_slots.npz, gen_slots_*.npz   (target `slots`) the same three records for
+                 fixtures.SLOT_FIXTURES, the models that reach every register-file variant of the meshing
+                 kernel; values.npz and bounds.npz are left as they are
 """
 import hashlib
 import os
@@ -63,22 +66,22 @@ def shared_points():
     return np.concatenate([a, b, c, d]).astype(np.float64)
 
 
-def gen_values():
+def gen_values(table=fixtures.FIXTURES, fname='values.npz'):
     P = shared_points()
     out = {'P': P}
-    for name in fixtures.FIXTURES:
+    for name in table:
         f = fixtures.build(name, NS)
         with np.errstate(all='ignore'):
             v = f(P.copy()).reshape(-1)
         assert v.dtype == np.float64 and v.shape == (len(P),)
         out['v_' + name] = v
-    np.savez_compressed(os.path.join(OUT, 'values.npz'), **out)
-    print('values.npz', len(fixtures.FIXTURES), 'fixtures x', len(P), 'points')
+    np.savez_compressed(os.path.join(OUT, fname), **out)
+    print(fname, len(table), 'fixtures x', len(P), 'points')
 
 
-def gen_bounds():
+def gen_bounds(table=fixtures.FIXTURES, fname='bounds.npz'):
     out = {}
-    for name in fixtures.FIXTURES:
+    for name in table:
         if name in ('ex_custbox',):      # 1e9-sized model: estimator output not meaningful
             continue
         f = fixtures.build(name, NS)
@@ -88,8 +91,8 @@ def gen_bounds():
             out[name] = np.array(b, dtype=np.float64)
         except Exception as e:           # reference crashes on empty `where` (core.py:63 TODO)
             print('bounds failed for', name, type(e).__name__)
-    np.savez_compressed(os.path.join(OUT, 'bounds.npz'), **out)
-    print('bounds.npz', len(out))
+    np.savez_compressed(os.path.join(OUT, fname), **out)
+    print(fname, len(out))
 
 
 def mc_soup(volume):
@@ -261,6 +264,18 @@ def gen_generate():
         np.savez_compressed(os.path.join(OUT, 'gen_%s.npz' % tag), **rec)
 
 
+def gen_slots():
+    """values, bounds and one full soup of the register-slot models (fixtures.SLOT_FIXTURES)"""
+    gen_values(fixtures.SLOT_FIXTURES, 'values_slots.npz')
+    gen_bounds(fixtures.SLOT_FIXTURES, 'bounds_slots.npz')
+    # eight saved-distance slots, no BLAS on the way (no rotate): bit-compared by the generate parity test
+    kw = dict(samples=2 ** 16)
+    rec = run_generate('slots_plain_8_8_d8', True, **dict(kw))
+    rec['fixture'] = np.array('slots_plain_8_8_d8')
+    rec['kwargs'] = np.array(repr(kw))
+    np.savez_compressed(os.path.join(OUT, 'gen_slots_plain_8_8_d8_s16.npz'), **rec)
+
+
 def gen_stl():
     """byte-exact STL of a small soup (reference sdf/stl.py:4-24)"""
     import tempfile
@@ -276,10 +291,11 @@ def gen_stl():
 
 
 if __name__ == '__main__':
-    what = sys.argv[1:] or ['values', 'bounds', 'mc', 'probe', 'generate', 'stl']
+    what = sys.argv[1:] or ['values', 'bounds', 'mc', 'probe', 'generate', 'stl', 'slots']
     if 'values' in what: gen_values()
     if 'bounds' in what: gen_bounds()
     if 'mc' in what: gen_mc()
     if 'probe' in what: gen_mc_probe()
     if 'generate' in what: gen_generate()
     if 'stl' in what: gen_stl()
+    if 'slots' in what: gen_slots()
