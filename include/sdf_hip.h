@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 10
+#define SDF_ABI_VERSION 11
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -142,6 +142,21 @@ int sdf_eval_extern_points_host(sdf_tape *tape, const double *h_points, int64_t 
                                 int precision);
 int sdf_eval_points_extern_host(sdf_tape *tape, const double *h_points, int64_t n, int dim, const double *h_ext_values,
                                 double *h_out, int precision);
+/* Triangle mesh -> dense narrow-band signed-distance grid (ABI 11; replaces OpenVDB's createLevelSetFromPolygons +
+ * copyToArray in `Mesh.sdf`, reference sdf/mesh.py:64-113).  h_points: n_points x 3 float64, h_tris: n_tris x 3 indices.
+ * Voxel (i, j, k) sits at (i, j, k) * voxel_size; its value is float32(min(d, background)), negated when an odd number of
+ * triangles cross its +z column below it, with d the exact float64 distance to the nearest triangle and background =
+ * float32(half_width_voxels * voxel_size).  The result is the index box of the voxels with
+ * |value| < background: its first voxel in out_ijk0, its shape in out_dims, the values in h_out, C order [i][j][k].
+ * Synchronous.  Like sdf_marching_cubes_host, when prod(out_dims) > cap_voxels (or h_out is NULL) the dims are reported
+ * and nothing is filled: call again with a larger buffer.  The arguments are checked on the host before anything is
+ * uploaded (an empty mesh, an index out of range, a non-finite point, voxel_size <= 0, a work grid larger than the free
+ * device memory allows): those return 2, other failures 1.  Device memory is allocated for the call and freed before
+ * it returns. */
+int sdf_mesh_level_set_host(sdf_ctx *ctx, const double *h_points, int64_t n_points, const int32_t *h_tris, int64_t n_tris,
+                            double voxel_size, int half_width_voxels, int64_t out_ijk0[3], int64_t out_dims[3], float *h_out,
+                            int64_t cap_voxels);
+
 /* The batch loop of `generate` (reference sdf/core.py:114-141) around a field evaluated by a HOST callback:
  * `field(user, points (n x 3 float64, host), n, values (n float64, host))` returns 0, or non-zero to abort.  The
  * library builds the points of the skip test (`_skip`, core.py:28-43) and of every surviving batch

@@ -536,6 +536,8 @@ struct sdf_mesh {
 
 namespace sdfk {
 int weld_device(hipStream_t stream, const double *pts, long long n, double **d_uniq, long long **d_inv, long long *n_unique);   // sdf_weld.hip
+int level_set_host(hipStream_t st, const double *h_pts, long long np, const int32_t *h_tris, long long nt, double vs, int hw,
+                   int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, long long cap, std::string &err);           // sdf_level_set.hip
 }
 
 static bool tape_needs_full(const uint32_t *code, uint32_t n_words, const double *consts) {
@@ -1026,6 +1028,16 @@ int sdf_marching_cubes_host(sdf_ctx *c, const float *h_vol, int n0, int n1, int 
         HIPCHK(hipMemcpyAsync(h_out, c->scratch_out.p, (size_t)ncopy * 36, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(stream_wait(c->stream));
     }
+    return 0;
+}
+
+int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t n_pts, const int32_t *h_tris, int64_t n_tris, double vs, int hw,
+                            int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, int64_t cap) {
+    if (!c || !out_ijk0 || !out_dims) return fail("sdf_mesh_level_set_host: NULL argument");
+    HIPCHK(set_device(c->device));
+    std::string err;
+    const int rc = sdfk::level_set_host(c->stream, h_pts, n_pts, h_tris, n_tris, vs, hw, out_ijk0, out_dims, h_out, cap, err);
+    if (rc) { fail("sdf_mesh_level_set_host: " + err); return rc; }
     return 0;
 }
 

@@ -90,6 +90,8 @@ ABI = {
                                           _c_i64, ctypes.POINTER(_c_i64)]),
     'sdf_marching_cubes_host': (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                _f32p, _c_i64, ctypes.POINTER(_c_i64)]),
+    'sdf_mesh_level_set_host': (ctypes.c_int, [_vp, _f64p, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_double,
+                                               ctypes.c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _f32p, _c_i64]),
     'sdf_generate': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int,
                                     ctypes.POINTER(_vp)]),
@@ -139,7 +141,7 @@ ABI = {
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def build_info():
@@ -639,6 +641,46 @@ class Engine:
             if nt.value <= cap:
                 return out[:nt.value].reshape(-1, 3)
             cap = nt.value
+
+    def mesh_level_set(self, points, triangles, voxel_size, half_width_voxels):
+        """the narrow-band signed-distance grid of a triangle mesh (sdf_mesh_level_set_host; what OpenVDB's
+        createLevelSetFromPolygons + copyToArray give the reference's `Mesh.sdf`): returns
+        (ijk0, A) with A the float32 values of the voxels ijk0 + [0, A.shape), voxel (i, j, k) at (i, j, k) * voxel_size.
+        Raises ValueError, before any device work, for an empty mesh, an index out of range, a non-finite point,
+        voxel_size <= 0 or a work grid larger than the device memory allows."""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        tri = np.asarray(triangles)
+        if pts.ndim != 2 or pts.shape[1] != 3 or tri.ndim != 2 or tri.shape[1] != 3:
+            raise ValueError('points must be (V, 3) and triangles (T, 3), got %s and %s' % (pts.shape, tri.shape))
+        if len(pts) == 0 or len(tri) == 0:
+            raise ValueError('empty mesh: %d points, %d triangles' % (len(pts), len(tri)))
+        if not np.all(np.isfinite(pts)):
+            raise ValueError('the mesh has non-finite points')
+        if tri.min() < 0 or tri.max() >= len(pts):
+            raise ValueError('triangle indices must lie in [0, %d), got %d .. %d' % (len(pts), tri.min(), tri.max()))
+        vs = float(voxel_size)
+        if not (vs > 0 and np.isfinite(vs)):
+            raise ValueError('voxel_size must be positive, got %r' % voxel_size)
+        tri = np.ascontiguousarray(tri, dtype=np.int32)
+        hw = int(half_width_voxels)
+        # the work grid bounds the result: one call in the usual case
+        lo = np.floor(pts.min(axis=0) / vs) - hw - 1
+        hi = np.ceil(pts.max(axis=0) / vs) + hw + 1
+        cap = int(min(np.prod(hi - lo + 1), 1 << 28))
+        ijk0, dims = (_c_i64 * 3)(), (_c_i64 * 3)()
+        while True:
+            out = np.empty(cap, np.float32)
+            rc = self.lib.sdf_mesh_level_set_host(self.ctx, _dp(pts, _f64p), len(pts), _dp(tri, ctypes.POINTER(ctypes.c_int32)), len(tri), vs,
+                                                  hw, ijk0, dims, _dp(out, _f32p), cap)
+            if rc == 2:
+                raise ValueError(self.lib.sdf_last_error().decode())
+            _check(self.lib, rc)
+            n = int(np.prod(list(dims)))
+            if n == 0:
+                raise ValueError('no voxel lies within the narrow band of this mesh')
+            if n <= cap:
+                return np.array(list(ijk0), dtype=np.int64), out[:n].reshape(tuple(dims))
+            cap = n
 
     def generate(self, sdf, X, Y, Z, batch_size=32, sparse=True, shard=(0, 1), out_ptr=None, out_cap=0, wait=True, records=False):
         """mesh the grid X x Y x Z.  records=True (one device, the whole work list, no output buffer): for a

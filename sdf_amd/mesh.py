@@ -9,7 +9,9 @@ the tape's constants and the interpreter does the trilinear interpolation per sa
 
 `grid_sdf` builds the leaf from a ready voxel grid (any producer); `Mesh.sdf` is the reference's
 entry point and needs `pyopenvdb` for the voxelisation step only -- without it the import fails
-exactly where the reference's does (reference sdf/mesh.py:66).
+exactly where the reference's does (reference sdf/mesh.py:66).  `level_set` (`Mesh.sdf(...,
+voxelizer='device')`) makes the grid on the device instead (csrc/sdf_level_set.hip, DESIGN.md
+section 4c); `Mesh.from_stl` reads a binary STL without meshio.
 """
 import numpy as np
 
@@ -38,6 +40,34 @@ def grid_sdf(xyz, array, background, bounding_box):
     return f
 
 
+def half_width_voxels(voxel_size, half_width=None):
+    """the narrow band in voxels (reference sdf/mesh.py:73-77): 3, or ceil(half_width / voxel_size) if that is larger"""
+    hw = 3
+    if half_width is not None:
+        hw = max(hw, int(np.ceil(half_width / voxel_size)))
+    return hw
+
+
+def level_set(points, triangles, voxel_size, half_width=None):
+    """`Mesh.sdf` with the voxelisation on the device (csrc/sdf_level_set.hip) instead of OpenVDB's: the grid_sdf of the
+    dense narrow-band grid of the mesh, cropped to the voxels with |value| < background like the reference's
+    `evalActiveVoxelBoundingBox` + `copyToArray` (reference sdf/mesh.py:79-92).  The returned SDF3 carries the grid:
+    `f.array`, `f.xyz`, `f.ijk0` (index of array[0, 0, 0]) and `f.background`."""
+    from . import engine
+    points = np.asarray(points, dtype=np.float64)
+    hw = half_width_voxels(voxel_size, half_width)
+    ijk0, A = engine.get_engine().mesh_level_set(points, triangles, voxel_size, hw)
+    size = np.array(A.shape)
+    ijk1 = ijk0 + size - 1
+    p0, p1 = ijk0 * float(voxel_size), ijk1 * float(voxel_size)     # indexToWorld of a linear transform
+    xyz = tuple(np.linspace(p0[i], p1[i], size[i]) for i in range(3))
+    background = float(np.float32(hw * voxel_size))
+    lo, hi = points.min(axis=0), points.max(axis=0)
+    f = grid_sdf(xyz, A, background, (tuple(lo.tolist()), tuple(hi.tolist())))
+    f.ijk0, f.background = ijk0, background
+    return f
+
+
 class Mesh:
     """reference sdf/mesh.py:8-62: points (V, 3), triangles (T, 3) and rigid / scaling transforms"""
 
@@ -50,6 +80,21 @@ class Mesh:
         import meshio
         m = meshio.read(path)
         return cls(m.points, m.cells[0].data)
+
+    @classmethod
+    def from_stl(cls, path):
+        """a binary STL (80-byte header, u32 count, 50-byte records) without meshio, its vertices welded like the
+        reference's `_mesh` welds a soup (reference sdf/core.py:160-164): np.unique(points, axis=0, return_inverse=True)"""
+        with open(path, 'rb') as fp:
+            data = fp.read()
+        if len(data) < 84:
+            raise ValueError('%s: %d bytes is too short for a binary STL' % (path, len(data)))
+        n = int(np.frombuffer(data, dtype='<u4', count=1, offset=80)[0])
+        if len(data) != 84 + 50 * n:
+            raise ValueError('%s: %d bytes, but a binary STL of %d triangles has %d' % (path, len(data), n, 84 + 50 * n))
+        rec = np.frombuffer(data, dtype=np.dtype([('normal', '<f4', 3), ('points', '<f4', (3, 3)), ('attr', '<u2')]), count=n, offset=84)
+        points, cells = np.unique(rec['points'].reshape(-1, 3).astype(np.float64), axis=0, return_inverse=True)
+        return cls(points, np.asarray(cells).reshape((-1, 3)))
 
     @property
     def bounding_box(self):
@@ -83,17 +128,18 @@ class Mesh:
     def centered(self):
         return self.positioned((0, 0, 0), (0.5, 0.5, 0.5))
 
-    def sdf(self, voxel_size, half_width=None):
-        """reference sdf/mesh.py:64-113; the voxelisation is OpenVDB's (host, like the reference),
-        the per-sample lookup runs on the device"""
+    def sdf(self, voxel_size, half_width=None, voxelizer='openvdb'):
+        """reference sdf/mesh.py:64-113; the voxelisation is OpenVDB's (host, like the reference) unless
+        voxelizer='device' (`level_set`: on the device, no OpenVDB); the per-sample lookup runs on the device"""
+        if voxelizer == 'device':
+            return level_set(self.points, self.triangles, voxel_size, half_width)
+        if voxelizer != 'openvdb':
+            raise ValueError("voxelizer must be 'openvdb' or 'device', got %r" % (voxelizer,))
         import pyopenvdb as vdb
 
-        half_width_voxels = 3
-        if half_width is not None:
-            half_width_voxels = max(half_width_voxels, int(np.ceil(half_width / voxel_size)))
         grid = vdb.FloatGrid.createLevelSetFromPolygons(
             self.points, triangles=self.triangles,
-            transform=vdb.createLinearTransform(voxelSize=voxel_size), halfWidth=half_width_voxels)
+            transform=vdb.createLinearTransform(voxelSize=voxel_size), halfWidth=half_width_voxels(voxel_size, half_width))
         v0, v1 = grid.evalActiveVoxelBoundingBox()
         ijk0, ijk1 = np.array(v0, dtype=int), np.array(v1, dtype=int)
         size = ijk1 - ijk0 + 1
