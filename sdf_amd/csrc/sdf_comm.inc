@@ -123,7 +123,8 @@ static int exchange_submit(sdf_exchange *x) {
     const int world = cm->world, rank = cm->rank, C = x->chunks, S = world * C;
     const double *X = x->axes.data(), *Y = X + x->nx, *Z = Y + x->ny;
     const int bs = x->bs;
-    const long long nb = (long long)((x->nx + bs - 1) / bs) * ((x->ny + bs - 1) / bs) * ((x->nz + bs - 1) / bs);
+    GridDesc grid;
+    const long long nb = grid_desc(x->nx, x->ny, x->nz, bs, grid);
     const size_t sb = SlabLayout(x->cap_items, x->cap_tris).bytes;
     x->slab_bytes = sb;
     if (L.mine.ensure((size_t)C * sb) || L.gathered.ensure((size_t)S * sb) || L.soup.ensure((size_t)std::max<int64_t>(x->out_cap, 1) * 72) ||
@@ -150,9 +151,10 @@ static int exchange_submit(sdf_exchange *x) {
         m->ctx = c;
         x->meshes[(size_t)j] = m;
         unsigned char *mine = (unsigned char *)L.mine.p + (size_t)j * sb;
-        if (generate_impl(x->tape, m, X, x->nx, Y, x->ny, Z, x->nz, bs, x->sparse, (int64_t)rank * C + j, (int64_t)S, x->precision, mine,
-                          x->cap_tris, true, x->cap_items, L.stream, d_kinds))
-            return 1;
+        GenCall call = gen_call(x->tape, X, x->nx, Y, x->ny, Z, x->nz, bs, x->sparse, (int64_t)rank * C + j, (int64_t)S, x->precision);
+        call.dest = GenCall::SLAB; call.d_out = mine; call.cap_items = x->cap_items; call.cap_tris = x->cap_tris;
+        call.collected = true; call.lane = L.stream; call.d_kinds = d_kinds;
+        if (generate_impl(m, call)) return 1;
         unsigned char *g = (unsigned char *)L.gathered.p + (size_t)j * world * sb;
         if (C == 1) {
             HIPCHK(hipEventRecord(L.ev[1], L.stream));
@@ -312,7 +314,8 @@ int sdf_generate_sharded_async(sdf_comm *cm, sdf_tape *t, const double *X, int n
     // rank, and a capacity inherited on one rank only would give the ranks slabs of different sizes in one all-gather)
     snprintf(key, sizeof key, "%016llx:%u:%d:%d:%d:%d:%d:%d:%d", t->content_hash, t->n_words, nx, ny, nz, bs, x->sparse, precision, x->chunks);
     x->key = key;
-    const long long nb = (long long)((nx + bs - 1) / bs) * ((ny + bs - 1) / bs) * ((nz + bs - 1) / bs);
+    GridDesc grid;
+    const long long nb = grid_desc(nx, ny, nz, bs, grid);
     auto it = cm->hints.find(x->key);
     if (it != cm->hints.end()) {
         x->cap_items = it->second.cap_items; x->cap_tris = it->second.cap_tris;
@@ -370,8 +373,8 @@ int sdf_exchange_wait(sdf_exchange *x, void **d_soup, int64_t *n_tris) {
         cm->hints[x->key] = sdf_comm::Hint{need_items + need_items / 8 + 16, need_tris + need_tris / 64 + 1024, total};
         sdf_exchange_stats &st = x->st;
         st = sdf_exchange_stats{};
-        const int bs = x->bs;
-        st.n_batches = (int64_t)((x->nx + bs - 1) / bs) * ((x->ny + bs - 1) / bs) * ((x->nz + bs - 1) / bs);
+        GridDesc grid;
+        st.n_batches = (int64_t)grid_desc(x->nx, x->ny, x->nz, x->bs, grid);
         st.n_skipped = st.n_batches - heads[9];
         st.n_grid_voxels = (int64_t)x->nx * x->ny * x->nz;
         st.n_triangles = total; st.n_retries = x->attempt; st.chunks = C; st.world = world; st.slab_bytes = (int64_t)x->slab_bytes;
@@ -403,8 +406,9 @@ int sdf_skip_kinds(sdf_tape *t, const double *X, int nx, const double *Y, int ny
     if (bs < 1 || bs > 32) return fail("sdf_skip_kinds: batch_size must be in 1..32");
     if (precision != SDF_PRECISION_F64 && precision != SDF_PRECISION_F32) return fail("sdf_skip_kinds: bad precision");
     if (nx < 0 || ny < 0 || nz < 0) return fail("sdf_skip_kinds: negative axis length");
-    const long long nb = (long long)((nx + bs - 1) / bs) * ((ny + bs - 1) / bs) * ((nz + bs - 1) / bs);
-    if (nb > 0x7fffffffLL) return fail("sdf_skip_kinds: too many batches");
+    GridDesc grid;
+    int nb = 0;
+    if (grid_batches(nx, ny, nz, bs, "sdf_skip_kinds", grid, nb)) return 1;
     if (b_begin < 0 || b_end < b_begin || b_end > nb) return fail("sdf_skip_kinds: batch range outside the grid");
     if (b_begin == b_end) return 0;
     sdf_ctx *c = t->ctx;

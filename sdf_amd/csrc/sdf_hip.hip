@@ -468,7 +468,7 @@ struct sdf_ctx {
     int tail_order = 1;               // SDF_TAIL_ORDER=0: k_mesh takes the whole work list in order
     int twopass = -1;                 // SDF_MESH_TWOPASS=0 / 1: force the one-pass k_mesh (look-back + parking) resp. k_mesh / k_scan_items / k_emit2
     int defer = 1;                    // SDF_DEFER=0: k_mesh keeps every tile dense and writes (or parks) a batch's triangles right after counting it
-    int cull_levels = 0;              // SDF_CULL_LEVELS=2 / 3: interval levels of k_cull (3: + sub-groups of 2^3 cells); 0: by the tape (see generate_impl)
+    int cull_levels = 0;              // SDF_CULL_LEVELS=2 / 3: interval levels of k_cull (3: + sub-groups of 2^3 cells); 0: by the tape (see enqueue_cull)
     DevBuf bounds_work;               // k_estimate_bounds_w: the waves' exchange words (tagged per call, sdf_bounds.hip)
     unsigned bounds_tag = 0, bounds_tag0 = 0;
     // sdf_generate_records: what the last call of a MODEL (content hash) on a grid needed -- triangles, raw-area triangles -- so that the
@@ -497,6 +497,28 @@ struct sdf_tape {
                                                             // on every rank alike and whatever address the tape object lands on (sdf_comm.inc)
 };
 
+// What one fused call (prepass -> k_cull -> k_mesh) is asked to do.  The entry points build one by naming fields; a call in
+// flight keeps its descriptor in sdf_mesh::Pending.
+struct GenCall {
+    sdf_tape *tape = nullptr;
+    const double *X = nullptr, *Y = nullptr, *Z = nullptr;   // the host's axes
+    int nx = 0, ny = 0, nz = 0, bs = 0, sparse = 0, precision = 0;
+    int64_t shard_index = 0, shard_count = 1;
+    // where the triangles go.  SOUP: a library buffer sized from the last call of the tape on the grid; CALLER: d_out, cap_tris
+    // float64 triangles; SLAB: compact mode (sdf_generate_compact_async, sdf_generate_records) -- d_out is a SLAB of capacity
+    // (cap_items, cap_tris)
+    enum Dest { SOUP, CALLER, SLAB } dest = SOUP;
+    void *d_out = nullptr;
+    int64_t cap_tris = 0, cap_items = 0;
+    bool collected = false;                   // the call returns in flight and sdf_mesh_wait finishes it (else: synchronous)
+    hipStream_t lane = nullptr;               // the stream the whole call is enqueued on (the exchange steps of sdf_comm run on lanes of their own)
+    // the skip test's verdict for every batch is already on the device (0 skipped / 255 pending, n_batches
+    // bytes: sdf_skip_kinds, possibly all-gathered from the ranks that each tested a share): k_skip is not run
+    const unsigned char *d_kinds = nullptr;
+};
+// ... and what the call learned while it was enqueued: finishing it needs these
+struct CallState { int slot = 0, nb = 0; bool pruning = false, own_start = false; uint32_t n_instr = 0; unsigned long long key = 0; };
+
 struct sdf_mesh {
     sdf_ctx *ctx = nullptr;
     sdf_stats st = {};
@@ -512,15 +534,9 @@ struct sdf_mesh {
     // sdf_generate_to_device_async: everything sdf_mesh_wait needs to finish the call
     struct Pending {
         bool active = false;
-        sdf_tape *tape = nullptr;
-        int slot = 0, nb = 0, bs = 0, sparse = 0, precision = 0;
-        bool pruning = false, own_start = false, compact = false;
-        uint32_t n_instr = 0;
-        unsigned long long key = 0;
-        void *d_out = nullptr;
-        int64_t cap_out = 0, shard_index = 0, shard_count = 1;
+        GenCall call;                  // (its axes point into `axes`)
         std::vector<double> axes;      // host copy (a soup that does not fit is re-run synchronously)
-        int nx = 0, ny = 0, nz = 0;
+        CallState got;
     } pend;
     double *weld_pts = nullptr;    // sdf_mesh_weld: unique rows / row -> unique row (hipMalloc'ed by sdf_weld.hip)
     long long *weld_inv = nullptr;
@@ -1043,27 +1059,61 @@ int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t n_pts, cons
 
 }  // extern "C"
 
+// The grid of a call: batches of bs cells per axis, without the device copies of the axes.  Returns the number of batches; a
+// batch size below 1 (sdf_generate_records asks before the batch size has been validated) gives a grid without batches.
+static long long grid_desc(int nx, int ny, int nz, int bs, GridDesc &g) {
+    g = GridDesc{};
+    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
+    if (bs < 1) return 0;
+    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
+    return (long long)g.nbx * g.nby * g.nbz;
+}
+// ... for an entry point that indexes the batches with an int (`who` names it in the message)
+static int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb) {
+    const long long nb64 = grid_desc(nx, ny, nz, bs, g);
+    if (nb64 > 0x7fffffffLL) return fail(std::string(who) + ": too many batches");
+    nb = (int)nb64;
+    return 0;
+}
+
+// a batch's first sample and its number of samples per axis: the host's copy of batch_origin (sdf_device.h)
+struct BatchBox { int ox, oy, oz, lx, ly, lz; };
+static BatchBox batch_box(const GridDesc &g, int b) {
+    const int ibz = b % g.nbz, iby = (b / g.nbz) % g.nby, ibx = b / (g.nbz * g.nby);
+    BatchBox o;
+    o.ox = ibx * g.bs; o.oy = iby * g.bs; o.oz = ibz * g.bs;
+    o.lx = std::min(g.bs + 1, g.nx - o.ox); o.ly = std::min(g.bs + 1, g.ny - o.oy); o.lz = std::min(g.bs + 1, g.nz - o.oz);
+    return o;
+}
+
+// k_mesh's dynamic LDS behind the fixed part: the float32 tile, the sign bits, the list region (which also receives the
+// batch's cull record) -- launch_mesh passes the layout to the kernel, generate_impl asks it whether a cull record fits
+struct MeshLds { size_t bits_off, list_off, list_cap; };
+static MeshLds mesh_lds(int bs, size_t lds_max) {
+    const size_t nvox = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
+    MeshLds l;
+    l.bits_off = (MESH_LDS_VOL + nvox * 4 + 15) & ~(size_t)15;
+    l.list_off = (l.bits_off + ((nvox + 63) / 64 + 2) * 8 + 15) & ~(size_t)15;
+    l.list_cap = lds_max > l.list_off ? std::min<size_t>((lds_max - l.list_off) / 4, 16384) : 0;
+    return l;
+}
+
 // k_mesh launch: the register-file variant is the smallest that holds the tape's slots, the
 // shape (threads x samples per lane) a per-precision default found by measurement
 static int launch_mesh(sdf_tape *t, const void *code, int precision, MeshArgs &a, int grid, int bs, hipStream_t st) {
     sdf_ctx *c = t->ctx;
-    const size_t tile = (size_t)(bs + 1) * (bs + 1) * (bs + 1) * 4;
-    const size_t bits_off = (MESH_LDS_VOL + tile + 15) & ~(size_t)15;
-    const size_t nvox = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
-    const size_t list_off = (bits_off + ((nvox + 63) / 64 + 2) * 8 + 15) & ~(size_t)15;
-    if (list_off + 4096 > c->lds_max) return fail("sdf_generate: device LDS too small for this batch size");
-    a.bits_off = (int)bits_off;
-    const size_t list_cap = std::min<size_t>((c->lds_max - list_off) / 4, 16384);
-    a.list_off = (int)list_off; a.list_cap = (int)list_cap;
-    const size_t lds = list_off + list_cap * 4;
+    const MeshLds l = mesh_lds(bs, c->lds_max);
+    if (l.list_off + 4096 > c->lds_max) return fail("sdf_generate: device LDS too small for this batch size");
+    a.bits_off = (int)l.bits_off; a.list_off = (int)l.list_off; a.list_cap = (int)l.list_cap;
+    const size_t lds = l.list_off + l.list_cap * 4;
     // two slots of sparse tiles share the dense tile's region (deferred emission, k_mesh); a slot has to hold its header,
     // some samples and the cell table of the per-cell counting -- else every tile stays dense
     // -- and between them and the sign bits the area through which a waiting batch's triangles are transposed (the sign bits
     // and the work area stay free: the next work item's record arrives there meanwhile)
     a.slot_bytes = 0; a.stage_off = 0;
-    if (c->defer && !a.twopass && a.cull && bits_off > MESH_LDS_VOL + 16 * MESH_STAGE_BYTES) {
-        const size_t slot = ((bits_off - MESH_LDS_VOL - 16 * MESH_STAGE_BYTES) / 2) & ~(size_t)15;
-        if (slot >= MESH_SLOT_HDR + 2048 + 8192 && list_cap * 4 >= CULL_RECORD) {
+    if (c->defer && !a.twopass && a.cull && l.bits_off > MESH_LDS_VOL + 16 * MESH_STAGE_BYTES) {
+        const size_t slot = ((l.bits_off - MESH_LDS_VOL - 16 * MESH_STAGE_BYTES) / 2) & ~(size_t)15;
+        if (slot >= MESH_SLOT_HDR + 2048 + 8192 && l.list_cap * 4 >= CULL_RECORD) {
             a.slot_bytes = (int)slot;
             a.stage_off = (int)(MESH_LDS_VOL + 2 * slot);
         }
@@ -1088,10 +1138,9 @@ static int launch_mesh(sdf_tape *t, const void *code, int precision, MeshArgs &a
 static int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
                         unsigned char *d_kinds, hipStream_t st) {
     if (b1 <= b0) return 0;
-    GridDesc g = {};
+    GridDesc g;
+    grid_desc(nx, ny, nz, bs, g);
     g.X = d_axes; g.Y = d_axes + nx; g.Z = d_axes + nx + ny;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
-    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
     PruneArgs pa = {};
     pa.first_block = 0x7fffffff;     // (no interval pass in this launch)
     const unsigned blocks = (unsigned)((b1 - b0 + SKIP_BATCHES_PER_BLOCK - 1) / SKIP_BATCHES_PER_BLOCK);
@@ -1102,31 +1151,28 @@ static int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int n
 }
 
 // the per-call statistics from the counters the meshing pass left (end of sdf_generate / sdf_mesh_wait)
-extern "C" int sdf_mesh_wait(sdf_mesh *m, int *emitted);
-
-static void finish_stats(sdf_tape *t, sdf_mesh *m, const MeshCounters &h, int nb, bool pruning, uint32_t n_instr, unsigned long long key,
-                         float ms_prepass, float ms_total) {
+static void finish_stats(sdf_tape *t, sdf_mesh *m, const MeshCounters &h, const CallState &s, float ms_prepass, float ms_total) {
     m->work_begin = h.work_begin; m->work_end = h.work_end;
-    m->st.n_skipped = nb - h.nwork;
+    m->st.n_skipped = s.nb - h.nwork;
     m->st.n_work_begin = m->work_begin; m->st.n_work_end = m->work_end;
     m->st.n_triangles = (int64_t)h.total;
     m->st.n_empty = h.n_empty; m->st.n_nonempty = h.n_nonempty;
     m->st.n_eval_voxels = (int64_t)h.n_eval; m->st.n_ambiguous_cells = (int64_t)h.n_ambiguous;
-    m->st.n_pruned_instrs = pruning ? (int64_t)h.n_pruned : 0;
+    m->st.n_pruned_instrs = s.pruning ? (int64_t)h.n_pruned : 0;
     m->st.n_sampled_voxels = (int64_t)h.n_sampled;
     // the kernel's own clock readings: 100 MHz ticks between the first workgroup's start and the last one's end
     m->st.ms_mesh_device = (h.t_first_inv && h.t_last > ~h.t_first_inv) ? (double)(h.t_last - ~h.t_first_inv) * 1e-5 : 0.0;
     m->st.sclk_mhz = h.clk_ticks ? (double)h.clk_cycles / (double)h.clk_ticks * 100.0 : 0.0;
     m->st.t_mesh_first_us = h.t_first_inv ? (double)(~h.t_first_inv) * 0.01 : 0.0;
     m->st.t_mesh_last_us = (double)h.t_last * 0.01;
-    m->pruned = pruning;
+    m->pruned = s.pruning;
     m->st.mesh_kernel = 1;
-    m->st.n_batch_instrs = (int64_t)(n_instr - 1) * (h.work_end - h.work_begin);
-    t->hint_key = key; t->hint_total_tris = std::max<unsigned long long>(h.total, 1);
+    m->st.n_batch_instrs = (int64_t)(s.n_instr - 1) * (h.work_end - h.work_begin);
+    t->hint_key = s.key; t->hint_total_tris = std::max<unsigned long long>(h.total, 1);
     {   // (per MODEL and grid, for sdf_generate_records; a handful of entries per job -- the map is emptied when it grows past 4096)
         auto &rh = t->ctx->rec_hints;
         if (rh.size() > 4096) rh.clear();
-        sdf_ctx::RecHint &e = rh[std::make_pair(t->content_hash, key)];
+        sdf_ctx::RecHint &e = rh[std::make_pair(t->content_hash, s.key)];
         e.tris = std::max<unsigned long long>(h.total, 1); e.raw = h.n_raw;
     }
     m->st.ms_prepass = ms_prepass;
@@ -1140,20 +1186,28 @@ static unsigned long long grid_key(int nx, int ny, int nz, int bs, int sparse, i
            ((unsigned long long)bs << 36) ^ (sparse ? 1ull << 63 : 0ull);
 }
 
-static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const double *Y, int ny, const double *Z, int nz,
-                         int bs, int sparse, int64_t shard_index, int64_t shard_count, int precision, void *d_out, int64_t cap_out,
-                         bool async_mode = false, int64_t slab_items = -1, hipStream_t lane_stream = nullptr,
-                         const unsigned char *d_kinds_in = nullptr) {
-    // slab_items >= 0: compact mode (sdf_generate_compact_async) -- d_out is a SLAB of capacity (slab_items, cap_out)
-    // lane_stream: the stream the whole call is enqueued on (the exchange steps of sdf_comm run on lanes of their own)
-    // d_kinds_in: the skip test's verdict for every batch is already on the device (0 skipped / 255 pending, n_batches
-    // bytes: sdf_skip_kinds, possibly all-gathered from the ranks that each tested a share): k_skip is not run
-    sdf_ctx *c = t->ctx;
-    const bool compact = slab_items >= 0;
-    // a free call slot; when all are held by calls in flight, the oldest of them is COLLECTED first (its counters
-    // and event times live in the slot's pinned staging and events: reusing the slot before sdf_mesh_wait has
-    // read them would hand that mesh this call's numbers)
-    int slot = -1;
+// The end of a fused call whose counters have arrived in its slot's pinned staging (the stream was waited for, or the slot's
+// `done` event): the counters into h, the event intervals, the look-back time-out.  The statistics are taken unless the
+// soup overflowed and the caller repeats the call (stats_if_short: a short SLAB is not repeated here, its call counts as it is).
+static int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, MeshCounters &h) {
+    sdf_ctx *c = m->ctx;
+    CallSlot &cs = c->slots[s.slot];
+    h = *(const MeshCounters *)((char *)c->h_stage + (size_t)s.slot * SDF_STAGE_BYTES + SDF_STAGE_BYTES - 256);
+    float ms = 0, ms_pre = 0, ms_tot = 0;
+    HIPCHK(hipEventElapsedTime(&ms, s.own_start ? cs.e3 : cs.e2, cs.e4));
+    HIPCHK(hipEventElapsedTime(&ms_pre, cs.e0, cs.e2));
+    HIPCHK(hipEventElapsedTime(&ms_tot, cs.e0, cs.e4));
+    m->st.ms_mesh = ms;
+    if (h.overflow & 2u) return fail("sdf_generate: ordered-allocation look-back timed out");
+    if (!h.overflow || stats_if_short) finish_stats(call.tape, m, h, s, ms_pre, ms_tot);
+    return 0;
+}
+
+// a free call slot; when all are held by calls in flight, the oldest of them is COLLECTED first (its counters
+// and event times live in the slot's pinned staging and events: reusing the slot before sdf_mesh_wait has
+// read them would hand that mesh this call's numbers)
+static int take_slot(sdf_ctx *c, int &slot) {
+    slot = -1;
     for (int k = 0; k < SDF_CALL_SLOTS && slot < 0; k++)
         if (!c->slots[(c->slot_seq + (unsigned)k) % SDF_CALL_SLOTS].busy) slot = (int)((c->slot_seq + (unsigned)k) % SDF_CALL_SLOTS);
     if (slot < 0) {
@@ -1164,39 +1218,16 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         held.busy = false; held.owner = nullptr;
     }
     c->slot_seq = (unsigned)slot + 1u;
-    CallSlot &cs = c->slots[slot];
-    // Calls in flight (sdf_generate_to_device_async) each run on their slot's OWN stream: call i + 1's prepass then
-    // fills the compute units that call i's k_mesh leaves idle in its tail (a persistent workgroup per CU, the last
-    // batches finish at different times: 9 % of that kernel's CU-time) and the dispatch gaps of one call hide behind
-    // the kernels of the other.  Everything a call touches is its own (per-mesh buffers, per-slot staging / events /
-    // park slots), so the streams need no ordering among themselves.  An adopted caller stream is never left.
-    const bool own_lane = async_mode && !compact && c->stream == c->own_stream && c->slot_streams;
-    hipStream_t st = lane_stream ? lane_stream : (own_lane ? cs.stream : c->stream);
-    m->stream = (own_lane || lane_stream) ? st : nullptr;
-    char *stage = (char *)c->h_stage + (size_t)slot * SDF_STAGE_BYTES;
-    GridDesc &g = m->g;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
-    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
-    const long long nb64 = (long long)g.nbx * g.nby * g.nbz;
-    if (nb64 > 0x7fffffffLL) return fail("sdf_generate: too many batches");
-    const int nb = (int)nb64;
-    m->st.n_batches = nb;
-    m->st.n_grid_voxels = (int64_t)nx * ny * nz;
-    if (nb == 0) {
-        if (compact) HIPCHK(hipMemsetAsync(d_out, 0, sizeof(SlabHeader), st));   // an empty grid: an empty slab
-        return 0;
-    }
+    return 0;
+}
 
-    if (m->axes.ensure((size_t)(nx + ny + nz) * 8) || m->kinds.ensure((size_t)nb) || m->worklist.ensure((size_t)nb * 4) ||
-        m->status.ensure((size_t)nb * 8))
-        return 1;
-    if (!m->counters.p && !c->counter_pool.empty()) { m->counters = c->counter_pool.back(); c->counter_pool.pop_back(); }
-    if (m->counters.ensure(sizeof(MeshCounters))) return 1;
-    double *dX = (double *)m->axes.p, *dY = dX + nx, *dZ = dY + ny;
-    g.X = dX; g.Y = dY; g.Z = dZ;
-    HIPCHK(hipEventRecord(cs.e0, st));
+// the host axes into the mesh's device copy (X, then Y, then Z from dX on), through the slot's pinned staging where they fit
+static int stage_axes(const GenCall &call, char *stage, double *dX, hipStream_t st) {
+    const double *X = call.X, *Y = call.Y, *Z = call.Z;
+    const int nx = call.nx, ny = call.ny, nz = call.nz;
+    double *dY = dX + nx, *dZ = dY + ny;
     const size_t axis_bytes = (size_t)(nx + ny + nz) * 8;
-    if (async_mode && axis_bytes > SDF_STAGE_BYTES - 256) return fail("sdf_generate_to_device_async: axes too long for the staging slot");
+    if (call.collected && axis_bytes > SDF_STAGE_BYTES - 256) return fail("sdf_generate_to_device_async: axes too long for the staging slot");
     if (axis_bytes <= SDF_STAGE_BYTES - 256) {   // one copy from pinned memory instead of three from pageable
         double *hs = (double *)stage;
         memcpy(hs, X, (size_t)nx * 8); memcpy(hs + nx, Y, (size_t)ny * 8); memcpy(hs + nx + ny, Z, (size_t)nz * 8);
@@ -1206,29 +1237,24 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
         HIPCHK(hipMemcpyAsync(dY, Y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)nz * 8, hipMemcpyHostToDevice, st));
     }
+    return 0;
+}
 
-    // ---- prepass: skip test for every batch, then the ordered work list (+ this shard's slice) ----
-    // (three event records per call, not one per interval: each is a marker packet the queue has to drain to;
-    // ms_prepass = ev[0] -> ev[2] includes the copy of the axes, ms_mesh = ev[2] -> ev[4], ms_total = ev[0] -> ev[4])
-    // interval pass: per batch, which instructions never matter (float64 sampling only: the intervals
-    // bound the float64 interpreter, not the float32 one).  The box of a batch is spanned by its first
-    // and last coordinate per axis: monotone axes only.
-    auto monotone = [](const double *a, int n) {
-        bool up = true, down = true;
-        for (int i = 1; i < n; i++) { up &= a[i - 1] <= a[i]; down &= a[i - 1] >= a[i]; }
-        return up || down;
-    };
+// ---- prepass: skip test for every batch, then the ordered work list (+ this shard's slice) ----
+// interval pass: per batch, which instructions never matter.  tape_stride = 64-bit words per batch tape (0: no interval pass).
+static int enqueue_prepass(const GenCall &call, sdf_mesh *m, int nb, int tape_stride, hipStream_t st) {
+    sdf_tape *t = call.tape;
+    sdf_ctx *c = t->ctx;
+    const GridDesc &g = m->g;
+    const int sparse = call.sparse, precision = call.precision;
+    const bool pruning = tape_stride != 0;
     const uint32_t n_instr = t->n_words / 2;
-    const bool intervals_ok = precision == SDF_PRECISION_F64 && monotone(X, nx) && monotone(Y, ny) && monotone(Z, nz);
-    const bool pruning = c->prune && t->d_rstart && n_instr <= 256 && intervals_ok && t->n_consts < 0xFFFFF0u;
-    // 64-bit words per batch tape: the instructions, one more END, the length; whole 64-byte lines
-    const int tape_stride = (int)((n_instr + 2 + 7) & ~7u);
     PruneArgs pa = {};
     pa.first_block = 0x7fffffff;
     // many batches: the interval pass runs behind k_compact, for the surviving batches only (k_prune_list)
     // (a rank of a multi-GPU job prunes its own share of the work list only, whatever the grid's size)
-    const bool prune_listed = pruning && sparse && (nb >= c->prune_list_min || shard_count > 1);
-    unsigned skip_blocks = (sparse && !d_kinds_in) ? (unsigned)((nb + SKIP_BATCHES_PER_BLOCK - 1) / SKIP_BATCHES_PER_BLOCK) : 0u, prune_blocks = 0;
+    const bool prune_listed = pruning && sparse && (nb >= c->prune_list_min || call.shard_count > 1);
+    unsigned skip_blocks = (sparse && !call.d_kinds) ? (unsigned)((nb + SKIP_BATCHES_PER_BLOCK - 1) / SKIP_BATCHES_PER_BLOCK) : 0u, prune_blocks = 0;
     size_t prune_lds = 0;
     if (pruning) {
         if (m->prune.ensure((size_t)nb * 64) || m->tapes.ensure((size_t)nb * tape_stride * 8)) return 1;
@@ -1254,10 +1280,10 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
                             (const double *)t->d_c64, (const uint16_t *)t->d_rstart, (const uint16_t *)t->d_lstart, 0);
     }
     if (!sparse) HIPCHK(hipMemsetAsync(m->kinds.p, 255, (size_t)nb, st));
-    else if (d_kinds_in) HIPCHK(hipMemcpyAsync(m->kinds.p, d_kinds_in, (size_t)nb, hipMemcpyDeviceToDevice, st));   // (k_mesh writes its verdicts into the mesh's own copy)
+    else if (call.d_kinds) HIPCHK(hipMemcpyAsync(m->kinds.p, call.d_kinds, (size_t)nb, hipMemcpyDeviceToDevice, st));   // (k_mesh writes its verdicts into the mesh's own copy)
     launch_k_compact(dim3(1), dim3(1024), st, (const unsigned char *)m->kinds.p, nb, (int *)m->worklist.p,
-                       (MeshCounters *)m->counters.p, (unsigned long long *)m->status.p, (long long)shard_index,
-                       (long long)shard_count);
+                       (MeshCounters *)m->counters.p, (unsigned long long *)m->status.p, (long long)call.shard_index,
+                       (long long)call.shard_count);
     HIPCHK(hipGetLastError());
     if (prune_listed) {
         pa.worklist = (const int *)m->worklist.p; pa.ctr = (const MeshCounters *)m->counters.p;
@@ -1268,56 +1294,277 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
                            (const uint16_t *)t->d_lstart);
         HIPCHK(hipGetLastError());
     }
-    // second interval pass, per surviving batch: the sub-groups of 2^3 cells the surface cannot be in are not sampled
-    // (k_mesh reads the batch's record into the list region of its LDS, which has to hold it: launch_mesh's layout)
-    const size_t mesh_nvox = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
-    const size_t mesh_bits_off = (MESH_LDS_VOL + mesh_nvox * 4 + 15) & ~(size_t)15;
-    const size_t mesh_list_off = (mesh_bits_off + ((mesh_nvox + 63) / 64 + 2) * 8 + 15) & ~(size_t)15;
-    const bool culling = c->cull && intervals_ok && t->ia_complete && mesh_list_off + CULL_RECORD <= c->lds_max;
+    return 0;
+}
+
+// second interval pass, per surviving batch: the sub-groups of 2^3 cells the surface cannot be in are not sampled.
+// tail_order: every work item of the list's tail leaves its cost estimate in m->order.
+static int enqueue_cull(sdf_tape *t, sdf_mesh *m, int nb, int tape_stride, bool tail_order, int tail_max, hipStream_t st) {
+    sdf_ctx *c = t->ctx;
+    const GridDesc &g = m->g;
+    const bool pruning = tape_stride != 0;
+    const uint32_t n_instr = t->n_words / 2;
+    if (c->prof.p) HIPCHK(hipMemsetAsync((unsigned char *)c->prof.p + 128, 0, 384, st));
+    if (m->cull.ensure((size_t)nb * CULL_RECORD) || (tail_order && m->order.ensure(MESH_TAIL_MAX * sizeof(int)))) return 1;
+    const int ia_np = (int)std::max(t->n_p, 1u), ia_nd = (int)std::max(t->n_d, 1u);
+    auto kc = t->full ? (t->ia_rare ? k_cull<true, true> : k_cull<true, false>) : (t->ia_rare ? k_cull<false, true> : k_cull_lean);
+    int cull_block = CULL_BLOCK;
+    if (c->cull_block == 128 && kc == k_cull_lean) { kc = k_cull_lean128; cull_block = 128; }
+    // (the trig-capable variant with one or two waves per work item: the first level of the pass -- 64 boxes -- keeps
+    // ONE wave of a workgroup busy whatever its size, so smaller workgroups mean more work items per compute unit)
+    // measured (r03f, prepass of weave 2^33 / 2^27, gearlike 2^30, knurling 2^27, ms): 256 threads 8.95 / 1.52 / 0.325 /
+    // 0.364; 128: 6.61 / 1.35 / 0.276 / 0.361; 64: 6.05 / 1.44 / 0.298 / 0.442 -- two waves are the default here
+    if (t->full && !t->ia_rare && c->cull_block != 256) {
+        cull_block = c->cull_block == 64 ? 64 : 128;
+        kc = cull_block == 64 ? k_cull<true, false, 64> : k_cull<true, false, 128>;
+    }
+    // The third interval level (sub-groups of 2^3 cells) halves what k_mesh samples and costs 8 interval runs per
+    // undecided group of 4^3 cells.  r04a, same box, prepass + k_mesh in ms, two levels -> three: example 2^27 0.068 + 0.280
+    // -> 0.104 + 0.240, pawn 0.132 + 0.416 -> 0.276 + 0.289, blobby 2^30 0.229 + 0.874 -> 0.505 + 0.612 (level with or
+    // ahead, and the prepass of the NEXT call hides behind k_mesh when calls are in flight); with trigonometry in the tape
+    // the interval forms are dearer than the samples they save: gearlike 2^30 0.271 + 1.23 -> 0.64 + 0.99, knurling 2^27
+    // 0.364 + 1.52 -> 1.58 + 1.25, weave 2^33 6.6 + 24.2 -> 19.9 + 15.4.  Hence three levels for the lean tapes, two for
+    // the others -- which still list units of 2^3 samples instead of r03's cubes of 4^3.
+    const int cull_levels = c->cull_levels ? c->cull_levels : (kc == k_cull_lean || kc == k_cull_lean128 ? 3 : 2);
+    // (seven workgroups of 256 threads per CU instead of six -- 72 VGPRs, the interval state of 192 threads in LDS, so that
+    // every work item of the 512^3 example is resident at once -- was measured in r04k: example prepass 0.093 vs 0.091 ms,
+    // pawn 0.402 vs 0.266 ms: the levels then run in more passes.  Not the limit.)
+    const size_t ia_bytes = std::min<size_t>((size_t)cull_block * (6 * ia_np + 2 * ia_nd) * 8, c->lds_max - 896 - CULL_SCRATCH);
+    const size_t lds = 896 + CULL_SCRATCH + ia_bytes;
+    if (lds > 32768) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kc, dim3(nb), dim3(cull_block), lds, st,
+                       pruning ? (const uint32_t *)m->tapes.p : (const uint32_t *)t->d_code, (const double *)t->d_c64, g,
+                       (const int *)m->worklist.p, (const MeshCounters *)m->counters.p, pruning ? tape_stride : 0, (int)n_instr,
+                       ia_np, ia_nd, (int)ia_bytes, (unsigned char *)m->cull.p, (unsigned long long *)c->prof.p,
+                       tail_order ? (int *)m->order.p : (int *)nullptr, tail_max, cull_levels);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// capacity of the library's soup for a call's first attempt: from the last call of this tape on the same grid, else
+// from the work-list length (one synchronisation: not quiet)
+static int first_soup_cap(sdf_tape *t, sdf_mesh *m, unsigned long long key, hipStream_t st, unsigned long long &cap, bool &quiet) {
+    if (t->hint_key == key && t->hint_total_tris) {
+        cap = t->hint_total_tris + t->hint_total_tris / 4 + 4096;
+        return 0;
+    }
+    MeshCounters h;
+    quiet = false;
+    HIPCHK(hipMemcpyAsync(&h, m->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(st));
+    const unsigned long long nshard0 = (unsigned long long)std::max(h.work_end - h.work_begin, 1);
+    cap = std::max<unsigned long long>(4096ull * nshard0, 1ull << 16);
+    // a guess, not a need (the overflow re-run finds the exact size): never more than half the free memory
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        cap = std::min<unsigned long long>(cap, std::max<unsigned long long>(free_b / 2 / (72 + 40), 1ull << 16));   // (+ 40 B per triangle: the two-pass arenas)
+    return 0;
+}
+
+// where an attempt's triangles go: the call's own destination (cap == 0), or a library soup of `cap` triangles
+static int soup_target(const GenCall &call, sdf_mesh *m, int attempt, unsigned long long cap, bool &quiet, MeshArgs &a) {
+    sdf_ctx *c = m->ctx;
+    a.compact = 0; a.xf = nullptr; a.xf_cap = 0; a.raw = nullptr; a.raw_cap = 0;
+    if (cap) {
+        if (!m->out.p && !c->arena_pool.empty()) { m->out = c->arena_pool.back(); c->arena_pool.pop_back(); }
+        if (m->out.bytes < (size_t)cap * 72) quiet = false;     // (an allocation: the stream idles meanwhile)
+        if (m->out.ensure((size_t)cap * 72)) {
+            // a first-call guess that does not fit: shrink it and let the overflow re-run size the soup exactly
+            bool ok = false;
+            for (int k = 0; k < 6 && !ok && attempt == 0 && cap > (1ull << 16); k++) {
+                cap = std::max<unsigned long long>(cap / 4, 1ull << 16);
+                ok = m->out.ensure((size_t)cap * 72) == 0;
+            }
+            if (!ok) return 1;
+        }
+        a.out = (double *)m->out.p; a.out_cap = m->out.bytes / 72;
+    } else if (call.dest == GenCall::SLAB) {
+        unsigned char *d_slab = (unsigned char *)call.d_out;
+        const SlabLayout L(call.cap_items, call.cap_tris);
+        a.out = reinterpret_cast<double *>(d_slab + L.tris_off); a.out_cap = (unsigned long long)call.cap_tris;
+        a.compact = 1; a.xf = reinterpret_cast<double *>(d_slab + L.xf_off);
+        a.raw = reinterpret_cast<float *>(d_slab + L.raw_off); a.raw_cap = L.raw_cap;
+        a.xf_cap = (int)std::min<int64_t>(call.cap_items, 0x7fffffff);
+    } else {
+        a.out = (double *)call.d_out; a.out_cap = (unsigned long long)call.cap_tris;
+    }
+    return 0;
+}
+
+// One meshing attempt on `st`, up to the counters' copy into the slot's pinned staging: k_mesh [-> k_scan_items -> k_emit2]
+// [-> k_pack_slab].  soup_cap: see soup_target; quiet: nothing but k_mesh follows ev[2] on the stream, and the host did not
+// stall in between; tail: work items at the list's end that k_mesh hands out by k_cull's cost estimates (0: in order).
+static int mesh_attempt(const GenCall &call, sdf_mesh *m, CallState &s, hipStream_t st, int attempt, unsigned long long soup_cap, bool quiet,
+                        bool culling, int tail, int tape_stride) {
+    sdf_tape *t = call.tape;
+    sdf_ctx *c = t->ctx;
+    CallSlot &cs = c->slots[s.slot];
+    const int nb = s.nb;
+    const uint32_t n_instr = s.n_instr;
+    MeshArgs a;
+    a.twopass = 0; a.desc = nullptr; a.cells = nullptr; a.tlist = nullptr; a.cells_cap = a.tlist_cap = 0; a.block_item = nullptr;
+    a.order = tail ? (const int *)m->order.p : nullptr; a.tail = tail;
+    if (soup_target(call, m, attempt, soup_cap, quiet, a)) return 1;
+    if (attempt) {   // (the first pass finds both cleared by k_compact)
+        HIPCHK(hipMemsetAsync(m->counters.p, 0, MESH_COUNTERS_RESET_BYTES, st));
+        HIPCHK(hipMemsetAsync(m->status.p, 0, (size_t)nb * 8, st));
+    }
+    a.g = m->g; a.worklist = (const int *)m->worklist.p;
+    a.kinds = (unsigned char *)m->kinds.p; a.status = (unsigned long long *)m->status.p;
+    a.ctr = (MeshCounters *)m->counters.p;
+    a.mc = (const McTables *)c->mc.p;
+    a.prof = (unsigned long long *)c->prof.p;
+    // One pass or two?  (decided here: the two-pass scheme parks nothing -- its triangles are numbered by k_scan_items -- so a
+    // call that takes it does not make its lane allocate park slots: 1.2 GB that the long jobs' lanes never touched, r04 advisor)
+    const bool twopass = c->twopass >= 0 ? c->twopass != 0 : n_instr > 96;
+    DevBuf &park = call.collected ? cs.park : c->park;   // (k_mesh kernels of calls in flight may overlap in time, whichever
+                                                         // streams they run on: each call slot has its own staging slots)
+    const bool parks = c->parking && !twopass;
+    if (parks && !park.p) { quiet = false; if (park.ensure((size_t)c->n_cu * MESH_PARK_DEPTH * SDF_PARK_TRIS * 36)) return 1; }
+    a.park = parks ? (float *)park.p : nullptr; a.park_cap = a.park ? SDF_PARK_TRIS : 0;
+    a.park_spins = (unsigned)c->park_spins;
+    a.cull = culling ? (const unsigned char *)m->cull.p : nullptr;
+    a.tape_stride = tape_stride;
+    a.n_instr = (int)n_instr;
+    // One pass or two?  The one-pass kernel (look-back + parking inside the sampling kernel) is 7 - 20 % faster on
+    // short tapes: it hides its triangle traffic behind other workgroups' arithmetic, which three kernels in a row
+    // cannot.  On long tapes (weave at 2^33, 244 instructions) the two schemes tie -- 27.5 vs 28.0 ms -- and the
+    // two-pass one moves a third of the bytes (9 GB against 25 GB per call: no parking, and the 4-slot sampling
+    // kernel spills less without the emit phases): the tape's length decides (sdf_ctx_set_twopass / SDF_MESH_TWOPASS
+    // override).
+    if (twopass) {
+        // the arenas of the two-pass scheme: a surface cell carries at least one triangle, so the soup's capacity
+        // bounds both (a call whose arenas turn out too small is flagged and repeated like one whose soup is)
+        const size_t cap_t = (size_t)a.out_cap;
+        if (m->desc.bytes < (size_t)nb * sizeof(ItemDesc) || m->cellrecs.bytes < cap_t * 36 || m->trilist.bytes < cap_t * 4) quiet = false;
+        if (m->desc.ensure((size_t)nb * sizeof(ItemDesc)) || m->cellrecs.ensure(cap_t * 36) || m->trilist.ensure(cap_t * 4) ||
+            m->blockidx.ensure(((cap_t + 255) / 256 + 2) * sizeof(int)))
+            return 1;
+        a.twopass = 1; a.desc = (ItemDesc *)m->desc.p; a.cells = (unsigned *)m->cellrecs.p; a.tlist = (unsigned *)m->trilist.p;
+        a.block_item = (const int *)m->blockidx.p;
+        a.cells_cap = a.tlist_cap = (unsigned long long)cap_t;
+    }
+    if (a.prof) {   // (words 16.. are k_cull's: cleared before the prepass; behind byte 512: the workgroups' timelines)
+        HIPCHK(hipMemsetAsync(a.prof, 0, 128, st));
+        HIPCHK(hipMemsetAsync((unsigned char *)a.prof + 512, 0, 4096 * 32, st));
+    }
+    const int grid = std::min(nb, c->n_cu);   // persistent workgroups; surplus ones find the list empty
+    s.own_start = attempt > 0 || a.prof || !quiet;   // (something was enqueued, or the host waited, since ev[2])
+    if (s.own_start) HIPCHK(hipEventRecord(cs.e3, st));
+    if (launch_mesh(t, tape_stride ? m->tapes.p : (const void *)t->d_code, call.precision, a, grid, call.bs, st)) return 1;
+    if (a.twopass) {
+        const unsigned long long emit_blocks = (a.out_cap + 255ull) / 256ull;
+        if (emit_blocks > 0x7fffffffull) return fail("sdf_generate: soup capacity too large for one k_emit2 launch");
+        launch_k_scan_items(dim3(1), dim3(1024), st, (const ItemDesc *)m->desc.p, (MeshCounters *)m->counters.p,
+                           (unsigned long long *)m->status.p, (int *)m->blockidx.p, emit_blocks + 1ull);
+        launch_k_emit2(dim3((unsigned)std::max<unsigned long long>(emit_blocks, 1ull)), dim3(256), st, a);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(cs.e4, st));
+    if (call.dest == GenCall::SLAB) {
+        const unsigned pack_blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((call.cap_items + 255) / 256, 1), 1024);
+        HIPCHK((hipError_t)sdf_launch_pack_slab(pack_blocks, st, (const MeshCounters *)m->counters.p, (const unsigned long long *)m->status.p,
+                                                (unsigned char *)call.d_out, (long long)call.cap_items, (long long)call.cap_tris));
+    }
+    MeshCounters *hp = (MeshCounters *)((char *)c->h_stage + (size_t)s.slot * SDF_STAGE_BYTES + SDF_STAGE_BYTES - 256);   // pinned
+    HIPCHK(hipMemcpyAsync(hp, m->counters.p, sizeof(MeshCounters), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// SDF_MESH_PROF=1: what k_cull and the `grid` workgroups of k_mesh counted during the call that has just completed, to stderr
+static int mesh_prof_report(sdf_ctx *c, int grid, float ms) {
+    unsigned long long pc[64];
+    HIPCHK(hipMemcpy(pc, c->prof.p, 512, hipMemcpyDeviceToHost));
+    {   // timeline of the workgroups: when each ran out of work and when it was done, relative to the first start
+        std::vector<unsigned long long> tl((size_t)4 * grid);
+        HIPCHK(hipMemcpy(tl.data(), (unsigned char *)c->prof.p + 512, tl.size() * 8, hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, t_end = 0;
+        double s_out = 0, s_done = 0, mn_out = 1e30, mx_out = 0;
+        for (int i = 0; i < grid; i++) t0 = std::min(t0, tl[4 * i]);
+        for (int i = 0; i < grid; i++) {
+            const double o = (double)(tl[4 * i + 1] - t0) * 0.01, d = (double)(tl[4 * i + 2] - t0) * 0.01;   // us
+            s_out += o; s_done += d; mn_out = std::min(mn_out, o); mx_out = std::max(mx_out, o); t_end = std::max(t_end, tl[4 * i + 2]);
+        }
+        double first_hi = 0;   // the latest start: workgroups that were not resident from the beginning start late
+        for (int i = 0; i < grid; i++) first_hi = std::max(first_hi, (double)(tl[4 * i] - t0) * 0.01);
+        fprintf(stderr, "[k_mesh prof] %d workgroups (1 per CU), last of them started after %.1f us; out of work after min %.1f avg %.1f max %.1f us; done after avg %.1f, last %.1f us\n",
+                grid, first_hi, mn_out, s_out / grid, mx_out, s_done / grid, (double)(t_end - t0) * 0.01);
+    }
+    fprintf(stderr, "[k_cull prof] work items by listed tasks (of 563; bins of 64, last: not culled): %llu %llu %llu %llu %llu %llu %llu %llu %llu | %llu\n",
+            pc[32], pc[33], pc[34], pc[35], pc[36], pc[37], pc[38], pc[39], pc[40], pc[41]);
+    fprintf(stderr, "[k_cull prof] cycles of thread 0, summed over the workgroups: start %llu boxes %llu list %llu groups %llu (%llu passes, %llu groups) tasks %llu record %llu\n",
+            pc[16], pc[17], pc[18], pc[19], pc[23], pc[22], pc[20], pc[21]);
+    fprintf(stderr, "[k_cull prof] task listing: which tasks %llu, scans %llu; start: range %llu batch %llu origin %llu axes %llu barrier %llu (rest: tape length)\n", pc[24], pc[25], pc[26], pc[27], pc[30], pc[28], pc[29]);
+    fprintf(stderr, "[k_mesh prof] sampling: intervals %llu task list %llu interpreter %llu sign bits %llu\n", pc[8], pc[9], pc[10], pc[11]);
+    fprintf(stderr, "[k_mesh prof] fine: atomic %llu barrier+rank %llu header %llu | rows %llu cells %llu | placing %llu look-back %llu | round end %llu\n",
+            pc[42], pc[43], pc[44], pc[45], pc[46], pc[47], pc[48], pc[49]);
+    fprintf(stderr, "[k_mesh prof] %.3f ms; cycles/WG-sum: grab %llu sample %llu count %llu (of which placing the parked batch %llu) list %llu emit %llu tail %llu; %llu batches parked, %llu written one batch later from their slot\n",
+            ms, pc[0], pc[1], pc[2], pc[6], pc[3], pc[4], pc[5], pc[7], pc[12]);
+    return 0;
+}
+
+static int generate_impl(sdf_mesh *m, const GenCall &call) {
+    sdf_tape *t = call.tape;
+    sdf_ctx *c = t->ctx;
+    const bool slab = call.dest == GenCall::SLAB;
+    const int nx = call.nx, ny = call.ny, nz = call.nz;
+    CallState s;
+    if (take_slot(c, s.slot)) return 1;
+    CallSlot &cs = c->slots[s.slot];
+    // Calls in flight (sdf_generate_to_device_async) each run on their slot's OWN stream: call i + 1's prepass then
+    // fills the compute units that call i's k_mesh leaves idle in its tail (a persistent workgroup per CU, the last
+    // batches finish at different times: 9 % of that kernel's CU-time) and the dispatch gaps of one call hide behind
+    // the kernels of the other.  Everything a call touches is its own (per-mesh buffers, per-slot staging / events /
+    // park slots), so the streams need no ordering among themselves.  An adopted caller stream is never left.
+    const bool own_lane = call.collected && !slab && c->stream == c->own_stream && c->slot_streams;
+    hipStream_t st = call.lane ? call.lane : (own_lane ? cs.stream : c->stream);
+    m->stream = (own_lane || call.lane) ? st : nullptr;
+    if (grid_batches(nx, ny, nz, call.bs, "sdf_generate", m->g, s.nb)) return 1;
+    const int nb = s.nb;
+    m->st.n_batches = nb;
+    m->st.n_grid_voxels = (int64_t)nx * ny * nz;
+    if (nb == 0) {
+        if (slab) HIPCHK(hipMemsetAsync(call.d_out, 0, sizeof(SlabHeader), st));   // an empty grid: an empty slab
+        return 0;
+    }
+
+    if (m->axes.ensure((size_t)(nx + ny + nz) * 8) || m->kinds.ensure((size_t)nb) || m->worklist.ensure((size_t)nb * 4) ||
+        m->status.ensure((size_t)nb * 8))
+        return 1;
+    if (!m->counters.p && !c->counter_pool.empty()) { m->counters = c->counter_pool.back(); c->counter_pool.pop_back(); }
+    if (m->counters.ensure(sizeof(MeshCounters))) return 1;
+    double *dX = (double *)m->axes.p;
+    m->g.X = dX; m->g.Y = dX + nx; m->g.Z = dX + nx + ny;
+    HIPCHK(hipEventRecord(cs.e0, st));
+    if (stage_axes(call, (char *)c->h_stage + (size_t)s.slot * SDF_STAGE_BYTES, dX, st)) return 1;
+
+    // (three event records per call, not one per interval: each is a marker packet the queue has to drain to;
+    // ms_prepass = ev[0] -> ev[2] includes the copy of the axes, ms_mesh = ev[2] -> ev[4], ms_total = ev[0] -> ev[4])
+    // interval pass: per batch, which instructions never matter (float64 sampling only: the intervals
+    // bound the float64 interpreter, not the float32 one).  The box of a batch is spanned by its first
+    // and last coordinate per axis: monotone axes only.
+    auto monotone = [](const double *a, int n) {
+        bool up = true, down = true;
+        for (int i = 1; i < n; i++) { up &= a[i - 1] <= a[i]; down &= a[i - 1] >= a[i]; }
+        return up || down;
+    };
+    s.n_instr = t->n_words / 2;
+    const bool intervals_ok = call.precision == SDF_PRECISION_F64 && monotone(call.X, nx) && monotone(call.Y, ny) && monotone(call.Z, nz);
+    s.pruning = c->prune && t->d_rstart && s.n_instr <= 256 && intervals_ok && t->n_consts < 0xFFFFF0u;
+    // 64-bit words per batch tape: the instructions, one more END, the length; whole 64-byte lines
+    const int tape_stride = s.pruning ? (int)((s.n_instr + 2 + 7) & ~7u) : 0;
+    if (enqueue_prepass(call, m, nb, tape_stride, st)) return 1;
+    // (k_mesh reads the batch's cull record into the list region of its LDS, which has to hold it)
+    const bool culling = c->cull && intervals_ok && t->ia_complete && mesh_lds(call.bs, c->lds_max).list_off + CULL_RECORD <= c->lds_max;
     // the tail of the work list is handed out by descending cost (MeshArgs::order, k_cull's estimates); fewer items
     // than k_mesh has workgroups
     const int tail_max = std::min<int>(MESH_TAIL_MAX, std::min(nb, c->n_cu) - 1);
     // (not for calls in flight next to others: the argument that a reordered tail cannot stall -- fewer tail items than
     // workgroups -- counts RESIDENT workgroups, and a k_mesh that shares the device with another call's k_mesh may have
     // fewer of them for a while; the neighbours fill the tail of such a call anyway)
-    const bool tail_order = culling && c->tail_order && tail_max >= 2 && !async_mode;
-    const unsigned long long key = grid_key(nx, ny, nz, bs, sparse, shard_index, shard_count);
-    if (culling) {
-        if (c->prof.p) HIPCHK(hipMemsetAsync((unsigned char *)c->prof.p + 128, 0, 384, st));
-        if (m->cull.ensure((size_t)nb * CULL_RECORD) || (tail_order && m->order.ensure(MESH_TAIL_MAX * sizeof(int)))) return 1;
-        const int ia_np = (int)std::max(t->n_p, 1u), ia_nd = (int)std::max(t->n_d, 1u);
-        auto kc = t->full ? (t->ia_rare ? k_cull<true, true> : k_cull<true, false>) : (t->ia_rare ? k_cull<false, true> : k_cull_lean);
-        int cull_block = CULL_BLOCK;
-        if (c->cull_block == 128 && kc == k_cull_lean) { kc = k_cull_lean128; cull_block = 128; }
-        // (the trig-capable variant with one or two waves per work item: the first level of the pass -- 64 boxes -- keeps
-        // ONE wave of a workgroup busy whatever its size, so smaller workgroups mean more work items per compute unit)
-        // measured (r03f, prepass of weave 2^33 / 2^27, gearlike 2^30, knurling 2^27, ms): 256 threads 8.95 / 1.52 / 0.325 /
-        // 0.364; 128: 6.61 / 1.35 / 0.276 / 0.361; 64: 6.05 / 1.44 / 0.298 / 0.442 -- two waves are the default here
-        if (t->full && !t->ia_rare && c->cull_block != 256) {
-            cull_block = c->cull_block == 64 ? 64 : 128;
-            kc = cull_block == 64 ? k_cull<true, false, 64> : k_cull<true, false, 128>;
-        }
-        // The third interval level (sub-groups of 2^3 cells) halves what k_mesh samples and costs 8 interval runs per
-        // undecided group of 4^3 cells.  r04a, same box, prepass + k_mesh in ms, two levels -> three: example 2^27 0.068 + 0.280
-        // -> 0.104 + 0.240, pawn 0.132 + 0.416 -> 0.276 + 0.289, blobby 2^30 0.229 + 0.874 -> 0.505 + 0.612 (level with or
-        // ahead, and the prepass of the NEXT call hides behind k_mesh when calls are in flight); with trigonometry in the tape
-        // the interval forms are dearer than the samples they save: gearlike 2^30 0.271 + 1.23 -> 0.64 + 0.99, knurling 2^27
-        // 0.364 + 1.52 -> 1.58 + 1.25, weave 2^33 6.6 + 24.2 -> 19.9 + 15.4.  Hence three levels for the lean tapes, two for
-        // the others -- which still list units of 2^3 samples instead of r03's cubes of 4^3.
-        const int cull_levels = c->cull_levels ? c->cull_levels : (kc == k_cull_lean || kc == k_cull_lean128 ? 3 : 2);
-        // (seven workgroups of 256 threads per CU instead of six -- 72 VGPRs, the interval state of 192 threads in LDS, so that
-        // every work item of the 512^3 example is resident at once -- was measured in r04k: example prepass 0.093 vs 0.091 ms,
-        // pawn 0.402 vs 0.266 ms: the levels then run in more passes.  Not the limit.)
-        const size_t ia_bytes = std::min<size_t>((size_t)cull_block * (6 * ia_np + 2 * ia_nd) * 8, c->lds_max - 896 - CULL_SCRATCH);
-        const size_t lds = 896 + CULL_SCRATCH + ia_bytes;
-        if (lds > 32768) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kc, dim3(nb), dim3(cull_block), lds, st,
-                           pruning ? (const uint32_t *)m->tapes.p : (const uint32_t *)t->d_code, (const double *)t->d_c64, g,
-                           (const int *)m->worklist.p, (const MeshCounters *)m->counters.p, pruning ? tape_stride : 0, (int)n_instr,
-                           ia_np, ia_nd, (int)ia_bytes, (unsigned char *)m->cull.p, (unsigned long long *)c->prof.p,
-                           tail_order ? (int *)m->order.p : (int *)nullptr, tail_max, cull_levels);
-        HIPCHK(hipGetLastError());
-    }
+    const bool tail_order = culling && c->tail_order && tail_max >= 2 && !call.collected;
+    s.key = grid_key(nx, ny, nz, call.bs, call.sparse, call.shard_index, call.shard_count);
+    if (culling && enqueue_cull(t, m, nb, tape_stride, tail_order, tail_max, st)) return 1;
     HIPCHK(hipEventRecord(cs.e2, st));
 
     // ---- meshing.  The whole chain (prepass -> k_mesh) is enqueued without a host round trip: the
@@ -1327,184 +1574,99 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
     // call: from the work-list length, which costs one synchronisation).  A soup that does not fit
     // is detected on the device (nothing is written past the capacity) and the pass is re-run into
     // a library buffer of the exact size. ----
-    unsigned long long cap = 0;
-    MeshCounters h;
-    bool to_caller = compact || (d_out && cap_out > 0);
+    unsigned long long soup_cap = 0;   // (0: into the call's own destination)
     bool quiet = true;     // nothing but k_mesh follows ev[2] on the stream, and the host did not stall in between
-    if (!to_caller) {
-        if (t->hint_key == key && t->hint_total_tris) {
-            cap = t->hint_total_tris + t->hint_total_tris / 4 + 4096;
-        } else {
-            quiet = false;
-            HIPCHK(hipMemcpyAsync(&h, m->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
-            HIPCHK(stream_wait(st));
-            const unsigned long long nshard0 = (unsigned long long)std::max(h.work_end - h.work_begin, 1);
-            cap = std::max<unsigned long long>(4096ull * nshard0, 1ull << 16);
-            // a guess, not a need (the overflow re-run finds the exact size): never more than half the free memory
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-                cap = std::min<unsigned long long>(cap, std::max<unsigned long long>(free_b / 2 / (72 + 40), 1ull << 16));   // (+ 40 B per triangle: the two-pass arenas)
-        }
-    }
-    float ms = 0;
+    if (call.dest == GenCall::SOUP && first_soup_cap(t, m, s.key, st, soup_cap, quiet)) return 1;
     for (int attempt = 0;; attempt++) {
-        MeshArgs a;
-        a.compact = 0; a.xf = nullptr; a.xf_cap = 0; a.raw = nullptr; a.raw_cap = 0;
-        a.twopass = 0; a.desc = nullptr; a.cells = nullptr; a.tlist = nullptr; a.cells_cap = a.tlist_cap = 0; a.block_item = nullptr;
-        a.order = tail_order ? (const int *)m->order.p : nullptr; a.tail = tail_order ? tail_max : 0;
-        if (compact) {
-            const SlabLayout L(slab_items, cap_out);
-            a.out = reinterpret_cast<double *>((unsigned char *)d_out + L.tris_off); a.out_cap = (unsigned long long)cap_out;
-            a.compact = 1; a.xf = reinterpret_cast<double *>((unsigned char *)d_out + L.xf_off);
-            a.raw = reinterpret_cast<float *>((unsigned char *)d_out + L.raw_off); a.raw_cap = L.raw_cap;
-            a.xf_cap = (int)std::min<int64_t>(slab_items, 0x7fffffff);
-        } else if (to_caller) {
-            a.out = (double *)d_out; a.out_cap = (unsigned long long)cap_out;
-        } else {
-            if (!m->out.p && !c->arena_pool.empty()) { m->out = c->arena_pool.back(); c->arena_pool.pop_back(); }
-            if (m->out.bytes < (size_t)cap * 72) quiet = false;     // (an allocation: the stream idles meanwhile)
-            if (m->out.ensure((size_t)cap * 72)) {
-                // a first-call guess that does not fit: shrink it and let the overflow re-run size the soup exactly
-                bool ok = false;
-                for (int k = 0; k < 6 && !ok && attempt == 0 && cap > (1ull << 16); k++) {
-                    cap = std::max<unsigned long long>(cap / 4, 1ull << 16);
-                    ok = m->out.ensure((size_t)cap * 72) == 0;
-                }
-                if (!ok) return 1;
-            }
-            a.out = (double *)m->out.p; a.out_cap = m->out.bytes / 72;
-        }
-        if (attempt) {   // (the first pass finds both cleared by k_compact)
-            HIPCHK(hipMemsetAsync(m->counters.p, 0, MESH_COUNTERS_RESET_BYTES, st));
-            HIPCHK(hipMemsetAsync(m->status.p, 0, (size_t)nb * 8, st));
-        }
-        a.g = g; a.worklist = (const int *)m->worklist.p;
-        a.kinds = (unsigned char *)m->kinds.p; a.status = (unsigned long long *)m->status.p;
-        a.ctr = (MeshCounters *)m->counters.p;
-        a.mc = (const McTables *)c->mc.p;
-        a.prof = (unsigned long long *)c->prof.p;
-        // One pass or two?  (decided here: the two-pass scheme parks nothing -- its triangles are numbered by k_scan_items -- so a
-        // call that takes it does not make its lane allocate park slots: 1.2 GB that the long jobs' lanes never touched, r04 advisor)
-        const bool twopass = c->twopass >= 0 ? c->twopass != 0 : n_instr > 96;
-        DevBuf &park = async_mode ? cs.park : c->park;   // (k_mesh kernels of calls in flight may overlap in time, whichever
-                                                         // streams they run on: each call slot has its own staging slots)
-        const bool parks = c->parking && !twopass;
-        if (parks && !park.p) { quiet = false; if (park.ensure((size_t)c->n_cu * MESH_PARK_DEPTH * SDF_PARK_TRIS * 36)) return 1; }
-        a.park = parks ? (float *)park.p : nullptr; a.park_cap = a.park ? SDF_PARK_TRIS : 0;
-        a.park_spins = (unsigned)c->park_spins;
-        a.cull = culling ? (const unsigned char *)m->cull.p : nullptr;
-        a.tape_stride = pruning ? tape_stride : 0;
-        a.n_instr = (int)n_instr;
-        // One pass or two?  The one-pass kernel (look-back + parking inside the sampling kernel) is 7 - 20 % faster on
-        // short tapes: it hides its triangle traffic behind other workgroups' arithmetic, which three kernels in a row
-        // cannot.  On long tapes (weave at 2^33, 244 instructions) the two schemes tie -- 27.5 vs 28.0 ms -- and the
-        // two-pass one moves a third of the bytes (9 GB against 25 GB per call: no parking, and the 4-slot sampling
-        // kernel spills less without the emit phases): the tape's length decides (sdf_ctx_set_twopass / SDF_MESH_TWOPASS
-        // override).
-        if (twopass) {
-            // the arenas of the two-pass scheme: a surface cell carries at least one triangle, so the soup's capacity
-            // bounds both (a call whose arenas turn out too small is flagged and repeated like one whose soup is)
-            const size_t cap_t = (size_t)a.out_cap;
-            if (m->desc.bytes < (size_t)nb * sizeof(ItemDesc) || m->cellrecs.bytes < cap_t * 36 || m->trilist.bytes < cap_t * 4) quiet = false;
-            if (m->desc.ensure((size_t)nb * sizeof(ItemDesc)) || m->cellrecs.ensure(cap_t * 36) || m->trilist.ensure(cap_t * 4) ||
-                m->blockidx.ensure(((cap_t + 255) / 256 + 2) * sizeof(int)))
-                return 1;
-            a.twopass = 1; a.desc = (ItemDesc *)m->desc.p; a.cells = (unsigned *)m->cellrecs.p; a.tlist = (unsigned *)m->trilist.p;
-            a.block_item = (const int *)m->blockidx.p;
-            a.cells_cap = a.tlist_cap = (unsigned long long)cap_t;
-        }
-        if (a.prof) {   // (words 16.. are k_cull's: cleared before the prepass; behind byte 512: the workgroups' timelines)
-            HIPCHK(hipMemsetAsync(a.prof, 0, 128, st));
-            HIPCHK(hipMemsetAsync((unsigned char *)a.prof + 512, 0, 4096 * 32, st));
-        }
-        const int grid = std::min(nb, c->n_cu);   // persistent workgroups; surplus ones find the list empty
-        const bool own_start = attempt > 0 || a.prof || !quiet;   // (something was enqueued, or the host waited, since ev[2])
-        if (own_start) HIPCHK(hipEventRecord(cs.e3, st));
-        if (launch_mesh(t, pruning ? m->tapes.p : (const void *)t->d_code, precision, a, grid, bs, st)) return 1;
-        if (a.twopass) {
-            const unsigned long long emit_blocks = (a.out_cap + 255ull) / 256ull;
-            if (emit_blocks > 0x7fffffffull) return fail("sdf_generate: soup capacity too large for one k_emit2 launch");
-            launch_k_scan_items(dim3(1), dim3(1024), st, (const ItemDesc *)m->desc.p, (MeshCounters *)m->counters.p,
-                               (unsigned long long *)m->status.p, (int *)m->blockidx.p, emit_blocks + 1ull);
-            launch_k_emit2(dim3((unsigned)std::max<unsigned long long>(emit_blocks, 1ull)), dim3(256), st, a);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(cs.e4, st));
-        if (compact) {
-            const unsigned pack_blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((slab_items + 255) / 256, 1), 1024);
-            HIPCHK((hipError_t)sdf_launch_pack_slab(pack_blocks, st, (const MeshCounters *)m->counters.p, (const unsigned long long *)m->status.p,
-                                                    (unsigned char *)d_out, (long long)slab_items, (long long)cap_out));
-        }
-        MeshCounters *hp = (MeshCounters *)(stage + SDF_STAGE_BYTES - 256);   // pinned
-        HIPCHK(hipMemcpyAsync(hp, m->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
-        if (async_mode && attempt == 0) {   // the caller collects the result with sdf_mesh_wait
+        if (mesh_attempt(call, m, s, st, attempt, soup_cap, quiet, culling, tail_order ? tail_max : 0, tape_stride)) return 1;
+        if (call.collected) {   // the caller collects the result with sdf_mesh_wait
             HIPCHK(hipEventRecord(cs.done, st));
             cs.busy = true; cs.owner = m;
             sdf_mesh::Pending &pd = m->pend;
-            pd.active = true; pd.tape = t; pd.slot = slot; pd.nb = nb; pd.bs = bs; pd.sparse = sparse; pd.precision = precision;
-            pd.pruning = pruning; pd.own_start = own_start; pd.n_instr = n_instr; pd.key = key; pd.compact = compact;
-            pd.d_out = d_out; pd.cap_out = cap_out; pd.shard_index = shard_index; pd.shard_count = shard_count;
-            pd.nx = nx; pd.ny = ny; pd.nz = nz;
-            pd.axes.assign(X, X + nx); pd.axes.insert(pd.axes.end(), Y, Y + ny); pd.axes.insert(pd.axes.end(), Z, Z + nz);
+            pd.active = true; pd.call = call; pd.got = s;
+            pd.axes.assign(call.X, call.X + nx); pd.axes.insert(pd.axes.end(), call.Y, call.Y + ny); pd.axes.insert(pd.axes.end(), call.Z, call.Z + nz);
+            pd.call.X = pd.axes.data(); pd.call.Y = pd.call.X + nx; pd.call.Z = pd.call.Y + ny;
             return 0;
         }
         HIPCHK(stream_wait(st));
-        h = *hp;
-        HIPCHK(hipEventElapsedTime(&ms, own_start ? cs.e3 : cs.e2, cs.e4));
-        m->st.ms_mesh = ms;
-        if (c->prof.p) {
-            unsigned long long pc[64];
-            HIPCHK(hipMemcpy(pc, c->prof.p, 512, hipMemcpyDeviceToHost));
-            {   // timeline of the workgroups: when each ran out of work and when it was done, relative to the first start
-                std::vector<unsigned long long> tl((size_t)4 * grid);
-                HIPCHK(hipMemcpy(tl.data(), (unsigned char *)c->prof.p + 512, tl.size() * 8, hipMemcpyDeviceToHost));
-                unsigned long long t0 = ~0ull, t_end = 0;
-                double s_out = 0, s_done = 0, mn_out = 1e30, mx_out = 0;
-                for (int i = 0; i < grid; i++) t0 = std::min(t0, tl[4 * i]);
-                for (int i = 0; i < grid; i++) {
-                    const double o = (double)(tl[4 * i + 1] - t0) * 0.01, d = (double)(tl[4 * i + 2] - t0) * 0.01;   // us
-                    s_out += o; s_done += d; mn_out = std::min(mn_out, o); mx_out = std::max(mx_out, o); t_end = std::max(t_end, tl[4 * i + 2]);
-                }
-                double first_hi = 0;   // the latest start: workgroups that were not resident from the beginning start late
-                for (int i = 0; i < grid; i++) first_hi = std::max(first_hi, (double)(tl[4 * i] - t0) * 0.01);
-                fprintf(stderr, "[k_mesh prof] %d workgroups (1 per CU), last of them started after %.1f us; out of work after min %.1f avg %.1f max %.1f us; done after avg %.1f, last %.1f us\n",
-                        grid, first_hi, mn_out, s_out / grid, mx_out, s_done / grid, (double)(t_end - t0) * 0.01);
-            }
-            fprintf(stderr, "[k_cull prof] work items by listed tasks (of 563; bins of 64, last: not culled): %llu %llu %llu %llu %llu %llu %llu %llu %llu | %llu\n",
-                    pc[32], pc[33], pc[34], pc[35], pc[36], pc[37], pc[38], pc[39], pc[40], pc[41]);
-            fprintf(stderr, "[k_cull prof] cycles of thread 0, summed over the workgroups: start %llu boxes %llu list %llu groups %llu (%llu passes, %llu groups) tasks %llu record %llu\n",
-                    pc[16], pc[17], pc[18], pc[19], pc[23], pc[22], pc[20], pc[21]);
-            fprintf(stderr, "[k_cull prof] task listing: which tasks %llu, scans %llu; start: range %llu batch %llu origin %llu axes %llu barrier %llu (rest: tape length)\n", pc[24], pc[25], pc[26], pc[27], pc[30], pc[28], pc[29]);
-            fprintf(stderr, "[k_mesh prof] sampling: intervals %llu task list %llu interpreter %llu sign bits %llu\n", pc[8], pc[9], pc[10], pc[11]);
-            fprintf(stderr, "[k_mesh prof] fine: atomic %llu barrier+rank %llu header %llu | rows %llu cells %llu | placing %llu look-back %llu | round end %llu\n",
-                    pc[42], pc[43], pc[44], pc[45], pc[46], pc[47], pc[48], pc[49]);
-            fprintf(stderr, "[k_mesh prof] %.3f ms; cycles/WG-sum: grab %llu sample %llu count %llu (of which placing the parked batch %llu) list %llu emit %llu tail %llu; %llu batches parked, %llu written one batch later from their slot\n",
-                    ms, pc[0], pc[1], pc[2], pc[6], pc[3], pc[4], pc[5], pc[7], pc[12]);
-        }
+        MeshCounters h;
+        const int rc = finish_call(m, call, s, slab, h);
+        if (c->prof.p && mesh_prof_report(c, std::min(nb, c->n_cu), m->st.ms_mesh)) return 1;
         m->st.n_retries = attempt;
-        if (h.overflow & 2u) return fail("sdf_generate: ordered-allocation look-back timed out");
-        if (compact) {   // (the synchronous records mode, sdf_generate_records: its caller sizes the slab again and repeats the call)
-            const SlabLayout L(slab_items, cap_out);
+        if (rc) return 1;
+        if (slab) {   // (the synchronous records mode, sdf_generate_records: its caller sizes the slab again and repeats the call)
+            const SlabLayout L(call.cap_items, call.cap_tris);
             const bool raw_over = (long long)h.n_raw > L.raw_cap;
             m->n_raw = (long long)h.n_raw;
-            m->rec_overflow = (h.overflow & 1u) != 0 || raw_over || (long long)(h.work_end - h.work_begin) > (long long)slab_items;
+            m->rec_overflow = (h.overflow & 1u) != 0 || raw_over || (long long)(h.work_end - h.work_begin) > (long long)call.cap_items;
             m->rec_need_tris = std::max<long long>((long long)h.total, raw_over ? (long long)h.n_raw * SLAB_RAW_DIV : 0ll);
             m->emitted_to = nullptr;
-            break;
+            return 0;
         }
-        if (h.overflow) {
-            if (attempt >= 3) return fail("sdf_generate: soup buffer overflow persists");
-            to_caller = false;                       // the exact need is known now: h.total
-            cap = h.total + 1024;
-            continue;
+        if (!h.overflow) {
+            m->emitted_to = soup_cap ? nullptr : call.d_out;
+            return 0;
         }
-        m->emitted_to = to_caller ? d_out : nullptr;
-        break;
+        if (attempt >= 3) return fail("sdf_generate: soup buffer overflow persists");
+        soup_cap = h.total + 1024;               // the exact need is known now: h.total
     }
-    float ms_pre = 0, ms_tot = 0;
-    HIPCHK(hipEventElapsedTime(&ms_pre, cs.e0, cs.e2));
-    HIPCHK(hipEventElapsedTime(&ms_tot, cs.e0, cs.e4));
-    finish_stats(t, m, h, nb, pruning, n_instr, key, ms_pre, ms_tot);
+}
+
+// at most this many batches per submission of the paths through device memory (generate_big, sdf_generate_field)
+enum { FIELD_CHUNK_MAX = 32 };
+
+// the tile of a batch at sample vol_off of a chunk's volume buffer
+static FieldTile field_tile(const double *X, const double *Y, const double *Z, const BatchBox &o, size_t vol_off) {
+    FieldTile tl;
+    tl.vol_off = (long long)vol_off; tl.n0 = o.lx; tl.n1 = o.ly; tl.n2 = o.lz; tl.pad_ = 0;
+    // scale = the batch's first axis step (reference sdf/core.py:58-59: `X[1] - X[0]` of the batch's slices);
+    // a one-sample axis has none and the tile has no cells, so its value is never used
+    tl.of[0] = X[o.ox]; tl.of[1] = Y[o.oy]; tl.of[2] = Z[o.oz];
+    tl.sc[0] = o.lx > 1 ? X[o.ox + 1] - X[o.ox] : 0.0; tl.sc[1] = o.ly > 1 ? Y[o.oy + 1] - Y[o.oy] : 0.0; tl.sc[2] = o.lz > 1 ? Z[o.oz + 1] - Z[o.oz] : 0.0;
+    return tl;
+}
+
+// One chunk of nt <= FIELD_CHUNK_MAX tiles whose float32 volumes (the context's field_vol) and FieldTile table (field_tiles) are
+// on the device, marched into the ordered soup behind its first `total` triangles: k_field_rows / k_scan_rows number the
+// triangles, the host reads the offsets and classifies the chunk's `batches` (kinds 1 = empty, 2 = non-empty), the soup
+// grows, k_field_emit writes `points * scale + offset`; waits for the chunk.  prefix (or NULL): per tile its inclusive
+// triangle prefix as a look-back word of the fused path.
+static int march_chunk(sdf_mesh *m, hipStream_t st, const int *batches, int nt, int slots, uint8_t *kinds, unsigned long long &total,
+                       unsigned long long *prefix) {
+    sdf_ctx *c = m->ctx;
+    const size_t nslots = (size_t)nt * slots;
+    launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
+                        (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots);
+    unsigned long long *d_total = (unsigned long long *)c->rows_off.p + nslots;
+    launch_k_scan_rows(dim3(1), dim3(1024), st, (const unsigned *)c->rows.p, (long long)nslots, (unsigned long long *)c->rows_off.p, d_total);
+    HIPCHK(hipGetLastError());
+    // (per tile only its first slot's offset and the chunk's total are needed on the host)
+    unsigned long long offs[FIELD_CHUNK_MAX + 1];
+    HIPCHK(hipMemcpy2DAsync(offs, 8, c->rows_off.p, (size_t)slots * 8, 8, (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&offs[nt], d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(st));
+    const unsigned long long chunk_total = offs[nt];
+    for (int j = 0; j < nt; j++) {
+        const unsigned long long cnt = offs[j + 1] - offs[j];
+        kinds[(size_t)batches[j]] = cnt ? 2 : 1;
+        if (cnt) m->st.n_nonempty++; else m->st.n_empty++;
+        if (prefix) prefix[j] = MESH_FLAG_PFX | (total + offs[j + 1]);
+    }
+    if (!chunk_total) return 0;
+    if ((total + chunk_total) * 72 > m->out.bytes) {       // grow the soup (geometric), keeping what is there
+        DevBuf bigger;
+        if (bigger.ensure(std::max<size_t>((size_t)(total + chunk_total) * 72 * 2, (size_t)1 << 22))) return 1;
+        if (total) HIPCHK(hipMemcpyAsync(bigger.p, m->out.p, (size_t)total * 72, hipMemcpyDeviceToDevice, st));
+        HIPCHK(stream_wait(st));
+        m->out.release();
+        m->out = bigger;
+    }
+    launch_k_field_emit(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
+                        (const FieldTile *)c->field_tiles.p, (const unsigned long long *)c->rows_off.p, (double *)m->out.p, total,
+                        (unsigned long long)(m->out.bytes / 72), slots);
+    HIPCHK(hipGetLastError());
+    HIPCHK(stream_wait(st));   // (the chunk's buffers are refilled next)
+    total += chunk_total;
     return 0;
 }
 
@@ -1515,16 +1677,15 @@ static int generate_impl(sdf_tape *t, sdf_mesh *m, const double *X, int nx, cons
 // `points * scale + offset` into the ordered float64 soup -- the kernels behind sdf_generate_field, with the tape instead of a
 // host callback.  The skip test is k_skip's, the work list k_compact's.  One host synchronisation per chunk: a chunk is
 // >= 2.7e5 samples per batch, the launches are long.  Synchronous; the soup lives in library memory.
-static int generate_big(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const double *Y, int ny, const double *Z, int nz,
-                        int bs, int sparse, int64_t shard_index, int64_t shard_count, int precision) {
+static int generate_big(sdf_mesh *m, const GenCall &call) {
+    sdf_tape *t = call.tape;
     sdf_ctx *c = t->ctx;
     hipStream_t st = c->stream;
+    const double *X = call.X, *Y = call.Y, *Z = call.Z;
+    const int nx = call.nx, ny = call.ny, nz = call.nz, bs = call.bs;
     GridDesc &g = m->g;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
-    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
-    const long long nb64 = (long long)g.nbx * g.nby * g.nbz;
-    if (nb64 > 0x7fffffffLL) return fail("sdf_generate: too many batches");
-    const int nb = (int)nb64;
+    int nb = 0;
+    if (grid_batches(nx, ny, nz, bs, "sdf_generate", g, nb)) return 1;
     m->st.n_batches = nb;
     m->st.n_grid_voxels = (int64_t)nx * ny * nz;
     if (nb == 0) return 0;
@@ -1537,10 +1698,10 @@ static int generate_big(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const
     HIPCHK(hipMemcpyAsync(dX, X, (size_t)nx * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dY, Y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)nz * 8, hipMemcpyHostToDevice, st));
-    if (sparse) { if (enqueue_skip(t, dX, nx, ny, nz, bs, 0, nb, precision, (unsigned char *)m->kinds.p, st)) return 1; }
+    if (call.sparse) { if (enqueue_skip(t, dX, nx, ny, nz, bs, 0, nb, call.precision, (unsigned char *)m->kinds.p, st)) return 1; }
     else HIPCHK(hipMemsetAsync(m->kinds.p, 255, (size_t)nb, st));
     launch_k_compact(dim3(1), dim3(1024), st, (const unsigned char *)m->kinds.p, nb, (int *)m->worklist.p, (MeshCounters *)m->counters.p,
-                     (unsigned long long *)m->status.p, (long long)shard_index, (long long)shard_count);
+                     (unsigned long long *)m->status.p, (long long)call.shard_index, (long long)call.shard_count);
     HIPCHK(hipGetLastError());
     MeshCounters h;
     HIPCHK(hipMemcpyAsync(&h, m->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -1556,10 +1717,9 @@ static int generate_big(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const
 
     const size_t tile_max = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
     const int slots = (bs * bs + 255) & ~255;                                          // row slots per tile
-    const int CH = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)256 << 20) / (tile_max * 4)));   // batches per submission: <= 256 MB of volumes
+    const int CH = (int)std::max<size_t>(1, std::min<size_t>(FIELD_CHUNK_MAX, ((size_t)256 << 20) / (tile_max * 4)));   // batches per submission: <= 256 MB of volumes
     std::vector<FieldTile> tiles((size_t)CH);
     std::vector<int> org((size_t)CH * 3);
-    std::vector<unsigned long long> offs((size_t)CH * slots + 1);
     if (c->field_vol.ensure((size_t)CH * tile_max * 4) || c->field_tiles.ensure(sizeof(FieldTile) * CH + (size_t)CH * 12) ||
         c->rows.ensure((size_t)CH * slots * 4) || c->rows_off.ensure(((size_t)CH * slots + 1) * 8))
         return 1;
@@ -1572,56 +1732,18 @@ static int generate_big(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const
         const int nt = std::min(CH, h.work_end - w0);
         size_t npts = 0, big = 0;
         for (int j = 0; j < nt; j++) {
-            const int b = work[(size_t)(w0 + j)];
-            const int ibz = b % g.nbz, iby = (b / g.nbz) % g.nby, ibx = b / (g.nbz * g.nby);       // (batch_origin, sdf_device.h)
-            const int ox = ibx * bs, oy = iby * bs, oz = ibz * bs;
-            const int lx = std::min(bs + 1, nx - ox), ly = std::min(bs + 1, ny - oy), lz = std::min(bs + 1, nz - oz);
-            FieldTile &tl = tiles[(size_t)j];
-            tl.vol_off = (long long)npts; tl.n0 = lx; tl.n1 = ly; tl.n2 = lz; tl.pad_ = 0;
-            tl.of[0] = X[ox]; tl.of[1] = Y[oy]; tl.of[2] = Z[oz];
-            tl.sc[0] = lx > 1 ? X[ox + 1] - X[ox] : 0.0; tl.sc[1] = ly > 1 ? Y[oy + 1] - Y[oy] : 0.0; tl.sc[2] = lz > 1 ? Z[oz + 1] - Z[oz] : 0.0;
-            org[(size_t)3 * j] = ox; org[(size_t)3 * j + 1] = oy; org[(size_t)3 * j + 2] = oz;
-            const size_t n = (size_t)lx * ly * lz;
+            const BatchBox o = batch_box(g, work[(size_t)(w0 + j)]);
+            tiles[(size_t)j] = field_tile(X, Y, Z, o, npts);
+            org[(size_t)3 * j] = o.ox; org[(size_t)3 * j + 1] = o.oy; org[(size_t)3 * j + 2] = o.oz;
+            const size_t n = (size_t)o.lx * o.ly * o.lz;
             npts += n; big = std::max(big, n);
             m->st.n_eval_voxels += (int64_t)n;
         }
-        const size_t nslots = (size_t)nt * slots;
         HIPCHK(hipMemcpyAsync(c->field_tiles.p, tiles.data(), sizeof(FieldTile) * (size_t)nt, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_org, org.data(), (size_t)nt * 12, hipMemcpyHostToDevice, st));
-        LAUNCH_TAPE_ON(st, k_eval_tiles, dim3((unsigned)((big + 255) / 256), (unsigned)nt), dim3(256), 0, t, precision, (const double *)dX,
+        LAUNCH_TAPE_ON(st, k_eval_tiles, dim3((unsigned)((big + 255) / 256), (unsigned)nt), dim3(256), 0, t, call.precision, (const double *)dX,
                        (const double *)dY, (const double *)dZ, (const FieldTile *)c->field_tiles.p, (const int *)d_org, (float *)c->field_vol.p);
-        launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                            (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots);
-        unsigned long long *d_total = (unsigned long long *)c->rows_off.p + nslots;
-        launch_k_scan_rows(dim3(1), dim3(1024), st, (const unsigned *)c->rows.p, (long long)nslots, (unsigned long long *)c->rows_off.p, d_total);
-        HIPCHK(hipGetLastError());
-        // (per tile only its first slot's offset and the chunk's total are needed on the host)
-        HIPCHK(hipMemcpy2DAsync(offs.data(), 8, c->rows_off.p, (size_t)slots * 8, 8, (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&offs[(size_t)nt], d_total, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(stream_wait(st));
-        const unsigned long long chunk_total = offs[(size_t)nt];
-        for (int j = 0; j < nt; j++) {
-            const unsigned long long cnt = offs[(size_t)j + 1] - offs[(size_t)j];
-            kinds[(size_t)work[(size_t)(w0 + j)]] = cnt ? 2 : 1;
-            if (cnt) m->st.n_nonempty++; else m->st.n_empty++;
-            prefix[(size_t)(w0 + j - h.work_begin)] = MESH_FLAG_PFX | (total + offs[(size_t)j + 1]);
-        }
-        if (chunk_total) {
-            if ((total + chunk_total) * 72 > m->out.bytes) {       // grow the soup (geometric), keeping what is there
-                DevBuf bigger;
-                if (bigger.ensure(std::max<size_t>((size_t)(total + chunk_total) * 72 * 2, (size_t)1 << 22))) return 1;
-                if (total) HIPCHK(hipMemcpyAsync(bigger.p, m->out.p, (size_t)total * 72, hipMemcpyDeviceToDevice, st));
-                HIPCHK(stream_wait(st));
-                m->out.release();
-                m->out = bigger;
-            }
-            launch_k_field_emit(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                                (const FieldTile *)c->field_tiles.p, (const unsigned long long *)c->rows_off.p, (double *)m->out.p, total,
-                                (unsigned long long)(m->out.bytes / 72), slots);
-            HIPCHK(hipGetLastError());
-            HIPCHK(stream_wait(st));   // (the chunk's buffers are refilled next)
-            total += chunk_total;
-        }
+        if (march_chunk(m, st, &work[(size_t)w0], nt, slots, kinds.data(), total, &prefix[(size_t)(w0 - h.work_begin)])) return 1;
     }
     HIPCHK(hipEventRecord(c->ev[2], st));
     m->st.n_triangles = (int64_t)total;
@@ -1642,32 +1764,30 @@ static int generate_big(sdf_tape *t, sdf_mesh *m, const double *X, int nx, const
 
 extern "C" {
 
-int sdf_mesh_destroy(sdf_mesh *m);
-
-static int generate_entry(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
-                          int sparse, int64_t shard_index, int64_t shard_count, int precision, void *d_out, int64_t cap_out,
-                          sdf_mesh **out, bool async_mode = false, int64_t slab_items = -1, const unsigned char *d_kinds_in = nullptr) {
-    if (!t || !X || !Y || !Z || !out) return fail("sdf_generate: NULL argument");
+// every check and message of sdf_generate, then the call: fused, or through device memory for batch_size > 32
+static int generate_entry(const GenCall &call, sdf_mesh **out) {
+    sdf_tape *t = call.tape;
+    const int bs = call.bs, precision = call.precision;
+    if (!t || !call.X || !call.Y || !call.Z || !out) return fail("sdf_generate: NULL argument");
     *out = nullptr;
     if (t->n_extern) return fail("sdf_generate: the tape reads user closures (L_EXTERN): mesh it with sdf_generate_field");
     if (bs < 1 || bs > SDF_BATCH_SIZE_MAX) return fail("sdf_generate: batch_size must be in 1..512");
-    if (bs > 32 && slab_items >= 0) return fail("sdf_generate_compact: batch_size must be in 1..32 (batches of more than 33^3 samples are not part of the multi-GPU exchange)");
-    if (bs > 32 && d_kinds_in) return fail("sdf_generate_from_kinds: batch_size must be in 1..32");
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail("sdf_generate: bad shard");
+    if (bs > 32 && call.dest == GenCall::SLAB) return fail("sdf_generate_compact: batch_size must be in 1..32 (batches of more than 33^3 samples are not part of the multi-GPU exchange)");
+    if (bs > 32 && call.d_kinds) return fail("sdf_generate_from_kinds: batch_size must be in 1..32");
+    if (call.shard_count < 1 || call.shard_index < 0 || call.shard_index >= call.shard_count) return fail("sdf_generate: bad shard");
     if (precision == SDF_PRECISION_F32)
         return fail("sdf_generate: the meshing path samples in float64 (the reference's arithmetic); SDF_PRECISION_F32 was a diagnostic until round 4 -- "
                     "outside the 1e-5 tolerance at its maximum, slower than float64 behind the interval passes -- and was removed; sdf_eval_* and "
                     "sdf_estimate_bounds keep both precisions");
     if (precision != SDF_PRECISION_F64) return fail("sdf_generate: bad precision");
-    if (nx < 0 || ny < 0 || nz < 0) return fail("sdf_generate: negative axis length");
+    if (call.nx < 0 || call.ny < 0 || call.nz < 0) return fail("sdf_generate: negative axis length");
     sdf_ctx *c = t->ctx;
     HIPCHK(set_device(c->device));
     sdf_mesh *m = new sdf_mesh();
     m->ctx = c;
     // (batch_size > 32: through device memory, synchronously, into library memory -- a caller buffer is reported as not filled,
     // like one that was too small: sdf_mesh_emit_device copies)
-    if (bs > 32 ? generate_big(t, m, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision)
-                : generate_impl(t, m, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision, d_out, cap_out, async_mode, slab_items, nullptr, d_kinds_in)) {
+    if (bs > 32 ? generate_big(m, call) : generate_impl(m, call)) {
         const std::string keep = g_err;
         sdf_mesh_destroy(m);
         g_err = keep;
@@ -1677,9 +1797,18 @@ static int generate_entry(sdf_tape *t, const double *X, int nx, const double *Y,
     return 0;
 }
 
+// the part of a call descriptor that every entry point takes as arguments
+static GenCall gen_call(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs, int sparse,
+                        int64_t shard_index, int64_t shard_count, int precision) {
+    GenCall call;
+    call.tape = t; call.X = X; call.Y = Y; call.Z = Z; call.nx = nx; call.ny = ny; call.nz = nz;
+    call.bs = bs; call.sparse = sparse; call.precision = precision; call.shard_index = shard_index; call.shard_count = shard_count;
+    return call;
+}
+
 int sdf_generate(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
                  int sparse, int64_t shard_index, int64_t shard_count, int precision, sdf_mesh **out) {
-    return generate_entry(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision, nullptr, 0, out);
+    return generate_entry(gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision), out);
 }
 
 int sdf_generate_to_device(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
@@ -1687,7 +1816,9 @@ int sdf_generate_to_device(sdf_tape *t, const double *X, int nx, const double *Y
                            int64_t cap_tris, int *emitted, sdf_mesh **out) {
     if (emitted) *emitted = 0;
     if (!d_out || cap_tris <= 0) return fail("sdf_generate_to_device: output buffer is NULL or empty");
-    if (generate_entry(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision, d_out, cap_tris, out)) return 1;
+    GenCall call = gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision);
+    call.dest = GenCall::CALLER; call.d_out = d_out; call.cap_tris = cap_tris;
+    if (generate_entry(call, out)) return 1;
     if (emitted) *emitted = ((*out)->emitted_to == d_out || (*out)->st.n_triangles == 0) ? 1 : 0;
     return 0;
 }
@@ -1695,14 +1826,19 @@ int sdf_generate_to_device(sdf_tape *t, const double *X, int nx, const double *Y
 int sdf_generate_from_kinds(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
                             int64_t shard_index, int64_t shard_count, int precision, const void *d_kinds, sdf_mesh **out) {
     if (!d_kinds) return fail("sdf_generate_from_kinds: d_kinds is NULL");
-    return generate_entry(t, X, nx, Y, ny, Z, nz, bs, 1, shard_index, shard_count, precision, nullptr, 0, out, false, -1, (const unsigned char *)d_kinds);
+    GenCall call = gen_call(t, X, nx, Y, ny, Z, nz, bs, 1, shard_index, shard_count, precision);
+    call.d_kinds = (const unsigned char *)d_kinds;
+    return generate_entry(call, out);
 }
 
 int sdf_generate_to_device_async(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
                                  int sparse, int64_t shard_index, int64_t shard_count, int precision, void *d_out,
                                  int64_t cap_tris, sdf_mesh **out) {
     if (!d_out || cap_tris <= 0) return fail("sdf_generate_to_device_async: output buffer is NULL or empty");
-    return generate_entry(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision, d_out, cap_tris, out, true);
+    GenCall call = gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision);
+    call.dest = GenCall::CALLER; call.d_out = d_out; call.cap_tris = cap_tris;
+    call.collected = true;
+    return generate_entry(call, out);
 }
 
 // `generate` for a caller who wants the soup ON THE HOST (what the reference's `generate` returns, sdf/core.py:131-141): the triangles
@@ -1719,9 +1855,11 @@ int sdf_generate_records(sdf_tape *t, const double *X, int nx, const double *Y, 
     sdf_ctx *c = t->ctx;
     const unsigned long long key = grid_key(nx, ny, nz, bs, sparse, 0, 1);
     const auto it = c->rec_hints.find(std::make_pair(t->content_hash, key));
-    const long long nb64 = (long long)((nx + std::max(bs, 1) - 1) / std::max(bs, 1)) * ((ny + std::max(bs, 1) - 1) / std::max(bs, 1)) * ((nz + std::max(bs, 1) - 1) / std::max(bs, 1));
+    GridDesc g;
+    const long long nb64 = grid_desc(nx, ny, nz, bs, g);
+    GenCall call = gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, 0, 1, precision);
     if (bs < 1 || bs > 32 || t->n_extern || it == c->rec_hints.end() || nb64 <= 0 || nb64 > 0x7fffffffLL || precision != SDF_PRECISION_F64)
-        return generate_entry(t, X, nx, Y, ny, Z, nz, bs, sparse, 0, 1, precision, nullptr, 0, out);     // (every check and message of sdf_generate)
+        return generate_entry(call, out);     // (every check and message of sdf_generate)
     HIPCHK(set_device(c->device));
     long long cap_tris = (long long)(it->second.tris + it->second.tris / 64 + 1024);
     if ((long long)it->second.raw > cap_tris / SLAB_RAW_DIV + SLAB_RAW_MIN) cap_tris = std::max<long long>(cap_tris, (long long)(it->second.raw + it->second.raw / 8) * SLAB_RAW_DIV);
@@ -1734,7 +1872,8 @@ int sdf_generate_records(sdf_tape *t, const double *X, int nx, const double *Y, 
         m->slab_items = nb64; m->slab_tris = cap_tris;
         const SlabLayout L(m->slab_items, m->slab_tris);
         int rc = m->slab.ensure(L.bytes);
-        if (!rc) rc = generate_impl(t, m, X, nx, Y, ny, Z, nz, bs, sparse, 0, 1, precision, m->slab.p, cap_tris, false, m->slab_items);
+        call.dest = GenCall::SLAB; call.d_out = m->slab.p; call.cap_items = m->slab_items; call.cap_tris = cap_tris;
+        if (!rc) rc = generate_impl(m, call);
         if (!rc && m->rec_overflow && attempt >= 3) rc = fail("sdf_generate_records: slab overflow persists");
         if (rc) {
             const std::string keep = g_err;
@@ -1772,22 +1911,14 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
         ~Guard() { const std::string keep = g_err; if (a) sdf_host_free(a); if (b) sdf_host_free(b); if (m) sdf_mesh_destroy(m); g_err = keep; }
     } guard{m, h_pts, h_vals};
     GridDesc &g = m->g;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
-    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
-    const long long nb64 = (long long)g.nbx * g.nby * g.nbz;
-    if (nb64 > 0x7fffffffLL) return fail("sdf_generate_field: too many batches");
-    const int nb = (int)nb64;
+    int nb = 0;
+    if (grid_batches(nx, ny, nz, bs, "sdf_generate_field", g, nb)) return 1;
     m->st.n_batches = nb;
     m->st.n_grid_voxels = (int64_t)nx * ny * nz;
     if (nb == 0) { *out = m; m = nullptr; return 0; }
-    auto origin = [&](int b, int &ox, int &oy, int &oz, int &lx, int &ly, int &lz) {   // (batch_origin, sdf_device.h)
-        const int ibz = b % g.nbz, iby = (b / g.nbz) % g.nby, ibx = b / (g.nbz * g.nby);
-        ox = ibx * bs; oy = iby * bs; oz = ibz * bs;
-        lx = std::min(bs + 1, nx - ox); ly = std::min(bs + 1, ny - oy); lz = std::min(bs + 1, nz - oz);
-    };
     const size_t tile_max = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
     const int slots = bs <= 32 ? 1024 : ((bs * bs + 255) & ~255);                      // row slots per tile (k_field_rows)
-    const int CH = (int)std::max<size_t>(1, std::min<size_t>(32, ((size_t)64 << 20) / tile_max));   // batches per submission: <= 64 M points = 2 GB of pinned points + values -- except that ONE tile is always taken whole: (512 + 1)^3 points = 4.3 GB at the largest batch size
+    const int CH = (int)std::max<size_t>(1, std::min<size_t>(FIELD_CHUNK_MAX, ((size_t)64 << 20) / tile_max));   // batches per submission: <= 64 M points = 2 GB of pinned points + values -- except that ONE tile is always taken whole: (512 + 1)^3 points = 4.3 GB at the largest batch size
     const size_t pts_cap = std::max<size_t>((size_t)CH * tile_max, (size_t)9 << 12);   // points per callback
     if (sdf_host_alloc(pts_cap * 24, &h_pts) || sdf_host_alloc(pts_cap * 8, &h_vals)) return 1;
     double *pts = (double *)h_pts, *vals = (double *)h_vals;
@@ -1799,9 +1930,8 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
         for (int b0 = 0; b0 < nb; b0 += per) {
             const int n = std::min(per, nb - b0);
             for (int j = 0; j < n; j++) {
-                int ox, oy, oz, lx, ly, lz;
-                origin(b0 + j, ox, oy, oz, lx, ly, lz);
-                const double x0 = X[ox], x1 = X[ox + lx - 1], y0 = Y[oy], y1 = Y[oy + ly - 1], z0 = Z[oz], z1 = Z[oz + lz - 1];
+                const BatchBox o = batch_box(g, b0 + j);
+                const double x0 = X[o.ox], x1 = X[o.ox + o.lx - 1], y0 = Y[o.oy], y1 = Y[o.oy + o.ly - 1], z0 = Z[o.oz], z1 = Z[o.oz + o.lz - 1];
                 double *p = pts + (size_t)j * 27;
                 p[0] = (x0 + x1) / 2; p[1] = (y0 + y1) / 2; p[2] = (z0 + z1) / 2;
                 for (int k = 0; k < 8; k++) {             // itertools.product((x0, x1), (y0, y1), (z0, z1))
@@ -1810,9 +1940,8 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
             }
             if (field(user, pts, (int64_t)n * 9, vals)) return fail("sdf_generate_field: the field callback failed");
             for (int j = 0; j < n; j++) {
-                int ox, oy, oz, lx, ly, lz;
-                origin(b0 + j, ox, oy, oz, lx, ly, lz);
-                const double x0 = X[ox], y0 = Y[oy], z0 = Z[oz];
+                const BatchBox o = batch_box(g, b0 + j);
+                const double x0 = X[o.ox], y0 = Y[o.oy], z0 = Z[o.oz];
                 const double *p = pts + (size_t)j * 27, *v = vals + (size_t)j * 9;
                 const double r = fabs(v[0]);
                 const double d = sqrt(((p[0] - x0) * (p[0] - x0) + (p[1] - y0) * (p[1] - y0)) + (p[2] - z0) * (p[2] - z0));
@@ -1833,26 +1962,19 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
 
     // ---- `_worker` for the shard's batches, CH at a time ----
     std::vector<FieldTile> tiles((size_t)CH);
-    std::vector<unsigned long long> offs((size_t)CH * slots + 1);
     unsigned long long total = 0;
     for (int w0 = w_begin; w0 < w_end; w0 += CH) {
         const int nt = std::min(CH, w_end - w0);
         size_t npts = 0;
         for (int j = 0; j < nt; j++) {
-            int ox, oy, oz, lx, ly, lz;
-            origin(work[(size_t)(w0 + j)], ox, oy, oz, lx, ly, lz);
-            FieldTile &tl = tiles[(size_t)j];
-            tl.vol_off = (long long)npts; tl.n0 = lx; tl.n1 = ly; tl.n2 = lz; tl.pad_ = 0;
-            // scale = the batch's first axis step (reference sdf/core.py:58-59: `X[1] - X[0]` of the batch's slices);
-            // a one-sample axis has none and the tile has no cells, so its value is never used
-            tl.of[0] = X[ox]; tl.of[1] = Y[oy]; tl.of[2] = Z[oz];
-            tl.sc[0] = lx > 1 ? X[ox + 1] - X[ox] : 0.0; tl.sc[1] = ly > 1 ? Y[oy + 1] - Y[oy] : 0.0; tl.sc[2] = lz > 1 ? Z[oz + 1] - Z[oz] : 0.0;
+            const BatchBox o = batch_box(g, work[(size_t)(w0 + j)]);
+            tiles[(size_t)j] = field_tile(X, Y, Z, o, npts);
             double *p = pts + npts * 3;
-            for (int ix = 0; ix < lx; ix++)
-                for (int iy = 0; iy < ly; iy++)
-                    for (int iz = 0; iz < lz; iz++, p += 3) { p[0] = X[ox + ix]; p[1] = Y[oy + iy]; p[2] = Z[oz + iz]; }
-            npts += (size_t)lx * ly * lz;
-            m->st.n_eval_voxels += (int64_t)lx * ly * lz;
+            for (int ix = 0; ix < o.lx; ix++)
+                for (int iy = 0; iy < o.ly; iy++)
+                    for (int iz = 0; iz < o.lz; iz++, p += 3) { p[0] = X[o.ox + ix]; p[1] = Y[o.oy + iy]; p[2] = Z[o.oz + iz]; }
+            npts += (size_t)o.lx * o.ly * o.lz;
+            m->st.n_eval_voxels += (int64_t)o.lx * o.ly * o.lz;
         }
         if (field(user, pts, (int64_t)npts, vals)) return fail("sdf_generate_field: the field callback failed");
         const size_t nslots = (size_t)nt * slots;
@@ -1863,36 +1985,7 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
         HIPCHK(hipMemcpyAsync(c->field_tiles.p, tiles.data(), sizeof(FieldTile) * (size_t)nt, hipMemcpyHostToDevice, c->stream));
         launch_k_cast_f32(dim3((unsigned)((npts + 255) / 256)), dim3(256), c->stream, (const double *)c->field_vals.p,
                            (float *)c->field_vol.p, (long long)npts);
-        launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), c->stream, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                           (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots);
-        unsigned long long *d_total = (unsigned long long *)c->rows_off.p + nslots;
-        launch_k_scan_rows(dim3(1), dim3(1024), c->stream, (const unsigned *)c->rows.p, (long long)nslots,
-                           (unsigned long long *)c->rows_off.p, d_total);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(offs.data(), c->rows_off.p, (nslots + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(stream_wait(c->stream));
-        const unsigned long long chunk_total = offs[nslots];
-        for (int j = 0; j < nt; j++) {
-            const unsigned long long cnt = offs[(size_t)(j + 1) * slots] - offs[(size_t)j * slots];
-            kinds[(size_t)work[(size_t)(w0 + j)]] = cnt ? 2 : 1;
-            if (cnt) m->st.n_nonempty++; else m->st.n_empty++;
-        }
-        if (chunk_total) {
-            if ((total + chunk_total) * 72 > m->out.bytes) {       // grow the soup (geometric), keeping what is there
-                DevBuf bigger;
-                if (bigger.ensure(std::max<size_t>((size_t)(total + chunk_total) * 72 * 2, (size_t)1 << 22))) return 1;
-                if (total) HIPCHK(hipMemcpyAsync(bigger.p, m->out.p, (size_t)total * 72, hipMemcpyDeviceToDevice, c->stream));
-                HIPCHK(stream_wait(c->stream));
-                m->out.release();
-                m->out = bigger;
-            }
-            launch_k_field_emit(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), c->stream, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                               (const FieldTile *)c->field_tiles.p, (const unsigned long long *)c->rows_off.p, (double *)m->out.p, total,
-                               (unsigned long long)(m->out.bytes / 72), slots);
-            HIPCHK(hipGetLastError());
-            HIPCHK(stream_wait(c->stream));   // (the chunk's buffers are refilled next)
-            total += chunk_total;
-        }
+        if (march_chunk(m, c->stream, &work[(size_t)w0], nt, slots, kinds.data(), total, nullptr)) return 1;
     }
     m->st.n_triangles = (int64_t)total;
     m->st.n_sampled_voxels = m->st.n_eval_voxels;
@@ -1914,7 +2007,10 @@ int sdf_generate_compact_async(sdf_tape *t, const double *X, int nx, const doubl
                                int sparse, int64_t shard_index, int64_t shard_count, int precision, void *d_slab,
                                int64_t cap_items, int64_t cap_tris, sdf_mesh **out) {
     if (!d_slab || cap_items < 0 || cap_tris < 0) return fail("sdf_generate_compact_async: slab is NULL or its capacities are negative");
-    return generate_entry(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision, d_slab, cap_tris, out, true, cap_items);
+    GenCall call = gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision);
+    call.dest = GenCall::SLAB; call.d_out = d_slab; call.cap_items = cap_items; call.cap_tris = cap_tris;
+    call.collected = true;
+    return generate_entry(call, out);
 }
 
 int sdf_expand_slabs(sdf_ctx *c, const void *const *d_slabs, int n_slabs, int64_t cap_items, int64_t cap_tris, void *d_out, int64_t cap_out) {
@@ -1937,34 +2033,29 @@ int sdf_mesh_wait(sdf_mesh *m, int *emitted) {
     if (pd.active) {
         sdf_ctx *c = m->ctx;
         HIPCHK(set_device(c->device));
-        CallSlot &cs = c->slots[pd.slot];
+        CallSlot &cs = c->slots[pd.got.slot];
         HIPCHK(event_wait(cs.done));
         pd.active = false;
-        const MeshCounters h = *(const MeshCounters *)((char *)c->h_stage + (size_t)pd.slot * SDF_STAGE_BYTES + SDF_STAGE_BYTES - 256);
-        float ms = 0, ms_pre = 0, ms_tot = 0;
-        HIPCHK(hipEventElapsedTime(&ms, pd.own_start ? cs.e3 : cs.e2, cs.e4));
-        HIPCHK(hipEventElapsedTime(&ms_pre, cs.e0, cs.e2));
-        HIPCHK(hipEventElapsedTime(&ms_tot, cs.e0, cs.e4));
-        m->st.ms_mesh = ms;
+        const bool slab = pd.call.dest == GenCall::SLAB;
+        MeshCounters h;
+        const int rc = finish_call(m, pd.call, pd.got, slab, h);
         cs.busy = false; cs.owner = nullptr;      // (everything the slot held for this mesh has been read)
-        if (h.overflow & 2u) return fail("sdf_generate: ordered-allocation look-back timed out");
-        if (h.overflow && pd.compact) {
+        if (rc) return 1;
+        if (h.overflow && slab) {
             // a slab that was too small: the exchange protocol retries with larger slabs on EVERY rank (sdf_amd/dist.py)
-            finish_stats(pd.tape, m, h, pd.nb, pd.pruning, pd.n_instr, pd.key, ms_pre, ms_tot);
             m->emitted_to = nullptr;
         } else if (h.overflow) {
             // the soup did not fit the caller's buffer: the call is repeated synchronously into library memory
             // (sized from the count just learned)
-            pd.tape->hint_key = pd.key; pd.tape->hint_total_tris = std::max<unsigned long long>(h.total, 1);
-            const double *X = pd.axes.data(), *Y = X + pd.nx, *Z = Y + pd.ny;
-            if (generate_impl(pd.tape, m, X, pd.nx, Y, pd.ny, Z, pd.nz, pd.bs, pd.sparse, pd.shard_index, pd.shard_count, pd.precision,
-                              nullptr, 0, false))
-                return 1;
+            pd.call.tape->hint_key = pd.got.key; pd.call.tape->hint_total_tris = std::max<unsigned long long>(h.total, 1);
+            GenCall again = pd.call;
+            again.dest = GenCall::SOUP; again.d_out = nullptr; again.cap_tris = 0;
+            again.collected = false;
+            if (generate_impl(m, again)) return 1;
             m->st.n_retries += 1;
         } else {
-            m->emitted_to = pd.compact ? nullptr : pd.d_out;
+            m->emitted_to = slab ? nullptr : pd.call.d_out;
             m->st.n_retries = 0;
-            finish_stats(pd.tape, m, h, pd.nb, pd.pruning, pd.n_instr, pd.key, ms_pre, ms_tot);
         }
         pd.axes.clear(); pd.axes.shrink_to_fit();
     }
@@ -2323,7 +2414,7 @@ int sdf_mesh_destroy(sdf_mesh *m) {
     (void)hipSetDevice(c->device);
     (void)stream_wait(c->stream);
     if (m->stream) (void)stream_wait(m->stream);        // (a call slot's lane)
-    if (m->pend.active) { c->slots[m->pend.slot].busy = false; c->slots[m->pend.slot].owner = nullptr; m->pend.active = false; }   // (abandoned; the stream is idle now)
+    if (m->pend.active) { c->slots[m->pend.got.slot].busy = false; c->slots[m->pend.got.slot].owner = nullptr; m->pend.active = false; }   // (abandoned; the stream is idle now)
     if (m->out.p) {   // keep one soup buffer around for the next call
         if (c->arena_pool.empty()) c->arena_pool.push_back(m->out);
         else if (c->arena_pool.back().bytes < m->out.bytes) { c->arena_pool.back().release(); c->arena_pool.back() = m->out; }
