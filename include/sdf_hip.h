@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 11
+#define SDF_ABI_VERSION 12
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -156,6 +156,16 @@ int sdf_eval_points_extern_host(sdf_tape *tape, const double *h_points, int64_t 
 int sdf_mesh_level_set_host(sdf_ctx *ctx, const double *h_points, int64_t n_points, const int32_t *h_tris, int64_t n_tris,
                             double voxel_size, int half_width_voxels, int64_t out_ijk0[3], int64_t out_dims[3], float *h_out,
                             int64_t cap_voxels);
+/* Boolean mask -> signed exact Euclidean distance texture in pixels (ABI 12; replaces the two scipy
+ * distance_transform_edt calls of `text` / `image`, reference sdf/text.py:77-87).  h_mask: rows x cols bytes, C order,
+ * non-zero = True; h_out: rows x cols float64.  With D(p) the smallest (d row)^2 + (d col)^2 to a pixel of the OTHER class
+ * (an integer), h_out[p] = -sqrt((double)D(p)) where the mask is True and +sqrt((double)D(p)) elsewhere, the square root
+ * correctly rounded.  Synchronous.  Refused on the host before anything is uploaded or launched,
+ * with return value 2: a NULL pointer, rows or cols below 1, rows^2 + cols^2 >= 2^31 (the squared distances are 32-bit),
+ * a shorter side above 16384 pixels, a mask that needs more device memory than is free (13 bytes per pixel), and a mask
+ * whose pixels are all of one class.  Other failures return 1.  Device memory is allocated for the call and freed before
+ * it returns. */
+int sdf_distance_texture_host(sdf_ctx *ctx, const uint8_t *h_mask, int64_t rows, int64_t cols, double *h_out);
 
 /* The batch loop of `generate` (reference sdf/core.py:114-141) around a field evaluated by a HOST callback:
  * `field(user, points (n x 3 float64, host), n, values (n float64, host))` returns 0, or non-zero to abort.  The

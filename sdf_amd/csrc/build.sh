@@ -27,8 +27,10 @@ $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=1 -DMESH_NAME=sdf_launch_mesh_f64_full
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_plain.o sdf_plain.hip "$@" & pids="$pids $!"
 # (the mesh-to-level-set voxelizer: plain kernels, float64 rounded like NumPy's, see sdf_level_set.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_level_set.o sdf_level_set.hip "$@" & pids="$pids $!"
+# (the exact Euclidean distance transform of `text` / `image`: plain kernels, integer arithmetic and one float64 sqrt, see sdf_edt.hip)
+$HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_edt.o sdf_edt.hip "$@" & pids="$pids $!"
 # (the weld uses hipCUB's radix sort and scan; it has no floating-point arithmetic of its own)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build/sdf_weld.o sdf_weld.hip "$@" & pids="$pids $!"
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
-    build/sdf_bounds.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o
+    build/sdf_bounds.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o

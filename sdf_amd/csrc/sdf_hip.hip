@@ -554,6 +554,7 @@ namespace sdfk {
 int weld_device(hipStream_t stream, const double *pts, long long n, double **d_uniq, long long **d_inv, long long *n_unique);   // sdf_weld.hip
 int level_set_host(hipStream_t st, const double *h_pts, long long np, const int32_t *h_tris, long long nt, double vs, int hw,
                    int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, long long cap, std::string &err);           // sdf_level_set.hip
+int edt_host(hipStream_t st, const uint8_t *h_mask, long long rows, long long cols, double *h_out, std::string &err);   // sdf_edt.hip
 }
 
 static bool tape_needs_full(const uint32_t *code, uint32_t n_words, const double *consts) {
@@ -1054,6 +1055,15 @@ int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t n_pts, cons
     std::string err;
     const int rc = sdfk::level_set_host(c->stream, h_pts, n_pts, h_tris, n_tris, vs, hw, out_ijk0, out_dims, h_out, cap, err);
     if (rc) { fail("sdf_mesh_level_set_host: " + err); return rc; }
+    return 0;
+}
+
+int sdf_distance_texture_host(sdf_ctx *c, const uint8_t *h_mask, int64_t rows, int64_t cols, double *h_out) {
+    if (!c || !h_mask || !h_out) { fail("sdf_distance_texture_host: NULL argument"); return 2; }
+    HIPCHK(set_device(c->device));
+    std::string err;
+    const int rc = sdfk::edt_host(c->stream, h_mask, rows, cols, h_out, err);
+    if (rc) { fail("sdf_distance_texture_host: " + err); return rc; }
     return 0;
 }
 

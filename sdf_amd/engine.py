@@ -92,6 +92,7 @@ ABI = {
                                                _f32p, _c_i64, ctypes.POINTER(_c_i64)]),
     'sdf_mesh_level_set_host': (ctypes.c_int, [_vp, _f64p, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_double,
                                                ctypes.c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _f32p, _c_i64]),
+    'sdf_distance_texture_host': (ctypes.c_int, [_vp, _u8p, _c_i64, _c_i64, _f64p]),
     'sdf_generate': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int,
                                     ctypes.POINTER(_vp)]),
@@ -141,7 +142,7 @@ ABI = {
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 def build_info():
@@ -681,6 +682,25 @@ class Engine:
             if n <= cap:
                 return np.array(list(ijk0), dtype=np.int64), out[:n].reshape(tuple(dims))
             cap = n
+
+    def distance_texture(self, mask):
+        """the signed exact Euclidean distance texture of a 2-D boolean mask, in pixels (sdf_distance_texture_host; what two
+        scipy distance_transform_edt calls give the reference's `text` / `image`): float64 of the
+        mask's shape, -sqrt(D) where the mask is True and +sqrt(D) elsewhere, D the integer squared distance to the
+        nearest pixel of the other class.  Raises ValueError, before any device work, for a mask that is not 2-D, is
+        empty, is too large or whose pixels are all of one class."""
+        a = np.asarray(mask)
+        if a.ndim != 2:
+            raise ValueError('the mask must be 2-D, got shape %s' % (a.shape,))
+        if a.size == 0:
+            raise ValueError('empty mask: shape %s' % (a.shape,))
+        a = np.ascontiguousarray(a != 0, dtype=np.uint8)
+        out = np.empty(a.shape, np.float64)
+        rc = self.lib.sdf_distance_texture_host(self.ctx, _dp(a, _u8p), a.shape[0], a.shape[1], _dp(out, _f64p))
+        if rc == 2:
+            raise ValueError(self.lib.sdf_last_error().decode())
+        _check(self.lib, rc)
+        return out
 
     def generate(self, sdf, X, Y, Z, batch_size=32, sparse=True, shard=(0, 1), out_ptr=None, out_cap=0, wait=True, records=False):
         """mesh the grid X x Y x Z.  records=True (one device, the whole work list, no output buffer): for a

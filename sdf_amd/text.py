@@ -7,6 +7,12 @@ so `.extrude(...)` etc. work as usual.
 
 The host preprocessing needs Pillow and scipy (the reference needs them too); they are imported
 lazily so that the rest of the package works without them.
+
+`edt='device'` (per call, or this module's `EDT = 'device'` for every call that does not say --
+`importlib.import_module('sdf_amd.text').EDT = 'device'`: the package attribute `sdf_amd.text` is
+the function, as in the reference) makes the distance texture on the device instead
+(csrc/sdf_edt.hip): the same bits, no scipy -- `text()` then needs only
+Pillow.  The default, 'host', is the reference's code.
 """
 import numpy as np
 
@@ -14,6 +20,7 @@ from . import d2
 from .ir import Node, unwrap
 
 PIXELS = 2 ** 22
+EDT = 'host'        # where `distance_texture` runs when a call does not say: 'host' (scipy) or 'device' (csrc/sdf_edt.hip)
 
 
 def _as_pil(source):
@@ -63,26 +70,39 @@ MARGIN = 0.2        # of the glyph box, on every side (reference sdf/text.py:48)
 
 
 @d2.sdf2
-def text(font_name, text, width=None, height=None, pixels=PIXELS, points=512):
+def text(font_name, text, width=None, height=None, pixels=PIXELS, points=512, edt=None):
     """reference sdf/text.py:42-63: the string rendered white on black into an 8-bit canvas one pixel larger than its glyph box
-    plus the margin on every side, then the distance texture of that canvas"""
+    plus the margin on every side, then the distance texture of that canvas (`edt`: see `distance_texture`; None = `EDT`)"""
+    canvas, pad = _canvas(font_name, text, points)
+    return _sdf(width, height, pixels, pad[0], pad[1], canvas, edt)
+
+
+def _canvas(font_name, text, points):
+    """(canvas, (px, py)): the rendered string and the margin around its glyph box, in pixels"""
     from PIL import Image, ImageDraw
     font, left, top, cols, rows = _glyph_box(font_name, text, points)
     pad = (int(cols * MARGIN), int(rows * MARGIN))
     canvas = Image.new('L', (cols + 1 + 2 * pad[0], rows + 1 + 2 * pad[1]))
     ImageDraw.Draw(canvas).text((pad[0] - left, pad[1] - top), text, font=font, fill=255)
-    return _sdf(width, height, pixels, pad[0], pad[1], canvas)
+    return canvas, pad
 
 
 @d2.sdf2
-def image(thing, width=None, height=None, pixels=PIXELS):
-    """reference sdf/text.py:65-68: any picture, as 8-bit grey, without padding"""
-    return _sdf(width, height, pixels, 0, 0, _as_pil(thing).convert('L'))
+def image(thing, width=None, height=None, pixels=PIXELS, edt=None):
+    """reference sdf/text.py:65-68: any picture, as 8-bit grey, without padding (`edt`: see `distance_texture`; None = `EDT`)"""
+    return _sdf(width, height, pixels, 0, 0, _as_pil(thing).convert('L'), edt)
 
 
-def distance_texture(mask):
+def distance_texture(mask, edt='host'):
     """signed distance (pixels) of a boolean mask: negative inside, positive outside
-    (reference sdf/text.py:81-87)"""
+    (reference sdf/text.py:81-87).  edt='host': scipy's exact Euclidean distance transform, as in the reference;
+    edt='device': the same values, bit for bit, from the device (`Engine.distance_texture`, csrc/sdf_edt.hip; no scipy),
+    which refuses -- ValueError -- a mask whose pixels are all of one class or that is too large"""
+    if edt == 'device':
+        from . import engine
+        return engine.get_engine().distance_texture(mask)
+    if edt != 'host':
+        raise ValueError("edt must be 'host' or 'device', got %r" % (edt,))
     import scipy.ndimage as nd
     a = np.asarray(mask, dtype=bool)
     inside = -nd.distance_transform_edt(a)
@@ -93,9 +113,16 @@ def distance_texture(mask):
     return texture
 
 
-def _sdf(width, height, pixels, px, py, im):
+def _sdf(width, height, pixels, px, py, im, edt=None):
     """reference sdf/text.py:70-136 up to the closure; the closure itself (`f`, :116-134, with
     `_bilinear_interpolate`, :138-153) is the `texture2d` leaf evaluated on the device"""
+    mask, px, py = _mask(pixels, px, py, im)
+    texture = distance_texture(mask, EDT if edt is None else edt)
+    return _texture_node(texture, width, height, px, py)
+
+
+def _mask(pixels, px, py, im):
+    """(mask, px, py): the picture resized to at most `pixels` pixels and thresholded, with the padding scaled along"""
     tw, th = im.size
     factor = (pixels / (tw * th)) ** 0.5
     if factor < 1:
@@ -103,8 +130,7 @@ def _sdf(width, height, pixels, px, py, im):
         px, py = int(round(px * factor)), int(round(py * factor))
         im = im.resize((tw, th))
     im = im.convert('1')
-    texture = distance_texture(np.array(im))
-    return _texture_node(texture, width, height, px, py)
+    return np.array(im), px, py
 
 
 def _texture_node(texture, width=None, height=None, px=0, py=0):
