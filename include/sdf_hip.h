@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 12
+#define SDF_ABI_VERSION 13
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -166,6 +166,23 @@ int sdf_mesh_level_set_host(sdf_ctx *ctx, const double *h_points, int64_t n_poin
  * whose pixels are all of one class.  Other failures return 1.  Device memory is allocated for the call and freed before
  * it returns. */
 int sdf_distance_texture_host(sdf_ctx *ctx, const uint8_t *h_mask, int64_t rows, int64_t cols, double *h_out);
+/* Sphere-traced render buffers of a model (ABI 13; DESIGN.md section 4e, defined by tests/render_ref.py and reproduced bit for
+ * bit).  frame18 = o0, ou, ov, c, du, dv (3 doubles each): pixel (row j, column i) has the origin (o0 + i ou) + j ov and the
+ * direction ((c + i du) + j dv) normalised -- a perspective camera has ou = ov = 0, an orthographic one du = dv = 0.
+ * params5 = t_near, t_far, hit_eps, step_scale, normal_eps.  A ray marches t += f * step_scale from t_near until f < hit_eps
+ * (a hit), t > t_far, f is NaN (misses) or max_steps evaluations are spent (a miss); a hit that stepped inside the surface is
+ * bisected back `refine` times; the normal is the normalised central difference of f at the hit, step normal_eps.  Outputs,
+ * row-major height x width: h_depth float64 (the hit's ray parameter, +inf for a miss), h_normal 3 x float64 (0 for a miss),
+ * h_steps int32 (evaluations of the march), h_status uint8 (1 hit, 0 miss).  Float64 only.  Synchronous, on the context's
+ * stream; one device allocation (37 bytes per pixel), freed before it returns; nothing is kept in the context.  Refused on the
+ * host before anything is allocated or launched, with return value 2: a NULL pointer, width or height below 1, more than 2^26
+ * pixels, max_steps < 1, refine < 0, a non-finite frame or parameter, hit_eps <= 0, normal_eps <= 0, step_scale outside
+ * (0, 1], t_far < t_near, and a tape with user closures (sdf_tape_extern_count > 0: every step would need a host round trip).
+ * Other failures return 1. */
+int sdf_render_host(sdf_tape *tape, const double *frame18, int width, int height, const double *params5, int max_steps, int refine,
+                    double *h_depth, double *h_normal, int32_t *h_steps, uint8_t *h_status);
+/* the kernel of this thread's last successful sdf_render_host alone, milliseconds by HIP events (tools/render_time.py) */
+double sdf_render_last_kernel_ms(void);
 
 /* The batch loop of `generate` (reference sdf/core.py:114-141) around a field evaluated by a HOST callback:
  * `field(user, points (n x 3 float64, host), n, values (n float64, host))` returns 0, or non-zero to abort.  The

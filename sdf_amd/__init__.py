@@ -36,3 +36,5 @@ from .core import (
 from .stl import (
     write_binary_stl,
 )
+
+from .render import render   # (not in the reference: sphere-traced previews)

@@ -21,6 +21,8 @@ INFO="$($HIPCC --version | grep -m1 -i 'HIP version' | tr -d '"' | sed 's/^ *//'
 pids=""
 $HIPCC $FLAGS "-DSDF_BUILD_INFO=\"$INFO\"" -c -o build/sdf_hip.o sdf_hip.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -c -o build/sdf_bounds.o sdf_bounds.hip "$@" & pids="$pids $!"
+# (the sphere tracer k_render: a tape interpreter whose loops are all wave-uniform, see sdf_render.hip)
+$HIPCC $FLAGS -c -o build/sdf_render.o sdf_render.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=0 -DMESH_NAME=sdf_launch_mesh_f64 -c -o build/mesh_f64.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=1 -DMESH_NAME=sdf_launch_mesh_f64_full -c -o build/mesh_f64_full.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 # (every kernel that is not a tape interpreter: built WITHOUT the structurizer option, see sdf_plain.hip)
@@ -33,4 +35,4 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build/sdf_weld.o sdf_weld.hip "$@" & pids="$pids $!"
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
-    build/sdf_bounds.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o
+    build/sdf_bounds.o build/sdf_render.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o

@@ -1,5 +1,5 @@
 // sdf_hip.hip -- the tape-interpreter kernels (k_eval_*, k_skip, k_prune_list, k_cull) + the C ABI of libsdf_hip.so (gfx950
-// only).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip; every kernel that is not an
+// only).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip, k_render in sdf_render.hip; every kernel that is not an
 // interpreter (k_compact, k_scan_items, k_emit2, k_pack_slab, k_expand, k_mc_*, k_field_*, k_cast_f32, k_stl) in sdf_plain.hip.
 //
 // Kernels (one call of sdf_generate enqueues k_skip -> k_compact [-> k_prune_list] -> k_cull -> k_mesh
@@ -50,6 +50,7 @@
 #include "sdf_expand_host.h"
 #include "sdf_plain.h"
 #include "sdf_bounds.h"
+#include "sdf_render.h"
 
 using namespace sdfk;
 
@@ -1066,6 +1067,23 @@ int sdf_distance_texture_host(sdf_ctx *c, const uint8_t *h_mask, int64_t rows, i
     if (rc) { fail("sdf_distance_texture_host: " + err); return rc; }
     return 0;
 }
+
+static thread_local double g_render_kernel_ms = 0.0;
+
+int sdf_render_host(sdf_tape *t, const double *frame18, int width, int height, const double *params5, int max_steps, int refine,
+                    double *h_depth, double *h_normal, int32_t *h_steps, uint8_t *h_status) {
+    if (!t) { fail("sdf_render_host: NULL argument"); return 2; }
+    if (t->n_extern) { fail("sdf_render_host: the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip"); return 2; }
+    sdf_ctx *c = t->ctx;
+    HIPCHK(set_device(c->device));
+    std::string err;
+    const int rc = sdfk::render_host(c->stream, t->d_code, t->d_c64, t->full, frame18, width, height, params5, max_steps, refine, h_depth,
+                                     h_normal, h_steps, h_status, &g_render_kernel_ms, err);
+    if (rc) { fail("sdf_render_host: " + err); return rc; }
+    return 0;
+}
+
+double sdf_render_last_kernel_ms(void) { return g_render_kernel_ms; }
 
 }  // extern "C"
 

@@ -93,6 +93,9 @@ ABI = {
     'sdf_mesh_level_set_host': (ctypes.c_int, [_vp, _f64p, _c_i64, ctypes.POINTER(ctypes.c_int32), _c_i64, ctypes.c_double,
                                                ctypes.c_int, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _f32p, _c_i64]),
     'sdf_distance_texture_host': (ctypes.c_int, [_vp, _u8p, _c_i64, _c_i64, _f64p]),
+    'sdf_render_host': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _f64p,
+                                       ctypes.POINTER(ctypes.c_int32), _u8p]),
+    'sdf_render_last_kernel_ms': (ctypes.c_double, []),
     'sdf_generate': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, _c_i64, _c_i64, ctypes.c_int,
                                     ctypes.POINTER(_vp)]),
@@ -142,7 +145,7 @@ ABI = {
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def build_info():
@@ -697,6 +700,35 @@ class Engine:
         a = np.ascontiguousarray(a != 0, dtype=np.uint8)
         out = np.empty(a.shape, np.float64)
         rc = self.lib.sdf_distance_texture_host(self.ctx, _dp(a, _u8p), a.shape[0], a.shape[1], _dp(out, _f64p))
+        if rc == 2:
+            raise ValueError(self.lib.sdf_last_error().decode())
+        _check(self.lib, rc)
+        return out
+
+    def render_buffers(self, sdf, frame, width, height, t_near=0.0, t_far=1e9, hit_eps=1e-4, step_scale=1.0, normal_eps=1e-4,
+                       max_steps=256, refine=8):
+        """the sphere-traced buffers of a model (sdf_render_host, csrc/sdf_render.hip): a dict of `depth`
+        (height, width) float64 -- the hit's ray parameter, +inf for a miss --, `normal` (height, width, 3) float64, `steps`
+        (height, width) int32 and `status` (height, width) uint8 (1 hit, 0 miss).  frame: 18 doubles o0, ou, ov, c, du, dv
+        (sdf_amd/render.py `camera` makes one).  Raises ValueError, before any device work, for what the entry point refuses
+        (include/sdf_hip.h), for a model with user closures and for a context in float32 precision."""
+        if self.precision != PRECISION_F64:
+            raise ValueError('render_buffers traces in float64 only; this engine is set to float32 precision')
+        dt = self.tape_for(sdf)
+        if dt.tape.externs:
+            raise ValueError('render_buffers cannot trace a model with user closures: every step of every ray would need a host round trip')
+        frame = np.ascontiguousarray(frame, dtype=np.float64).reshape(-1)
+        if frame.size != 18:
+            raise ValueError('the ray frame has 18 numbers (o0, ou, ov, c, du, dv), got %d' % frame.size)
+        w, h = int(width), int(height)
+        if w < 1 or h < 1 or w * h > 1 << 26:
+            raise ValueError('image of %d x %d: the sides must be positive and the pixels at most 2^26' % (w, h))
+        params = np.array([t_near, t_far, hit_eps, step_scale, normal_eps], dtype=np.float64)
+        out = {'depth': np.empty((h, w), np.float64), 'normal': np.empty((h, w, 3), np.float64), 'steps': np.empty((h, w), np.int32),
+               'status': np.empty((h, w), np.uint8)}
+        rc = self.lib.sdf_render_host(dt.handle, _dp(frame, _f64p), w, h, _dp(params, _f64p), int(max_steps), int(refine),
+                                      _dp(out['depth'], _f64p), _dp(out['normal'], _f64p),
+                                      _dp(out['steps'], ctypes.POINTER(ctypes.c_int32)), _dp(out['status'], _u8p))
         if rc == 2:
             raise ValueError(self.lib.sdf_last_error().decode())
         _check(self.lib, rc)
