@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 13
+#define SDF_ABI_VERSION 14
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -352,6 +352,25 @@ int sdf_mesh_weld(sdf_mesh *mesh, int64_t *n_unique);
  * library generated.  The memory stays the caller's (alive and complete until the handle is destroyed). */
 int sdf_mesh_adopt_soup(sdf_ctx *ctx, const void *d_soup, int64_t n_tris, sdf_mesh **out);
 int sdf_mesh_weld_fetch(sdf_mesh *mesh, double *h_points, int64_t *h_cells);
+/* Vertex normals of the welded mesh from the FIELD (ABI 14; DESIGN.md section 4f, defined by tests/normals_ref.py and reproduced
+ * bit for bit): at every unique vertex p of sdf_mesh_weld, for axis k = 0, 1, 2, g_k = f(p + eps e_k) - f(p - eps e_k) (only
+ * coordinate k changes, by x + eps and x + (-eps)), len = sqrt((g0*g0 + g1*g1) + g2*g2), n = g / len; a vertex whose len is 0 or
+ * NaN is "flat": its normal is (0, 0, 0) and it is counted in *n_flat.  Float64, the interpreter of sdf_eval_points.  The normals
+ * (n_unique x 3 float64) stay on the device with the mesh, until it is destroyed, and are copied to h_normals unless it is NULL; a
+ * second call with the same model and eps reuses them.  The tape is an argument so that adopted soups (sdf_mesh_adopt_soup) are
+ * served.  Refused on the host before anything is allocated or launched, with return value 2: a NULL mesh, tape or n_flat, an eps
+ * that is not finite or not above 0, a tape with user closures (sdf_tape_extern_count > 0), a mesh that is not welded, a tape of
+ * another context.  Other failures return 1. */
+int sdf_mesh_vertex_normals(sdf_mesh *mesh, sdf_tape *tape, double eps, double *h_normals, int64_t *n_flat);
+/* the kernel of this thread's last sdf_mesh_vertex_normals that computed (not one served from the cache) alone, milliseconds by
+ * HIP events (tools/export_time.py) */
+double sdf_mesh_normals_last_kernel_ms(void);
+/* The body of a binary little-endian PLY file of the welded mesh: h_vertices receives n_unique records of float32 x, y, z (12
+ * bytes) or, with_normals = 1, float32 x, y, z, nx, ny, nz (24 bytes; needs a successful sdf_mesh_vertex_normals first);
+ * h_faces receives T records of 13 bytes: uint8 3 and three little-endian int32 vertex indices.  Refused with return value 2: a
+ * NULL argument, a mesh that is not welded, with_normals without normals, 2^31 or more vertices.  One device allocation, freed
+ * before it returns. */
+int sdf_mesh_emit_ply_host(sdf_mesh *mesh, int with_normals, void *h_vertices, void *h_faces);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -28,6 +28,7 @@ from .text import (
 
 from .core import (
     generate,
+    generate_mesh,   # (not in the reference: the indexed mesh with the field's normals)
     save,
     sample_slice,
     show_slice,

@@ -19,6 +19,7 @@ Differences a caller can observe:
   every rank still returns the complete soup in reference order.
 """
 import multiprocessing
+import os
 import time
 
 import numpy as np
@@ -151,13 +152,14 @@ def generate(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, _stl=False, _weld=False):
+        verbose=True, sparse=True, _stl=False, _weld=False, _export=None):
     """reference sdf/core.py:84-150.  `batch_size` up to 512 (the reference takes any: a larger one is refused with a message; up
     to 32 runs the fused kernels, above that the batches go through device memory -- a model with user closures then hands its
     callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512).  (`_stl=True` is what `save` uses for .stl files: the soup
     stays on the device and the 50-byte STL records come back instead of the points; `_weld=True` is
     what `save` uses for every other format: the soup is welded on the device and the indexed mesh
-    (unique points, cells) comes back.)"""
+    (unique points, cells) comes back; `_export` is what `generate_mesh` and the native PLY / OBJ writers of `save` use: see
+    `_export_mesh`.)"""
 
     from . import engine, dist
     start = time.time()
@@ -182,7 +184,13 @@ def generate(
         num_samples = overlapped(len(X)) * overlapped(len(Y)) * overlapped(len(Z))
         print('%d samples in %d batches with %d workers' % (num_samples, num_batches, workers))
 
-    records = welded = None
+    records = welded = exported = None
+    if _export is not None:
+        _weld = True
+        if _export.get('normals') and _export.get('eps') is None:
+            # (the preview's value, render.render_buffers: a file and a preview of one model show the same normals)
+            lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
+            _export = dict(_export, eps=1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2))
     if dist.world_size() > 1:
         soup, stats = dist.generate_sharded_device(eng, tape, X, Y, Z, batch_size, sparse)
         if (_stl or _weld) and getattr(soup, 'is_cuda', False) and hasattr(eng, 'adopt_soup'):
@@ -193,6 +201,8 @@ def generate(
             try:
                 if _stl:
                     records = mesh.stl_records()
+                elif _export is not None:
+                    exported = _export_mesh(mesh, tape, _export)
                 else:
                     welded = mesh.weld()
                 points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
@@ -210,6 +220,9 @@ def generate(
             if _stl:
                 records = mesh.stl_records()
                 points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
+            elif _export is not None:
+                exported = _export_mesh(mesh, tape, _export)
+                points = np.empty((3 * mesh.n_triangles, 0))
             elif _weld:
                 welded = mesh.weld()
                 points = np.empty((3 * mesh.n_triangles, 0))
@@ -228,18 +241,83 @@ def generate(
     if _stl:
         return records if records is not None else stl.stl_records(points).view(np.uint8).reshape(-1)
     if _weld:
-        if welded is None:      # (multi-process: the gathered soup is welded like the reference does it)
+        if welded is None and exported is None:      # (multi-process: the gathered soup is welded like the reference does it)
             pts, cells = np.unique(points, axis=0, return_inverse=True)
             welded = (pts, np.asarray(cells).reshape((-1, 3)))
-        return welded
+            if _export is not None:
+                exported = _export_host(eng, tape, welded, _export)
+        return welded if _export is None else exported
     return points
 
 
 generate.last_stats = None
 
 
-def save(path, *args, **kwargs):
-    """reference sdf/core.py:152-158"""
+def _export_mesh(mesh, tape, want):
+    """what the indexed export takes from a device mesh: welds it, takes the field's normals at the welded vertices when
+    want['normals'] (step want['eps']: k_vertex_normals) and returns a dict of `n_vertices`, `n_faces`, `normals` ((U, 3) float64
+    or None), `n_flat` and -- want['ply']: the device-packed PLY body `ply` = (vertex_bytes, face_bytes); otherwise `points`,
+    `cells` of the weld"""
+    out = {'normals': None, 'n_flat': 0}
+    if want.get('normals'):
+        out['normals'], out['n_flat'] = mesh.vertex_normals(tape, want['eps'])
+    if want.get('ply'):
+        closures = out['normals'] is not None and bool(tape.tape.externs)      # (their normals were taken on the host)
+        if closures:
+            from . import meshfile
+            out['points'], out['cells'] = mesh.weld()
+            out['ply'] = meshfile.ply_records(out['points'], out['cells'], out['normals'])
+        else:
+            out['ply'] = mesh.ply_records(normals=bool(want.get('normals')))
+        out['n_vertices'], out['n_faces'] = len(out['ply'][0]) // (24 if want.get('normals') else 12), mesh.n_triangles
+    else:
+        out['points'], out['cells'] = mesh.weld()
+        out['n_vertices'], out['n_faces'] = len(out['points']), len(out['cells'])
+    return out
+
+
+def _export_host(eng, tape, welded, want):
+    """the same for a soup that was gathered and welded on the host (multi-process runs): the normals come from the
+    definition over eval_points, the PLY body from the host packer"""
+    from . import meshfile
+    pts, cells = welded
+    out = {'points': pts, 'cells': cells, 'normals': None, 'n_flat': 0, 'n_vertices': len(pts), 'n_faces': len(cells)}
+    if want.get('normals'):
+        out['normals'], out['n_flat'] = meshfile.vertex_normals(lambda P: eng.eval_points(tape, P), pts, want['eps'])
+    if want.get('ply'):
+        out['ply'] = meshfile.ply_records(pts, cells, out['normals'])
+    return out
+
+
+def generate_mesh(sdf, normals=False, normal_eps=None, **generate_kwargs):
+    """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
+    welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
+    difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
+    value).  The normals point outward for this library's winding; a vertex where the field has no gradient gets (0, 0, 0)
+    (`generate_mesh.last_flat` counts them).  Not in the reference."""
+    got = generate(sdf, _export={'normals': bool(normals), 'eps': normal_eps}, **generate_kwargs)
+    generate_mesh.last_flat = got['n_flat']
+    return got['points'], got['cells'], got['normals']
+
+
+generate_mesh.last_flat = 0
+
+
+def save(path, *args, normals=False, normal_eps=None, writer=None, **kwargs):
+    """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
+    normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
+    'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native."""
+    from . import meshfile
+    path = os.fspath(path)
+    how = meshfile.choose_writer(path, writer, normals)
+    if how == 'native':
+        ply = path.lower().endswith('.ply')
+        got = generate(*args, _export={'normals': bool(normals), 'eps': normal_eps, 'ply': ply}, **kwargs)
+        if ply:
+            meshfile.write_ply(path, got['ply'][0], got['ply'][1], got['n_vertices'], got['n_faces'], bool(normals))
+        else:
+            meshfile.write_obj(path, got['points'], got['cells'], got['normals'])
+        return
     if path.lower().endswith('.stl'):
         # normals and the 50-byte records are made on the device (k_stl); byte-identical to
         # stl.write_binary_stl(path, points) -- tests/test_gpu.py

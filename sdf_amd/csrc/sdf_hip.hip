@@ -29,6 +29,7 @@
 //   k_mc_rows / k_mc_emit         marching cubes of a caller-supplied volume (`_marching_cubes`);
 //   k_cast_f32 / k_field_*        the same for the batches of a host-evaluated field (user closures)
 //   k_stl                         50-byte STL records (reference sdf/stl.py:4-24)
+//   k_vertex_normals              the field's gradient at the welded vertices (sdf_normals.hip); k_ply_vertices / k_ply_faces: binary PLY records
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,6 +52,7 @@
 #include "sdf_plain.h"
 #include "sdf_bounds.h"
 #include "sdf_render.h"
+#include "sdf_normals.h"
 
 using namespace sdfk;
 
@@ -542,6 +544,13 @@ struct sdf_mesh {
     double *weld_pts = nullptr;    // sdf_mesh_weld: unique rows / row -> unique row (hipMalloc'ed by sdf_weld.hip)
     long long *weld_inv = nullptr;
     long long weld_n = -1;
+    // sdf_mesh_vertex_normals: weld_n x 3 float64 + the flat counter in one block of its own (dev_malloc, freed with the mesh); the
+    // model (content hash) and eps they were taken with: a second call with the same ones reuses them
+    double *nrm = nullptr;
+    bool nrm_valid = false;
+    unsigned long long nrm_model = 0;
+    double nrm_eps = 0.0;
+    long long nrm_flat = 0;
     // sdf_generate_records: the triangles were written as 16-byte records into a slab of the library's (sdf_slab.h); the float64 soup
     // is made on the host threads (sdf_mesh_emit_host_workers) or, for the readers that want it on the device, by k_expand on demand
     bool records = false;
@@ -2345,6 +2354,83 @@ int sdf_mesh_weld_fetch(sdf_mesh *m, double *h_points, int64_t *h_cells) {
     return 0;
 }
 
+// ---- the indexed export: field normals at the welded vertices, binary PLY records ----
+static thread_local double g_normals_kernel_ms = 0.0;
+
+int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_normals, int64_t *n_flat) {
+    if (!m || !t || !n_flat) { fail("sdf_mesh_vertex_normals: NULL argument"); return 2; }
+    if (!(std::isfinite(eps) && eps > 0.0)) { fail("sdf_mesh_vertex_normals: eps must be finite and positive"); return 2; }
+    if (t->n_extern) { fail("sdf_mesh_vertex_normals: the tape reads user closures (L_EXTERN): take the normals over sdf_eval_points_extern_host"); return 2; }
+    if (m->weld_n < 0) { fail("sdf_mesh_vertex_normals: call sdf_mesh_weld first"); return 2; }
+    if (t->ctx != m->ctx) { fail("sdf_mesh_vertex_normals: the tape and the mesh belong to different contexts"); return 2; }
+    sdf_ctx *c = m->ctx;
+    const long long nu = m->weld_n;
+    *n_flat = 0;
+    if (nu == 0) { m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps; m->nrm_flat = 0; return 0; }
+    HIPCHK(set_device(c->device));
+    if (!(m->nrm_valid && m->nrm_model == t->content_hash && m->nrm_eps == eps)) {
+        m->nrm_valid = false;
+        if (!m->nrm) {
+            const hipError_t e = dev_malloc((void **)&m->nrm, (size_t)nu * 24 + 8);
+            if (e != hipSuccess) { m->nrm = nullptr; return fail(std::string("sdf_mesh_vertex_normals: hipMalloc(") + std::to_string((size_t)nu * 24 + 8) + "): " + hipGetErrorString(e)); }
+        }
+        unsigned long long *d_flat = reinterpret_cast<unsigned long long *>(m->nrm + 3 * nu);
+        unsigned long long flat = 0;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipMemsetAsync(d_flat, 0, 8, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
+        if (e == hipSuccess) e = (hipError_t)sdfk::launch_vertex_normals(c->stream, t->d_code, t->d_c64, t->full, m->weld_pts, nu, eps, m->nrm, d_flat);
+        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&flat, d_flat, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = stream_wait(c->stream);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        if (e != hipSuccess) (void)stream_wait(c->stream);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e != hipSuccess) return fail(std::string("sdf_mesh_vertex_normals: ") + hipGetErrorString(e));
+        g_normals_kernel_ms = (double)ms;
+        m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps; m->nrm_flat = (long long)flat;
+    }
+    *n_flat = (int64_t)m->nrm_flat;
+    if (h_normals) return copy_to_host(c, h_normals, m->nrm, (size_t)nu * 24);
+    return 0;
+}
+
+double sdf_mesh_normals_last_kernel_ms(void) { return g_normals_kernel_ms; }
+
+int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
+    if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }
+    if (m->weld_n < 0) { fail("sdf_mesh_emit_ply_host: call sdf_mesh_weld first"); return 2; }
+    if (with_normals && !m->nrm_valid) { fail("sdf_mesh_emit_ply_host: with_normals needs a successful sdf_mesh_vertex_normals first"); return 2; }
+    const long long nu = m->weld_n, nt = (long long)m->st.n_triangles;
+    if (nu >= (1ll << 31)) { fail("sdf_mesh_emit_ply_host: 2^31 or more vertices: the face records hold 32-bit indices"); return 2; }
+    if (nu == 0 || nt == 0) return 0;
+    sdf_ctx *c = m->ctx;
+    HIPCHK(set_device(c->device));
+    const int width = with_normals ? 6 : 3;
+    const size_t vbytes = (size_t)nu * 4 * (size_t)width, fbytes = (size_t)nt * 13, foff = (vbytes + 255) & ~(size_t)255;
+    char *base = nullptr;
+    hipError_t e = dev_malloc((void **)&base, foff + ((fbytes + 255) & ~(size_t)255));
+    if (e != hipSuccess) return fail(std::string("sdf_mesh_emit_ply_host: hipMalloc(") + std::to_string(foff + fbytes) + "): " + hipGetErrorString(e));
+    const long long nfl = nu * width;
+    launch_k_ply_vertices(dim3((unsigned)((nfl + 255) / 256)), dim3(256), c->stream, m->weld_pts, with_normals ? m->nrm : nullptr, nfl, width, (float *)base);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+        launch_k_ply_faces(dim3((unsigned)((nt + 255) / 256)), dim3(256), c->stream, m->weld_inv, nt, (unsigned char *)(base + foff));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_vertices, base, vbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_faces, base + foff, fbytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t ew = stream_wait(c->stream);
+    if (e == hipSuccess) e = ew;
+    (void)hipFree(base);
+    if (e != hipSuccess) return fail(std::string("sdf_mesh_emit_ply_host: ") + hipGetErrorString(e));
+    return 0;
+}
+
 // ---- pinned host memory for results ----
 // A device-to-host copy into fresh pageable memory runs at ~10 GB/s (page faults + the runtime's staging);
 // into pinned memory it runs at the link rate.  Pinning is expensive (tens of ms for 200 MB), so the
@@ -2451,7 +2537,7 @@ int sdf_mesh_destroy(sdf_mesh *m) {
     }
     if (m->counters.p) { c->counter_pool.push_back(m->counters); m->counters.p = nullptr; m->counters.bytes = 0; }
     for (DevBuf *b : {&m->axes, &m->kinds, &m->worklist, &m->status, &m->prune, &m->tapes, &m->cull, &m->order, &m->desc, &m->cellrecs, &m->trilist, &m->blockidx, &m->slab}) b->release();
-    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv);
+    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv); (void)hipFree(m->nrm);
     delete m;
     return 0;
 }

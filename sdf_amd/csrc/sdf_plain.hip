@@ -337,6 +337,45 @@ __global__ __launch_bounds__(256) void k_stl(const double *__restrict__ pts, lon
     o[24] = 0;
 }
 
+// ---- binary PLY records of the welded mesh (sdf_mesh_emit_ply_host; tests/normals_ref.py `ply_records`) ----
+// vertex record: float32 x, y, z (+ float32 nx, ny, nz): `width` = 3 or 6 floats.  One float per thread: the stores are consecutive words.
+__global__ __launch_bounds__(256) void k_ply_vertices(const double *__restrict__ pts, const double *__restrict__ nrm, long long n_floats, int width,
+                                                      float *__restrict__ out) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_floats) return;
+    const long long v = e / width;
+    const int c = (int)(e - v * width);
+    out[e] = (float)(c < 3 ? pts[3 * v + c] : nrm[3 * v + (c - 3)]);
+}
+
+// face record: uint8 3, three little-endian int32: 13 bytes, not word-aligned.  A workgroup assembles its 256 records (3328 bytes = 832
+// words, so every workgroup starts on a word) as bytes in LDS and stores aligned words; what is left of the last record of the file
+// (1 to 3 bytes) is stored as bytes.
+__global__ __launch_bounds__(256) void k_ply_faces(const long long *__restrict__ inv, long long ntri, unsigned char *__restrict__ out) {
+    __shared__ unsigned int rec[832];
+    unsigned char *rb = reinterpret_cast<unsigned char *>(rec);
+    const long long t0 = (long long)blockIdx.x * 256;
+    const long long t = t0 + threadIdx.x;
+    if (t < ntri) {
+        unsigned char *r = rb + 13 * (int)threadIdx.x;
+        r[0] = 3;
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const unsigned u = (unsigned)(int)inv[3 * t + q];
+            r[1 + 4 * q] = (unsigned char)(u & 255u); r[2 + 4 * q] = (unsigned char)((u >> 8) & 255u);
+            r[3 + 4 * q] = (unsigned char)((u >> 16) & 255u); r[4 + 4 * q] = (unsigned char)(u >> 24);
+        }
+    }
+    __syncthreads();
+    const long long left = ntri - t0;
+    const int nbytes = 13 * (int)(left < 256 ? left : 256);
+    unsigned char *dst = out + t0 * 13;                               // (t0 * 13 = blockIdx.x * 3328: a multiple of 4)
+    unsigned int *dst32 = reinterpret_cast<unsigned int *>(dst);
+    for (int w = threadIdx.x; w < (nbytes >> 2); w += 256) dst32[w] = rec[w];
+    const int tail = nbytes & 3;
+    if ((int)threadIdx.x < tail) dst[(nbytes & ~3) + threadIdx.x] = rb[(nbytes & ~3) + threadIdx.x];
+}
+
 // ---- the multi-GPU exchange unit (layout: sdf_slab.h) ----
 // header + the shard's look-back words (inclusive triangle prefix per work item) into the slab, behind k_mesh
 __global__ __launch_bounds__(256) void k_pack_slab(const MeshCounters *__restrict__ ctr, const unsigned long long *__restrict__ status,
@@ -506,4 +545,10 @@ void launch_k_emit2(dim3 grid, dim3 block, hipStream_t stream, const MeshArgs &a
 }
 void launch_k_stl(dim3 grid, dim3 block, hipStream_t stream, const double *pts, long long ntri, unsigned short *out) {
     hipLaunchKernelGGL(k_stl, grid, block, 0, stream, pts, ntri, out);
+}
+void launch_k_ply_vertices(dim3 grid, dim3 block, hipStream_t stream, const double *pts, const double *nrm, long long n_floats, int width, float *out) {
+    hipLaunchKernelGGL(k_ply_vertices, grid, block, 0, stream, pts, nrm, n_floats, width, out);
+}
+void launch_k_ply_faces(dim3 grid, dim3 block, hipStream_t stream, const long long *inv, long long ntri, unsigned char *out) {
+    hipLaunchKernelGGL(k_ply_faces, grid, block, 0, stream, inv, ntri, out);
 }

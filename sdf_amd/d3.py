@@ -68,6 +68,10 @@ class SDF3(SDFBase):
         from . import core
         return core.save(path, self, *args, **kwargs)
 
+    def generate_mesh(self, *args, **kwargs):
+        from . import core
+        return core.generate_mesh(self, *args, **kwargs)
+
     def render(self, path=None, **kwargs):
         import importlib
         return importlib.import_module(__package__ + '.render').render(self, path, **kwargs)

@@ -139,13 +139,16 @@ ABI = {
     'sdf_mesh_adopt_soup': (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.POINTER(_vp)]),
     'sdf_mesh_weld': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int64)]),
     'sdf_mesh_weld_fetch': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(ctypes.c_int64)]),
+    'sdf_mesh_vertex_normals': (ctypes.c_int, [_vp, _vp, ctypes.c_double, _f64p, ctypes.POINTER(ctypes.c_int64)]),
+    'sdf_mesh_normals_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_emit_ply_host': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def build_info():
@@ -387,6 +390,54 @@ class Mesh:
             _check(self.engine.lib, self.engine.lib.sdf_mesh_weld_fetch(self.handle, _dp(pts, _f64p),
                                                                        _dp(cells, ctypes.POINTER(ctypes.c_int64))))
         return pts, cells
+
+    def _welded(self):
+        """number of unique vertices; welds (on the device) if that has not happened yet"""
+        nu = ctypes.c_int64(0)
+        _check(self.engine.lib, self.engine.lib.sdf_mesh_weld(self.handle, ctypes.byref(nu)))
+        return int(nu.value)
+
+    def vertex_normals(self, sdf_or_tape, eps):
+        """(normals (U, 3) float64, n_flat): the normalised central difference of the FIELD, step eps, at the U welded vertices
+        (sdf_mesh_vertex_normals, csrc/sdf_normals.hip; defined by tests/normals_ref.py and reproduced bit
+        for bit).  A vertex where the difference is zero or NaN is flat: its normal is (0, 0, 0) and it is counted in n_flat.
+        The normals also stay on the device with the mesh, for `ply_records(normals=True)`.  A model with user closures takes
+        the same definition over `Engine.eval_points` on the host (and keeps nothing on the device).  Raises ValueError,
+        before any device work, for an eps that is not finite and positive and for an engine in float32 precision."""
+        eng = self.engine
+        eps = float(eps)
+        if not (np.isfinite(eps) and eps > 0):
+            raise ValueError('eps must be finite and positive, got %r' % eps)
+        if eng.precision != PRECISION_F64:
+            raise ValueError('vertex_normals takes the gradient in float64 only; this engine is set to float32 precision')
+        dt = eng.tape_for(sdf_or_tape)
+        if dt.tape.externs:
+            from . import meshfile
+            return meshfile.vertex_normals(lambda P: eng.eval_points(dt, P), self.weld()[0], eps)
+        nu = self._welded()
+        out = pinned_empty(eng.lib, (nu, 3), np.float64)
+        flat = ctypes.c_int64(0)
+        rc = eng.lib.sdf_mesh_vertex_normals(self.handle, dt.handle, eps, _dp(out, _f64p), ctypes.byref(flat))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        return out, int(flat.value)
+
+    def ply_records(self, normals=False):
+        """(vertex_bytes, face_bytes) uint8: the body of a binary little-endian PLY file of the welded mesh, packed on the device
+        (sdf_mesh_emit_ply_host): U records of float32 x, y, z (12 bytes; with normals=True + float32 nx, ny, nz: 24 bytes --
+        needs `vertex_normals` first) and T records of uint8 3 + 3 x int32 (13 bytes)"""
+        eng = self.engine
+        nu, t = self._welded(), self.n_triangles
+        vb = pinned_empty(eng.lib, (nu * (24 if normals else 12),), np.uint8)
+        fb = pinned_empty(eng.lib, (13 * t,), np.uint8)
+        if nu == 0 or t == 0:
+            return vb, fb
+        rc = eng.lib.sdf_mesh_emit_ply_host(self.handle, 1 if normals else 0, vb.ctypes.data_as(_vp), fb.ctypes.data_as(_vp))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        return vb, fb
 
     def stl_records(self):
         """T x 50-byte binary STL records (normals computed on the device)"""
