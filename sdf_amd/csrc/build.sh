@@ -1,5 +1,6 @@
 #!/bin/sh
 # Builds libsdf_hip.so for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
+# One object per translation unit of this directory; the comments below say which unit gets which flags and why.
 # -ffp-contract=off: the interpreter must round like NumPy (separate multiply and add);
 # fused multiply-adds are written explicitly where the reference goes through BLAS.
 # The fused sample+march kernel is instantiated per family (float64, with / without the trigonometric ops) in its own
@@ -29,6 +30,11 @@ $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=0 -DMESH_NAME=sdf_launch_mesh_f64 -c -
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=1 -DMESH_NAME=sdf_launch_mesh_f64_full -c -o build/mesh_f64_full.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 # (every kernel that is not a tape interpreter: built WITHOUT the structurizer option, see sdf_plain.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_plain.o sdf_plain.hip "$@" & pids="$pids $!"
+# (host code only -- the runtime every unit shares, the readers of a finished mesh, the multi-GPU step: they launch through the
+# launchers of sdf_plain / sdf_normals / sdf_weld, so they take the plain flags)
+for u in sdf_runtime sdf_mesh_out sdf_comm; do
+    $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/$u.o $u.hip "$@" & pids="$pids $!"
+done
 # (the mesh-to-level-set voxelizer: plain kernels, float64 rounded like NumPy's, see sdf_level_set.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_level_set.o sdf_level_set.hip "$@" & pids="$pids $!"
 # (the exact Euclidean distance transform of `text` / `image`: plain kernels, integer arithmetic and one float64 sqrt, see sdf_edt.hip)
@@ -37,4 +43,5 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build/sdf_weld.o sdf_weld.hip "$@" & pids="$pids $!"
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
-    build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o
+    build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o \
+    build/sdf_runtime.o build/sdf_mesh_out.o build/sdf_comm.o

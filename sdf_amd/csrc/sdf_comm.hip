@@ -1,5 +1,5 @@
-// sdf_comm.inc -- the multi-GPU exchange step inside the library (textually included at the end of sdf_hip.hip: it
-// drives generate_impl / k_expand directly).
+// sdf_comm.hip -- the multi-GPU exchange step inside the library: it drives generate_impl and enqueue_skip (sdf_hip.hip, declared in
+// sdf_internal.h) and k_expand's launcher directly.  No kernels of its own.
 //
 // One process per GPU.  A rank meshes its contiguous share of the surviving-batch work list into a SLAB (header with
 // the counts | per-batch triangle prefix and transform | triangles as 16-byte records in batch-local coordinates, sdf_slab.h
@@ -17,8 +17,17 @@
 // parallel, so the collective's time is one slab over one link; the slabs carry 16 B per triangle (sdf_slab.h; 36 B until r04n)
 // instead of the soup's 72 B for that reason.
 #include <dlfcn.h>
-#include <map>
 #include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+#include "sdf_internal.h"
+
+using namespace sdfk;
 
 namespace {
 

@@ -24,6 +24,8 @@
 #include <algorithm>
 #include <string>
 
+#include "sdf_internal.h"
+
 namespace sdfk {
 
 // "no pixel of the other class on this line": EDT_NONE^2 = 2147488281 >= 2^31 > every real D, and EDT_NONE^2 + k^2 (k < 16384)
@@ -106,24 +108,23 @@ __global__ __launch_bounds__(256) void k_edt_min(const int *__restrict__ g, EdtS
     }
 }
 
-static size_t edt_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace sdfk
 
-#define EDTCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); rc = 1; goto done; } } while (0)
+using namespace sdfk;
 
-// 0: done, 1: HIP error, 2: refused (nothing uploaded, nothing launched); `err` says why
-int edt_host(hipStream_t st, const uint8_t *h_mask, long long rows, long long cols, double *h_out, std::string &err) {
-    if (!h_mask || !h_out) { err = "NULL mask or output"; return 2; }
-    if (rows < 1 || cols < 1) { err = "empty mask: " + std::to_string(rows) + " x " + std::to_string(cols); return 2; }
+// 0: done, 1: HIP error, 2: refused (nothing uploaded, nothing launched); sdf_last_error says why
+extern "C" int sdf_distance_texture_host(sdf_ctx *c, const uint8_t *h_mask, int64_t rows, int64_t cols, double *h_out) {
+    auto refuse = [](const std::string &why) { fail("sdf_distance_texture_host: " + why); return 2; };
+    if (!c || !h_mask || !h_out) return refuse("NULL argument");
+    HIPCHK(set_device(c->device));
+    hipStream_t st = c->stream;
+    const std::string shape = std::to_string(rows) + " x " + std::to_string(cols);
+    if (rows < 1 || cols < 1) return refuse("empty mask: " + shape);
     // (either side above 46340 fails the first test by itself, so the squares below cannot overflow)
-    if (rows > 46340 || cols > 46340 || rows * rows + cols * cols >= (1ll << 31)) {
-        err = "mask of " + std::to_string(rows) + " x " + std::to_string(cols) + ": rows^2 + cols^2 must stay below 2^31 (32-bit squared distances)";
-        return 2;
-    }
-    if (std::min(rows, cols) > EDT_MAX_SHORT) {
-        err = "mask of " + std::to_string(rows) + " x " + std::to_string(cols) + ": the shorter side must not exceed " +
-              std::to_string(EDT_MAX_SHORT) + " pixels (one line across it is kept in LDS)";
-        return 2;
-    }
+    if (rows > 46340 || cols > 46340 || rows * rows + cols * cols >= (1ll << 31))
+        return refuse("mask of " + shape + ": rows^2 + cols^2 must stay below 2^31 (32-bit squared distances)");
+    if (std::min(rows, cols) > EDT_MAX_SHORT)
+        return refuse("mask of " + shape + ": the shorter side must not exceed " + std::to_string(EDT_MAX_SHORT) + " pixels (one line across it is kept in LDS)");
     const size_t n = (size_t)rows * (size_t)cols;
     {
         bool any_t = false, any_f = false;
@@ -131,22 +132,19 @@ int edt_host(hipStream_t st, const uint8_t *h_mask, long long rows, long long co
             if (h_mask[p]) any_t = true;
             else any_f = true;
         }
-        if (!(any_t && any_f)) {
-            err = std::string("every pixel of the mask is ") + (any_t ? "True" : "False") + ": the distance to the other class is undefined";
-            return 2;
-        }
+        if (!(any_t && any_f))
+            return refuse(std::string("every pixel of the mask is ") + (any_t ? "True" : "False") + ": the distance to the other class is undefined");
     }
-    const size_t o_g = edt_align256(n), o_out = o_g + edt_align256(n * 4), bytes = o_out + edt_align256(n * 8);
-    size_t free_b = 0, total_b = 0;
-    {
-        const hipError_t e = hipMemGetInfo(&free_b, &total_b);
-        if (e != hipSuccess) { err = std::string("hipMemGetInfo: ") + hipGetErrorString(e); return 1; }
-    }
-    if (bytes > free_b / 10 * 9) {
-        err = "mask of " + std::to_string(rows) + " x " + std::to_string(cols) + " needs " + std::to_string(bytes) +
-              " bytes of device memory, " + std::to_string(free_b) + " are free";
-        return 2;
-    }
+    uint8_t *mask;
+    int *g;
+    double *out;
+    Scratch scratch(st);
+    scratch.part(&mask, n); scratch.part(&g, n); scratch.part(&out, n);
+    size_t free_b = 0;
+    bool fits = false;
+    HIPCHK_FN(mem_fits(scratch.bytes, &fits, &free_b));
+    if (!fits)
+        return refuse("mask of " + shape + " needs " + std::to_string(scratch.bytes) + " bytes of device memory, " + std::to_string(free_b) + " are free");
     EdtShape sh;
     if (rows <= cols) { sh.S = (int)rows; sh.L = (int)cols; sh.stride_s = cols; sh.stride_l = 1; }
     else { sh.S = (int)cols; sh.L = (int)rows; sh.stride_s = 1; sh.stride_l = cols; }
@@ -156,25 +154,12 @@ int edt_host(hipStream_t st, const uint8_t *h_mask, long long rows, long long co
     // several waves per SIMD hide
     while (tl_log2 > 2 && (sh.L >> tl_log2) < 1024) tl_log2--;
     const unsigned tiles = (unsigned)((sh.L + (1 << tl_log2) - 1) >> tl_log2);
-    char *base = nullptr;
-    int rc = 0;
-    uint8_t *mask;
-    int *g;
-    double *out;
-    EDTCHK(hipMalloc((void **)&base, bytes));
-    mask = (uint8_t *)base;
-    g = (int *)(base + o_g);
-    out = (double *)(base + o_out);
-    EDTCHK(hipMemcpyAsync(mask, h_mask, n, hipMemcpyHostToDevice, st));
+    HIPCHK_FN(scratch.alloc());
+    HIPCHK_FN(hipMemcpyAsync(mask, h_mask, n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)sh.S), dim3(256), 0, st, (const uint8_t *)mask, sh, g);
     hipLaunchKernelGGL(k_edt_min, dim3(tiles), dim3(256), ((size_t)sh.S << tl_log2) * sizeof(int), st, (const int *)g, sh, tl_log2, out);
-    EDTCHK(hipGetLastError());
-    EDTCHK(hipMemcpyAsync(h_out, out, n * 8, hipMemcpyDeviceToHost, st));
-    EDTCHK(hipStreamSynchronize(st));
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    if (base) (void)hipFree(base);
-    return rc;
+    HIPCHK_FN(hipGetLastError());
+    HIPCHK_FN(hipMemcpyAsync(h_out, out, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(stream_wait(st));
+    return 0;
 }
-
-}  // namespace sdfk

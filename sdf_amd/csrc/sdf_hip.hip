@@ -1,5 +1,5 @@
-// sdf_hip.hip -- the tape-interpreter kernels (k_eval_*, k_skip, k_prune_list, k_cull) + the C ABI of libsdf_hip.so (gfx950
-// only).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip, k_render in sdf_render.hip; every kernel that is not an
+// sdf_hip.hip -- the tape-interpreter kernels (k_eval_*, k_skip, k_prune_list, k_cull) + the contexts, tapes and generate calls of
+// libsdf_hip.so's C ABI (gfx950 only; the rest of the ABI: sdf_runtime.hip, sdf_mesh_out.hip, sdf_comm.hip and the features' own units).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip, k_render in sdf_render.hip; every kernel that is not an
 // interpreter (k_compact, k_scan_items, k_emit2, k_pack_slab, k_expand, k_mc_*, k_field_*, k_cast_f32, k_stl) in sdf_plain.hip.
 //
 // Kernels (one call of sdf_generate enqueues k_skip -> k_compact [-> k_prune_list] -> k_cull -> k_mesh
@@ -33,26 +33,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/sdf_hip.h"
 #include "mc_table.h"
-#include "sdf_device.h"
 #include "sdf_prune.h"
-#include "sdf_slab.h"
-#include "sdf_expand_host.h"
 #include "sdf_plain.h"
 #include "sdf_bounds.h"
-#include "sdf_render.h"
-#include "sdf_normals.h"
+#include "sdf_internal.h"
 
 using namespace sdfk;
 
@@ -298,274 +288,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 // meshing's scan and emission, the slab kernels, the STL records -- lives in sdf_plain.hip: see build.sh for why)
 
 // ============================================================================================
-// host side: the C ABI
+// host side: contexts, tapes and the generate pipeline (the runtime underneath: sdf_runtime.h; the handles: sdf_internal.h; what
+// reads a finished mesh: sdf_mesh_out.hip; the multi-GPU step: sdf_comm.hip; each further feature its own unit)
 // ============================================================================================
-
-static thread_local std::string g_err;
-static int fail(const std::string &m) { g_err = m; return 1; }
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-// Waiting for the device WITHOUT going to sleep.  hipStreamSynchronize / hipEventSynchronize block on an interrupt
-// after a short active wait; on a virtualised host the wake-up costs milliseconds (BENCH_r02: a synchronous 512^3 call
-// took 2.2 ms on the driver's box against 0.4 ms of device work).  The calls of this library last 0.3 - 40 ms, so the
-// host polls the completion signal (hipStreamQuery / hipEventQuery read it directly) for up to g_spin_us microseconds
-// and only then falls back to the blocking wait.  SDF_WAIT_SPIN_US=0 restores the blocking behaviour.
-static long g_spin_us = [] { const char *e = getenv("SDF_WAIT_SPIN_US"); return e ? atol(e) : 100000L; }();
-template <typename Query, typename Block>
-static hipError_t spin_then_block(Query query, Block block) {
-    if (g_spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned n = 0;; n++) {
-            const hipError_t e = query();
-            if (e != hipErrorNotReady) return e;
-            if ((n & 63u) == 63u &&
-                std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > g_spin_us)
-                break;
-            __builtin_ia32_pause();
-        }
-    }
-    return block();
-}
-// Entering the library: select the context's device and DROP whatever error another library left in this thread's
-// "last error" slot (hipGetLastError is sticky per thread: a failed probe inside RCCL or torch -- seen after
-// destroy_process_group: "invalid device ordinal" -- would otherwise be reported by our next launch check)
-static hipError_t set_device(int device) {
-    const hipError_t e = hipSetDevice(device);
-    (void)hipGetLastError();
-    return e;
-}
-static hipError_t stream_wait(hipStream_t s) {
-    return spin_then_block([&] { return hipStreamQuery(s); }, [&] { return hipStreamSynchronize(s); });
-}
-static hipError_t event_wait(hipEvent_t ev) {
-    return spin_then_block([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); });
-}
-
-// Every allocation of this translation unit goes through these two, so that the tests can make the n-th one fail
-// (sdf_test_fail_alloc) and check that every error path hands back what it had taken.
-static int g_fail_alloc_in = 0;      // > 0: the g_fail_alloc_in-th allocation from now fails once
-static bool g_alloc_hook_hit = false;
-static bool alloc_fails_now() { g_alloc_hook_hit = g_fail_alloc_in > 0 && --g_fail_alloc_in == 0; return g_alloc_hook_hit; }
-static hipError_t dev_malloc(void **p, size_t bytes) { if (alloc_fails_now()) { *p = nullptr; return hipErrorOutOfMemory; } return hipMalloc(p, bytes); }
-static hipError_t host_malloc(void **p, size_t bytes) { if (alloc_fails_now()) { *p = nullptr; return hipErrorOutOfMemory; } return hipHostMalloc(p, bytes, hipHostMallocDefault); }
-
-// Device allocations are recycled through a small per-device free list: hipMalloc / hipFree cost
-// tens of microseconds each (and hipFree synchronises), which at ~1 ms per generate call was 10 %
-// of the step when every mesh allocated and freed its seven buffers.
-static const bool g_pool_trace = getenv("SDF_POOL_TRACE") != nullptr;   // every hipMalloc / hipFree behind the pool, to stderr
-struct DevPool {
-    struct Blk { void *p; size_t bytes; int device; };
-    std::vector<Blk> free_list;
-    std::mutex mu;
-    void *take(size_t need, int device, size_t *got) {
-        std::lock_guard<std::mutex> g(mu);
-        int best = -1;
-        for (int i = 0; i < (int)free_list.size(); i++) {
-            const Blk &b = free_list[i];
-            if (b.device != device || b.bytes < need || b.bytes > std::max<size_t>(4 * need, 1 << 16)) continue;
-            if (best < 0 || b.bytes < free_list[best].bytes) best = i;
-        }
-        if (best < 0) return nullptr;
-        void *p = free_list[best].p;
-        *got = free_list[best].bytes;
-        free_list.erase(free_list.begin() + best);
-        return p;
-    }
-    void give(void *p, size_t bytes, int device) {
-        std::lock_guard<std::mutex> g(mu);
-        // (up to eight calls in flight x up to twelve buffers each come back at once: a list shorter than that evicts -- hipFree, a
-        // device synchronisation -- blocks the very next call allocates again)
-        if (free_list.size() >= 160) {   // evict the oldest block
-            if (g_pool_trace) fprintf(stderr, "[sdf pool] evict %zu bytes (hipFree)\n", free_list.front().bytes);
-            (void)hipFree(free_list.front().p);
-            free_list.erase(free_list.begin());
-        }
-        free_list.push_back({p, bytes, device});
-    }
-    void drop_device(int device) {
-        std::lock_guard<std::mutex> g(mu);
-        for (size_t i = 0; i < free_list.size();) {
-            if (free_list[i].device == device) { (void)hipFree(free_list[i].p); free_list.erase(free_list.begin() + i); }
-            else i++;
-        }
-    }
-};
-static DevPool g_pool;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int device = -1;
-    int ensure(size_t need) {
-        if (need <= bytes) return 0;
-        release();
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        size_t want = std::max(need, (size_t)256);
-        want = (want + 255) & ~(size_t)255;
-        size_t got = 0;
-        if (void *q = g_pool.take(want, dev, &got)) { p = q; bytes = got; device = dev; return 0; }
-        if (g_pool_trace) fprintf(stderr, "[sdf pool] miss %zu bytes (hipMalloc)\n", want);
-        hipError_t e = dev_malloc(&p, want);
-        if (e != hipSuccess && !g_alloc_hook_hit) {   // give the cached blocks back to the driver and retry once
-            g_pool.drop_device(dev);
-            e = dev_malloc(&p, want);
-        }
-        if (e != hipSuccess) { p = nullptr; return fail(std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e)); }
-        bytes = want; device = dev;
-        return 0;
-    }
-    void release() { if (p) g_pool.give(p, bytes, device); p = nullptr; bytes = 0; }
-};
-
-#define SDF_STAGE_BYTES (1u << 20)
-// Calls in flight on one context (sdf_generate_to_device_async): each owns a slot = its pinned staging
-// (axes on the way in, counters on the way out) and its events; a slot is reused only after the call that
-// held it has completed.
-// (eight since r04: with six calls in flight the 512^3 example steps in 0.237 ms, with four in 0.248, same box alternating;
-// a lane's park slots -- 1.2 GB -- are allocated when the lane is first used)
-#ifndef SDF_CALL_SLOTS
-#define SDF_CALL_SLOTS 8
-#endif
-struct CallSlot {
-    hipEvent_t e0 = nullptr, e2 = nullptr, e3 = nullptr, e4 = nullptr;   // start, prepass end, k_mesh start (re-runs), k_mesh end
-    hipEvent_t done = nullptr;                                            // behind the counters' copy to the host
-    bool busy = false;
-    struct sdf_mesh *owner = nullptr;                                     // the in-flight mesh whose counters / events the slot holds
-    hipStream_t stream = nullptr;                                         // the lane asynchronous calls of this slot run on
-    DevBuf park;                                                          // ... and its k_mesh staging slots
-};
-#define SDF_BATCH_SIZE_MAX 512   // (513^3 float32 = 540 MB per tile: generate_big takes one tile per submission there)
-#define SDF_PARK_TRIS 8192   // triangles per workgroup staging slot of k_mesh (36 bytes each); larger batches wait instead
-                             // (16 slots per workgroup: 1.2 GB per call lane, allocated on a lane's first use; with 4096
-                             // per slot weave at 2^33 has batches that cannot park: 30.3 instead of 27.7 ms)
-
-struct sdf_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev[8] = {};
-    int n_cu = 256;
-    size_t lds_max = 0;
-    DevBuf scratch_in, scratch_out, rows, rows_off, mc;
-    DevBuf ext;                       // closure points / values of sdf_eval_*extern* (L_EXTERN leaves)
-    DevBuf field_vals, field_vol, field_tiles;   // sdf_generate_field: a chunk's sampled values (f64), volumes (f32), tile table
-    DevBuf prof;                      // SDF_MESH_PROF=1: per-phase cycle counters of k_mesh (diagnostics)
-    int prune = 1;                    // SDF_PRUNE=0 switches the interval prepass off (diagnostics)
-    int parking = 1;                  // SDF_PARK=0: k_mesh waits for its predecessors instead of parking a batch (diagnostics)
-    int cull = 1;                     // SDF_CULL=0: k_mesh samples every voxel of a batch instead of deciding cell groups by intervals
-    int prune_list_min = 8192;        // SDF_PRUNE_LIST_MIN: from this many batches on the interval prepass runs behind k_compact, over the work list
-    int park_spins = 1;               // SDF_PARK_SPINS: polls before parking (tuning; measured: waiting never pays)
-    DevBuf park;                      // k_mesh's staging slots, one per CU (allocated by the first sdf_generate)
-    int mesh_slots = -1;              // SDF_MESH_SLOTS override of the register-file variant (tuning)
-    std::vector<DevBuf> arena_pool;   // soup buffers handed back by destroyed meshes
-    std::vector<DevBuf> counter_pool; // 64-byte MeshCounters blocks handed back by destroyed meshes
-    void *h_stage = nullptr;          // pinned host staging, SDF_CALL_SLOTS x SDF_STAGE_BYTES
-    CallSlot slots[SDF_CALL_SLOTS];
-    unsigned slot_seq = 0;
-    int slot_streams = 1;             // SDF_SLOT_STREAMS=0: asynchronous calls stay on the context's stream (diagnostics)
-    int cull_block = 0;               // SDF_CULL_BLOCK=64 / 128 / 256: threads per work item of k_cull (0: the default of the variant)
-    int tail_order = 1;               // SDF_TAIL_ORDER=0: k_mesh takes the whole work list in order
-    int twopass = -1;                 // SDF_MESH_TWOPASS=0 / 1: force the one-pass k_mesh (look-back + parking) resp. k_mesh / k_scan_items / k_emit2
-    int defer = 1;                    // SDF_DEFER=0: k_mesh keeps every tile dense and writes (or parks) a batch's triangles right after counting it
-    int cull_levels = 0;              // SDF_CULL_LEVELS=2 / 3: interval levels of k_cull (3: + sub-groups of 2^3 cells); 0: by the tape (see enqueue_cull)
-    DevBuf bounds_work;               // k_estimate_bounds_w: the waves' exchange words (tagged per call, sdf_bounds.hip)
-    unsigned bounds_tag = 0, bounds_tag0 = 0;
-    // sdf_generate_records: what the last call of a MODEL (content hash) on a grid needed -- triangles, raw-area triangles -- so that the
-    // next one, possibly through a fresh tape object of the same model, can size its slab without a host round trip
-    struct RecHint { unsigned long long tris = 0, raw = 0; };
-    std::map<std::pair<unsigned long long, unsigned long long>, RecHint> rec_hints;
-    void *h_rec = nullptr;            // pinned staging of sdf_mesh_emit_host_workers: a slab's head, raw area and records on their way to the host threads
-    size_t h_rec_bytes = 0;
-    std::vector<hipEvent_t> rec_ev;   // ... one event per piece of the copy
-};
-
-struct sdf_tape {
-    sdf_ctx *ctx = nullptr;
-    uint32_t *d_code = nullptr;
-    double *d_c64 = nullptr;
-    float *d_c32 = nullptr;
-    uint32_t n_words = 0, n_consts = 0;
-    bool full = false;
-    uint32_t n_p = 0, n_d = 0;
-    uint16_t *d_rstart = nullptr, *d_lstart = nullptr;   // operand ranges of the prunable combines (or NULL)
-    bool ia_complete = false;                            // every op has an interval form (sdf_interval.h ia_has_form)
-    bool ia_rare = false;                                // ... one of them a leaf of ia_leaf_rare (the k_cull variant that knows them)
-    uint32_t n_extern = 0;                               // user closures the tape reads through L_EXTERN leaves (sdf_eval_points_extern_*)
-    unsigned long long hint_key = 0, hint_total_tris = 0;   // arena sizing: last call of this tape
-    unsigned long long content_hash = 0;                    // FNV-1a of the code words and the constants' bits: what identifies the MODEL,
-                                                            // on every rank alike and whatever address the tape object lands on (sdf_comm.inc)
-};
-
-// What one fused call (prepass -> k_cull -> k_mesh) is asked to do.  The entry points build one by naming fields; a call in
-// flight keeps its descriptor in sdf_mesh::Pending.
-struct GenCall {
-    sdf_tape *tape = nullptr;
-    const double *X = nullptr, *Y = nullptr, *Z = nullptr;   // the host's axes
-    int nx = 0, ny = 0, nz = 0, bs = 0, sparse = 0, precision = 0;
-    int64_t shard_index = 0, shard_count = 1;
-    // where the triangles go.  SOUP: a library buffer sized from the last call of the tape on the grid; CALLER: d_out, cap_tris
-    // float64 triangles; SLAB: compact mode (sdf_generate_compact_async, sdf_generate_records) -- d_out is a SLAB of capacity
-    // (cap_items, cap_tris)
-    enum Dest { SOUP, CALLER, SLAB } dest = SOUP;
-    void *d_out = nullptr;
-    int64_t cap_tris = 0, cap_items = 0;
-    bool collected = false;                   // the call returns in flight and sdf_mesh_wait finishes it (else: synchronous)
-    hipStream_t lane = nullptr;               // the stream the whole call is enqueued on (the exchange steps of sdf_comm run on lanes of their own)
-    // the skip test's verdict for every batch is already on the device (0 skipped / 255 pending, n_batches
-    // bytes: sdf_skip_kinds, possibly all-gathered from the ranks that each tested a share): k_skip is not run
-    const unsigned char *d_kinds = nullptr;
-};
-// ... and what the call learned while it was enqueued: finishing it needs these
-struct CallState { int slot = 0, nb = 0; bool pruning = false, own_start = false; uint32_t n_instr = 0; unsigned long long key = 0; };
-
-struct sdf_mesh {
-    sdf_ctx *ctx = nullptr;
-    sdf_stats st = {};
-    GridDesc g = {};
-    DevBuf axes, kinds, worklist, status, out, prune, tapes, cull, order;
-    DevBuf desc, cellrecs, trilist;   // two-pass meshing: per work item / per surface cell / per triangle (sdf_device.h ItemDesc)
-    DevBuf blockidx;                  // ... and per 256 triangles of the soup: the work item of the first of them
-    bool pruned = false;
-    hipStream_t stream = nullptr;  // the stream the generating call ran on (the context's, or a call slot's lane)
-    DevBuf counters;               // this call's MeshCounters block (pooled in the context)
-    int work_begin = 0, work_end = 0;
-    void *emitted_to = nullptr;    // caller buffer the soup was gathered into by sdf_generate_to_device
-    // sdf_generate_to_device_async: everything sdf_mesh_wait needs to finish the call
-    struct Pending {
-        bool active = false;
-        GenCall call;                  // (its axes point into `axes`)
-        std::vector<double> axes;      // host copy (a soup that does not fit is re-run synchronously)
-        CallState got;
-    } pend;
-    double *weld_pts = nullptr;    // sdf_mesh_weld: unique rows / row -> unique row (hipMalloc'ed by sdf_weld.hip)
-    long long *weld_inv = nullptr;
-    long long weld_n = -1;
-    // sdf_mesh_vertex_normals: weld_n x 3 float64 + the flat counter in one block of its own (dev_malloc, freed with the mesh); the
-    // model (content hash) and eps they were taken with: a second call with the same ones reuses them
-    double *nrm = nullptr;
-    bool nrm_valid = false;
-    unsigned long long nrm_model = 0;
-    double nrm_eps = 0.0;
-    long long nrm_flat = 0;
-    // sdf_generate_records: the triangles were written as 16-byte records into a slab of the library's (sdf_slab.h); the float64 soup
-    // is made on the host threads (sdf_mesh_emit_host_workers) or, for the readers that want it on the device, by k_expand on demand
-    bool records = false;
-    DevBuf slab;
-    long long slab_items = 0, slab_tris = 0, n_raw = 0;
-    bool rec_overflow = false;     // the slab (or its raw area) was too small: rec_need_tris is the capacity that holds the call
-    long long rec_need_tris = 0;
-};
-
-namespace sdfk {
-int weld_device(hipStream_t stream, const double *pts, long long n, double **d_uniq, long long **d_inv, long long *n_unique);   // sdf_weld.hip
-int level_set_host(hipStream_t st, const double *h_pts, long long np, const int32_t *h_tris, long long nt, double vs, int hw,
-                   int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, long long cap, std::string &err);           // sdf_level_set.hip
-int edt_host(hipStream_t st, const uint8_t *h_mask, long long rows, long long cols, double *h_out, std::string &err);   // sdf_edt.hip
-}
 
 static bool tape_needs_full(const uint32_t *code, uint32_t n_words, const double *consts) {
     auto trig_ease = [](int id) {
@@ -618,7 +343,6 @@ int sdf_abi_version(void) { return SDF_ABI_VERSION; }
 #define SDF_BUILD_INFO "unknown toolchain (not built by csrc/build.sh)"
 #endif
 const char *sdf_build_info(void) { return SDF_BUILD_INFO; }
-const char *sdf_last_error(void) { return g_err.c_str(); }
 
 int sdf_device_count(void) {
     int n = 0;
@@ -627,7 +351,6 @@ int sdf_device_count(void) {
     return n;
 }
 
-int sdf_test_fail_alloc(int nth) { g_fail_alloc_in = nth > 0 ? nth : 0; return 0; }
 
 int sdf_device_mem_info(int device, size_t *free_bytes, size_t *total_bytes) {
     if (!free_bytes || !total_bytes) return fail("sdf_device_mem_info: NULL argument");
@@ -859,16 +582,8 @@ int sdf_tape_destroy(sdf_tape *t) {
 }  // extern "C"
 
 // dispatch over (precision, FULL)
-#define LAUNCH_TAPE(KERNEL, grid, block, shmem, t, precision, ...)                                              \
-    do {                                                                                                        \
-        if ((precision) == SDF_PRECISION_F64) {                                                                 \
-            if ((t)->full) hipLaunchKernelGGL((KERNEL<double, true>), grid, block, shmem, (t)->ctx->stream, (t)->d_code, (t)->d_c64, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<double, false>), grid, block, shmem, (t)->ctx->stream, (t)->d_code, (t)->d_c64, __VA_ARGS__); \
-        } else {                                                                                                \
-            if ((t)->full) hipLaunchKernelGGL((KERNEL<float, true>), grid, block, shmem, (t)->ctx->stream, (t)->d_code, (t)->d_c32, __VA_ARGS__); \
-            else hipLaunchKernelGGL((KERNEL<float, false>), grid, block, shmem, (t)->ctx->stream, (t)->d_code, (t)->d_c32, __VA_ARGS__); \
-        }                                                                                                       \
-    } while (0)
+#define LAUNCH_TAPE(KERNEL, grid, block, shmem, t, precision, ...) \
+    LAUNCH_TAPE_ON((t)->ctx->stream, KERNEL, grid, block, shmem, t, precision, __VA_ARGS__)   /* on the context's stream */
 
 #define LAUNCH_TAPE_ON(STREAM, KERNEL, grid, block, shmem, t, precision, ...)                                   \
     do {                                                                                                        \
@@ -1058,55 +773,10 @@ int sdf_marching_cubes_host(sdf_ctx *c, const float *h_vol, int n0, int n1, int 
     return 0;
 }
 
-int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t n_pts, const int32_t *h_tris, int64_t n_tris, double vs, int hw,
-                            int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, int64_t cap) {
-    if (!c || !out_ijk0 || !out_dims) return fail("sdf_mesh_level_set_host: NULL argument");
-    HIPCHK(set_device(c->device));
-    std::string err;
-    const int rc = sdfk::level_set_host(c->stream, h_pts, n_pts, h_tris, n_tris, vs, hw, out_ijk0, out_dims, h_out, cap, err);
-    if (rc) { fail("sdf_mesh_level_set_host: " + err); return rc; }
-    return 0;
-}
-
-int sdf_distance_texture_host(sdf_ctx *c, const uint8_t *h_mask, int64_t rows, int64_t cols, double *h_out) {
-    if (!c || !h_mask || !h_out) { fail("sdf_distance_texture_host: NULL argument"); return 2; }
-    HIPCHK(set_device(c->device));
-    std::string err;
-    const int rc = sdfk::edt_host(c->stream, h_mask, rows, cols, h_out, err);
-    if (rc) { fail("sdf_distance_texture_host: " + err); return rc; }
-    return 0;
-}
-
-static thread_local double g_render_kernel_ms = 0.0;
-
-int sdf_render_host(sdf_tape *t, const double *frame18, int width, int height, const double *params5, int max_steps, int refine,
-                    double *h_depth, double *h_normal, int32_t *h_steps, uint8_t *h_status) {
-    if (!t) { fail("sdf_render_host: NULL argument"); return 2; }
-    if (t->n_extern) { fail("sdf_render_host: the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip"); return 2; }
-    sdf_ctx *c = t->ctx;
-    HIPCHK(set_device(c->device));
-    std::string err;
-    const int rc = sdfk::render_host(c->stream, t->d_code, t->d_c64, t->full, frame18, width, height, params5, max_steps, refine, h_depth,
-                                     h_normal, h_steps, h_status, &g_render_kernel_ms, err);
-    if (rc) { fail("sdf_render_host: " + err); return rc; }
-    return 0;
-}
-
-double sdf_render_last_kernel_ms(void) { return g_render_kernel_ms; }
-
 }  // extern "C"
 
-// The grid of a call: batches of bs cells per axis, without the device copies of the axes.  Returns the number of batches; a
-// batch size below 1 (sdf_generate_records asks before the batch size has been validated) gives a grid without batches.
-static long long grid_desc(int nx, int ny, int nz, int bs, GridDesc &g) {
-    g = GridDesc{};
-    g.nx = nx; g.ny = ny; g.nz = nz; g.bs = bs;
-    if (bs < 1) return 0;
-    g.nbx = (nx + bs - 1) / bs; g.nby = (ny + bs - 1) / bs; g.nbz = (nz + bs - 1) / bs;
-    return (long long)g.nbx * g.nby * g.nbz;
-}
-// ... for an entry point that indexes the batches with an int (`who` names it in the message)
-static int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb) {
+// the grid of a call (grid_desc, sdf_internal.h) for an entry point that indexes the batches with an int (`who` names it in the message)
+int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb) {
     const long long nb64 = grid_desc(nx, ny, nz, bs, g);
     if (nb64 > 0x7fffffffLL) return fail(std::string(who) + ": too many batches");
     nb = (int)nb64;
@@ -1172,8 +842,8 @@ static int launch_mesh(sdf_tape *t, const void *code, int precision, MeshArgs &a
 
 // the skip test (`_skip`, reference sdf/core.py:28-43) of batches [b0, b1) alone, enqueued on `st`: d_kinds[b] = 0 (skipped) or
 // 255 (pending) for those batches; the axes are on the device already (X, then Y, then Z)
-static int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
-                        unsigned char *d_kinds, hipStream_t st) {
+int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
+                 unsigned char *d_kinds, hipStream_t st) {
     if (b1 <= b0) return 0;
     GridDesc g;
     grid_desc(nx, ny, nz, bs, g);
@@ -1226,7 +896,7 @@ static unsigned long long grid_key(int nx, int ny, int nz, int bs, int sparse, i
 // The end of a fused call whose counters have arrived in its slot's pinned staging (the stream was waited for, or the slot's
 // `done` event): the counters into h, the event intervals, the look-back time-out.  The statistics are taken unless the
 // soup overflowed and the caller repeats the call (stats_if_short: a short SLAB is not repeated here, its call counts as it is).
-static int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, MeshCounters &h) {
+int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, MeshCounters &h) {
     sdf_ctx *c = m->ctx;
     CallSlot &cs = c->slots[s.slot];
     h = *(const MeshCounters *)((char *)c->h_stage + (size_t)s.slot * SDF_STAGE_BYTES + SDF_STAGE_BYTES - 256);
@@ -1540,7 +1210,7 @@ static int mesh_prof_report(sdf_ctx *c, int grid, float ms) {
     return 0;
 }
 
-static int generate_impl(sdf_mesh *m, const GenCall &call) {
+int generate_impl(sdf_mesh *m, const GenCall &call) {
     sdf_tape *t = call.tape;
     sdf_ctx *c = t->ctx;
     const bool slab = call.dest == GenCall::SLAB;
@@ -1834,15 +1504,6 @@ static int generate_entry(const GenCall &call, sdf_mesh **out) {
     return 0;
 }
 
-// the part of a call descriptor that every entry point takes as arguments
-static GenCall gen_call(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs, int sparse,
-                        int64_t shard_index, int64_t shard_count, int precision) {
-    GenCall call;
-    call.tape = t; call.X = X; call.Y = Y; call.Z = Z; call.nx = nx; call.ny = ny; call.nz = nz;
-    call.bs = bs; call.sparse = sparse; call.precision = precision; call.shard_index = shard_index; call.shard_count = shard_count;
-    return call;
-}
-
 int sdf_generate(sdf_tape *t, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, int bs,
                  int sparse, int64_t shard_index, int64_t shard_count, int precision, sdf_mesh **out) {
     return generate_entry(gen_call(t, X, nx, Y, ny, Z, nz, bs, sparse, shard_index, shard_count, precision), out);
@@ -2064,484 +1725,4 @@ int sdf_expand_slabs(sdf_ctx *c, const void *const *d_slabs, int n_slabs, int64_
     return 0;
 }
 
-int sdf_mesh_wait(sdf_mesh *m, int *emitted) {
-    if (!m) return fail("sdf_mesh_wait: NULL argument");
-    sdf_mesh::Pending &pd = m->pend;
-    if (pd.active) {
-        sdf_ctx *c = m->ctx;
-        HIPCHK(set_device(c->device));
-        CallSlot &cs = c->slots[pd.got.slot];
-        HIPCHK(event_wait(cs.done));
-        pd.active = false;
-        const bool slab = pd.call.dest == GenCall::SLAB;
-        MeshCounters h;
-        const int rc = finish_call(m, pd.call, pd.got, slab, h);
-        cs.busy = false; cs.owner = nullptr;      // (everything the slot held for this mesh has been read)
-        if (rc) return 1;
-        if (h.overflow && slab) {
-            // a slab that was too small: the exchange protocol retries with larger slabs on EVERY rank (sdf_amd/dist.py)
-            m->emitted_to = nullptr;
-        } else if (h.overflow) {
-            // the soup did not fit the caller's buffer: the call is repeated synchronously into library memory
-            // (sized from the count just learned)
-            pd.call.tape->hint_key = pd.got.key; pd.call.tape->hint_total_tris = std::max<unsigned long long>(h.total, 1);
-            GenCall again = pd.call;
-            again.dest = GenCall::SOUP; again.d_out = nullptr; again.cap_tris = 0;
-            again.collected = false;
-            if (generate_impl(m, again)) return 1;
-            m->st.n_retries += 1;
-        } else {
-            m->emitted_to = slab ? nullptr : pd.call.d_out;
-            m->st.n_retries = 0;
-        }
-        pd.axes.clear(); pd.axes.shrink_to_fit();
-    }
-    if (emitted) *emitted = (m->emitted_to != nullptr || m->st.n_triangles == 0) ? 1 : 0;
-    return 0;
-}
-
-// every reader of a mesh first collects a call that is still in flight
-#define MESH_READY(m) do { if ((m)->pend.active && sdf_mesh_wait((m), nullptr)) return 1; } while (0)
-
-int sdf_mesh_stats(sdf_mesh *m, sdf_stats *out) {
-    if (!m || !out) return fail("sdf_mesh_stats: NULL argument");
-    MESH_READY(m);
-    *out = m->st;
-    return 0;
-}
-
-int64_t sdf_mesh_triangles(sdf_mesh *m) {
-    if (!m) return 0;
-    if (m->pend.active && sdf_mesh_wait(m, nullptr)) return -1;
-    return m->st.n_triangles;
-}
-
-// where the soup of a mesh lives: the caller's buffer of sdf_generate_to_device, or the library's
-static const void *mesh_soup(const sdf_mesh *m) { return m->emitted_to ? m->emitted_to : m->out.p; }
-
-// a mesh of sdf_generate_records holds 16-byte records; a reader that wants the float64 soup on the device gets it from k_expand, once
-static int ensure_soup(sdf_mesh *m) {
-    if (!m->records || m->out.p || m->st.n_triangles == 0) return 0;
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    if (m->out.ensure((size_t)m->st.n_triangles * 72)) return 1;
-    SlabPtrs ptrs = {};
-    ptrs.p[0] = (const unsigned char *)m->slab.p;
-    HIPCHK((hipError_t)sdf_launch_expand(c->stream, ptrs, 1, m->slab_items, m->slab_tris, (double *)m->out.p, (unsigned long long)m->st.n_triangles));
-    return 0;
-}
-#define MESH_SOUP_READY(m) do { if (ensure_soup(m)) return 1; } while (0)
-
-int sdf_mesh_emit_device(sdf_mesh *m, void *d_out) {
-    if (!m || !d_out) return fail("sdf_mesh_emit_device: NULL argument");
-    MESH_READY(m);
-    MESH_SOUP_READY(m);
-    sdf_ctx *c = m->ctx;
-    if (m->st.n_triangles == 0 || d_out == mesh_soup(m)) return 0;
-    HIPCHK(set_device(c->device));
-    HIPCHK(hipEventRecord(c->ev[3], c->stream));
-    HIPCHK(hipMemcpyAsync(d_out, mesh_soup(m), (size_t)m->st.n_triangles * 72, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev[4], c->stream));
-    HIPCHK(stream_wait(c->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev[3], c->ev[4]));
-    m->st.ms_emit = ms;
-    return 0;
-}
-
-// (Cutting a large device-to-host copy into pieces that travel on several streams at once was measured in r02: the
-// 212 MB soup took 7.7 ms as one copy, 8.7 ms as two, 9.8 ms as four -- one copy already runs at the link's rate for
-// pinned memory (28 GB/s on the test boxes).  A kernel that stores straight into the mapped pinned block, 32 to 2048
-// workgroups: the same 7.5 ms.  One copy it stays.)
-static int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes) {
-    HIPCHK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(stream_wait(c->stream));
-    return 0;
-}
-
-// The soup on the host.  A mesh of sdf_generate_records sends its RECORDS (16 bytes per triangle + a transform per work item) and the
-// float64 soup is made where it is wanted, by `workers` host threads (<= 0: as many as the machine has, at most 32 -- a caller's number: at most 64; the reference's
-// `workers=` argument, sdf/core.py:87) -- block by block while the later records are still on the link: the pieces of the copy are
-// followed by events, the calling thread publishes how far the records have arrived and takes blocks itself in between.  The
-// arithmetic is k_expand's (`double(local) * scale + offset` on the same operands): the soup is the one the device would write.
-// Any other mesh: one copy of the float64 soup, as before (`workers` is ignored).
-int sdf_mesh_emit_host_workers(sdf_mesh *m, double *h_out, int workers) {
-    if (!m || !h_out) return fail("sdf_mesh_emit_host: NULL argument");
-    MESH_READY(m);
-    if (m->st.n_triangles == 0) return 0;
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    if (!m->records || m->out.p) return copy_to_host(c, h_out, mesh_soup(m), (size_t)m->st.n_triangles * 72);
-    const long long nt = m->st.n_triangles, ni = (long long)m->work_end - m->work_begin, nraw = std::min<long long>(m->n_raw, SlabLayout(m->slab_items, m->slab_tris).raw_cap);
-    const SlabLayout L(m->slab_items, m->slab_tris);
-    // pinned staging: [prefix ni x 8 | transforms ni x 48 | raw area nraw x 36 | records nt x 16]
-    const size_t off_xf = (size_t)ni * 8, off_raw = off_xf + (size_t)ni * 48, off_rec = (off_raw + (size_t)nraw * 36 + 63) & ~(size_t)63;
-    const size_t need = off_rec + (size_t)nt * 16;
-    if (c->h_rec_bytes < need) {
-        if (c->h_rec) (void)hipHostFree(c->h_rec);
-        c->h_rec = nullptr; c->h_rec_bytes = 0;
-        const size_t want = need + need / 8 + (1u << 20);
-        if (host_malloc(&c->h_rec, want) != hipSuccess) { c->h_rec = nullptr; return fail("sdf_mesh_emit_host: pinned staging for the records"); }
-        c->h_rec_bytes = want;
-    }
-    char *hs = (char *)c->h_rec;
-    const char *slab = (const char *)m->slab.p;
-    // the pieces: head (prefix, transforms, raw area) first, then the records in ~ 12 pieces of whole blocks
-    sdfhost::ExpandJob job;
-    static const long long rec_block = [] { const char *e = getenv("SDF_REC_BLOCK"); return e && atoll(e) >= 64 ? atoll(e) : 8192ll; }();     // (tuning)
-    static const long long rec_pieces = [] { const char *e = getenv("SDF_REC_PIECES"); return e && atoll(e) >= 1 ? std::min(atoll(e), 64ll) : 12ll; }();
-    job.block = rec_block;
-    const long long nblk = (nt + job.block - 1) / job.block;
-    const long long blk_per_piece = std::max<long long>(8, (nblk + rec_pieces - 1) / rec_pieces);
-    const int npieces = (int)((nblk + blk_per_piece - 1) / blk_per_piece);
-    while ((int)c->rec_ev.size() < npieces + 1) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->rec_ev.push_back(e);
-    }
-    hipStream_t st = c->stream;
-    static const bool rec_trace = getenv("SDF_REC_TRACE") != nullptr;   // (diagnostics: when the pieces arrived, when the last block was written)
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto tr_us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count(); };
-    // (r06j - r06l, 2 x 64 cores: 8 threads are bound by their own arithmetic (47 us per block of 8192 triangles, 2.2 ms), 32 by the memory
-    // the block lies in (138 us per block, 1.8 ms), 64 are no faster and have outliers: the machine's count is capped at 32, a caller's at 64)
-    int nthreads = workers > 0 ? std::min(workers, 64) : std::min((int)std::thread::hardware_concurrency(), 32);
-    nthreads = std::max(1, nthreads);
-    nthreads = (int)std::min<long long>(nthreads, std::max<long long>(nblk, 1));
-    job.prefix = (const unsigned long long *)hs; job.xf = (const double *)(hs + off_xf);
-    job.raw = (const float *)(hs + off_raw); job.raw_cap = std::max<long long>(nraw, 1);
-    job.recs = (const Tri16 *)(hs + off_rec);
-    job.n_items = ni; job.n_tris = nt; job.out = h_out;
-    std::vector<float> blk_trace;
-    if (rec_trace) { blk_trace.assign((size_t)2 * nblk, 0.0f); job.trace = blk_trace.data(); job.t_origin = tr0; }
-    static std::mutex expand_mu;                         // (ONE expansion at a time per process: the pool serves one job)
-    std::lock_guard<std::mutex> expand_lock(expand_mu);
-    sdfhost::Pool &pool = sdfhost::Pool::get();
-    // (from here on the helpers hold the job: an error lets them go before it returns)
-#define RECCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { job.abort.store(1); pool.wait(job); return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    pool.start(job, nthreads - 1);                       // (the helpers wake up while the copies are enqueued; this thread is one of the workers too)
-    RECCHK(hipMemcpyAsync(hs, slab + L.prefix_off, (size_t)ni * 8, hipMemcpyDeviceToHost, st));
-    RECCHK(hipMemcpyAsync(hs + off_xf, slab + L.xf_off, (size_t)ni * 48, hipMemcpyDeviceToHost, st));
-    if (nraw) RECCHK(hipMemcpyAsync(hs + off_raw, slab + L.raw_off, (size_t)nraw * 36, hipMemcpyDeviceToHost, st));
-    RECCHK(hipEventRecord(c->rec_ev[0], st));
-    for (int k = 0; k < npieces; k++) {
-        const long long t0 = (long long)k * blk_per_piece * job.block, t1 = std::min(nt, t0 + blk_per_piece * job.block);
-        RECCHK(hipMemcpyAsync(hs + off_rec + (size_t)t0 * 16, slab + L.tris_off + (size_t)t0 * 16, (size_t)(t1 - t0) * 16, hipMemcpyDeviceToHost, st));
-        RECCHK(hipEventRecord(c->rec_ev[(size_t)k + 1], st));
-    }
-#undef RECCHK
-    const double t_enq = tr_us();
-    double t_piece[16] = {};
-    hipError_t err = event_wait(c->rec_ev[0]);
-    const double t_head = tr_us();
-    for (int k = 0; k < npieces && err == hipSuccess; k++) {
-        err = event_wait(c->rec_ev[(size_t)k + 1]);
-        if (err == hipSuccess) job.avail.store(std::min(nt, (long long)(k + 1) * blk_per_piece * job.block), std::memory_order_release);
-        if (k < 16) t_piece[k] = tr_us();
-    }
-    if (err != hipSuccess) job.abort.store(1);
-    else sdfhost::expand_work(job);
-    const double t_own = tr_us();
-    pool.wait(job);
-    if (rec_trace) {
-        fprintf(stderr, "[records] %lld triangles, %d threads, %d pieces: enqueued %.0f us, head %.0f, pieces", nt, nthreads, npieces, t_enq, t_head);
-        for (int k = 0; k < npieces && k < 16; k++) fprintf(stderr, " %.0f", t_piece[k]);
-        fprintf(stderr, "; own share done %.0f, all done %.0f us\n", t_own, tr_us());
-        double dur = 0, dmax = 0;
-        for (long long b = 0; b < nblk; b++) { const double d = blk_trace[2 * b + 1] - blk_trace[2 * b]; dur += d; dmax = std::max(dmax, d); }
-        fprintf(stderr, "[records] %lld blocks of %lld triangles: %.0f us each on average (max %.0f); block: started / written, every %lld-th:", nblk, job.block, dur / std::max<long long>(nblk, 1), dmax, std::max<long long>(nblk / 24, 1));
-        for (long long b = 0; b < nblk; b += std::max<long long>(nblk / 24, 1)) fprintf(stderr, " %lld: %.0f / %.0f", b, blk_trace[2 * b], blk_trace[2 * b + 1]);
-        fprintf(stderr, "\n");
-    }
-    if (err != hipSuccess) return fail(std::string("sdf_mesh_emit_host: copying the records: ") + hipGetErrorString(err));
-    return 0;
-}
-
-int sdf_mesh_emit_host(sdf_mesh *m, double *h_out) { return sdf_mesh_emit_host_workers(m, h_out, 0); }
-
-int sdf_mesh_emit_host_range(sdf_mesh *m, int64_t first_tri, int64_t n_tris, double *h_out) {
-    if (!m || !h_out) return fail("sdf_mesh_emit_host_range: NULL argument");
-    MESH_READY(m);
-    if (first_tri < 0 || n_tris < 0 || first_tri + n_tris > m->st.n_triangles) return fail("sdf_mesh_emit_host_range: range outside the soup");
-    if (n_tris == 0) return 0;
-    MESH_SOUP_READY(m);
-    HIPCHK(set_device(m->ctx->device));
-    HIPCHK(hipMemcpyAsync(h_out, (const char *)mesh_soup(m) + (size_t)first_tri * 72, (size_t)n_tris * 72, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(stream_wait(m->ctx->stream));
-    return 0;
-}
-
-// Where each batch's triangles sit in this shard's soup: after k_mesh every work item's look-back word holds
-// the inclusive prefix of the triangle counts up to and including it (ordered_base / publish_count).
-int sdf_mesh_batch_offsets(sdf_mesh *m, int64_t *h_out) {
-    if (!m || !h_out) return fail("sdf_mesh_batch_offsets: NULL argument");
-    MESH_READY(m);
-    const int64_t nb = m->st.n_batches;
-    for (int64_t b = 0; b <= nb; b++) h_out[b] = 0;
-    const int nw = m->work_end - m->work_begin;
-    if (nb == 0 || nw <= 0) return 0;
-    if (!m->status.p || !m->worklist.p) return fail("sdf_mesh_batch_offsets: this mesh was not produced by sdf_generate");
-    HIPCHK(set_device(m->ctx->device));
-    std::vector<int> wl((size_t)nw);
-    std::vector<unsigned long long> stw((size_t)nw);
-    HIPCHK(hipMemcpyAsync(wl.data(), (const int *)m->worklist.p + m->work_begin, (size_t)nw * 4, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(hipMemcpyAsync(stw.data(), (const unsigned long long *)m->status.p + m->work_begin, (size_t)nw * 8, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(stream_wait(m->ctx->stream));
-    // h_out[b + 1] = triangles of batch b for now; the running sum follows
-    unsigned long long prev = 0;
-    for (int i = 0; i < nw; i++) {
-        if ((stw[(size_t)i] >> 62) != 2ull) return fail("sdf_mesh_batch_offsets: a work item has no prefix (the meshing pass did not complete)");
-        const unsigned long long incl = stw[(size_t)i] & MESH_VAL_MASK;
-        if (incl < prev || wl[(size_t)i] < 0 || wl[(size_t)i] >= nb) return fail("sdf_mesh_batch_offsets: inconsistent look-back words");
-        h_out[wl[(size_t)i] + 1] = (int64_t)(incl - prev);
-        prev = incl;
-    }
-    for (int64_t b = 0; b < nb; b++) h_out[b + 1] += h_out[b];
-    return 0;
-}
-
-int sdf_mesh_adopt_soup(sdf_ctx *c, const void *d_soup, int64_t n_tris, sdf_mesh **out) {
-    if (!c || !out || n_tris < 0 || (n_tris > 0 && !d_soup)) return fail("sdf_mesh_adopt_soup: NULL argument or negative count");
-    *out = nullptr;
-    sdf_mesh *m = new sdf_mesh();
-    m->ctx = c;
-    m->emitted_to = const_cast<void *>(d_soup);
-    m->st.n_triangles = n_tris;
-    *out = m;
-    return 0;
-}
-
-int sdf_mesh_emit_stl_host(sdf_mesh *m, void *h_out) {
-    if (!m || !h_out) return fail("sdf_mesh_emit_stl_host: NULL argument");
-    MESH_READY(m);
-    const long long nt = m->st.n_triangles;
-    if (nt == 0) return 0;
-    MESH_SOUP_READY(m);
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    if (c->scratch_out.ensure((size_t)nt * 50)) return 1;
-    launch_k_stl(dim3((unsigned)((nt + 255) / 256)), dim3(256), c->stream, (const double *)mesh_soup(m), nt,
-                       (unsigned short *)c->scratch_out.p);
-    HIPCHK(hipGetLastError());
-    return copy_to_host(c, h_out, c->scratch_out.p, (size_t)nt * 50);
-}
-
-int sdf_mesh_weld(sdf_mesh *m, int64_t *n_unique) {
-    if (!m || !n_unique) return fail("sdf_mesh_weld: NULL argument");
-    MESH_READY(m);
-    MESH_SOUP_READY(m);
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    if (m->weld_n < 0) {
-        long long nu = 0;
-        const int rc = sdfk::weld_device(c->stream, (const double *)mesh_soup(m), 3ll * (long long)m->st.n_triangles, &m->weld_pts, &m->weld_inv, &nu);
-        if (rc) return fail(std::string("sdf_mesh_weld: ") + hipGetErrorString((hipError_t)rc));
-        m->weld_n = nu;
-    }
-    *n_unique = (int64_t)m->weld_n;
-    return 0;
-}
-
-int sdf_mesh_weld_fetch(sdf_mesh *m, double *h_points, int64_t *h_cells) {
-    if (!m || !h_points || !h_cells) return fail("sdf_mesh_weld_fetch: NULL argument");
-    if (m->weld_n < 0) return fail("sdf_mesh_weld_fetch: call sdf_mesh_weld first");
-    if (m->weld_n == 0) return 0;
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    HIPCHK(hipMemcpyAsync(h_points, m->weld_pts, (size_t)m->weld_n * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_cells, m->weld_inv, (size_t)m->st.n_triangles * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(stream_wait(c->stream));
-    return 0;
-}
-
-// ---- the indexed export: field normals at the welded vertices, binary PLY records ----
-static thread_local double g_normals_kernel_ms = 0.0;
-
-int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_normals, int64_t *n_flat) {
-    if (!m || !t || !n_flat) { fail("sdf_mesh_vertex_normals: NULL argument"); return 2; }
-    if (!(std::isfinite(eps) && eps > 0.0)) { fail("sdf_mesh_vertex_normals: eps must be finite and positive"); return 2; }
-    if (t->n_extern) { fail("sdf_mesh_vertex_normals: the tape reads user closures (L_EXTERN): take the normals over sdf_eval_points_extern_host"); return 2; }
-    if (m->weld_n < 0) { fail("sdf_mesh_vertex_normals: call sdf_mesh_weld first"); return 2; }
-    if (t->ctx != m->ctx) { fail("sdf_mesh_vertex_normals: the tape and the mesh belong to different contexts"); return 2; }
-    sdf_ctx *c = m->ctx;
-    const long long nu = m->weld_n;
-    *n_flat = 0;
-    if (nu == 0) { m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps; m->nrm_flat = 0; return 0; }
-    HIPCHK(set_device(c->device));
-    if (!(m->nrm_valid && m->nrm_model == t->content_hash && m->nrm_eps == eps)) {
-        m->nrm_valid = false;
-        if (!m->nrm) {
-            const hipError_t e = dev_malloc((void **)&m->nrm, (size_t)nu * 24 + 8);
-            if (e != hipSuccess) { m->nrm = nullptr; return fail(std::string("sdf_mesh_vertex_normals: hipMalloc(") + std::to_string((size_t)nu * 24 + 8) + "): " + hipGetErrorString(e)); }
-        }
-        unsigned long long *d_flat = reinterpret_cast<unsigned long long *>(m->nrm + 3 * nu);
-        unsigned long long flat = 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipMemsetAsync(d_flat, 0, 8, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-        if (e == hipSuccess) e = (hipError_t)sdfk::launch_vertex_normals(c->stream, t->d_code, t->d_c64, t->full, m->weld_pts, nu, eps, m->nrm, d_flat);
-        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&flat, d_flat, 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = stream_wait(c->stream);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) (void)stream_wait(c->stream);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e != hipSuccess) return fail(std::string("sdf_mesh_vertex_normals: ") + hipGetErrorString(e));
-        g_normals_kernel_ms = (double)ms;
-        m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps; m->nrm_flat = (long long)flat;
-    }
-    *n_flat = (int64_t)m->nrm_flat;
-    if (h_normals) return copy_to_host(c, h_normals, m->nrm, (size_t)nu * 24);
-    return 0;
-}
-
-double sdf_mesh_normals_last_kernel_ms(void) { return g_normals_kernel_ms; }
-
-int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
-    if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }
-    if (m->weld_n < 0) { fail("sdf_mesh_emit_ply_host: call sdf_mesh_weld first"); return 2; }
-    if (with_normals && !m->nrm_valid) { fail("sdf_mesh_emit_ply_host: with_normals needs a successful sdf_mesh_vertex_normals first"); return 2; }
-    const long long nu = m->weld_n, nt = (long long)m->st.n_triangles;
-    if (nu >= (1ll << 31)) { fail("sdf_mesh_emit_ply_host: 2^31 or more vertices: the face records hold 32-bit indices"); return 2; }
-    if (nu == 0 || nt == 0) return 0;
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    const int width = with_normals ? 6 : 3;
-    const size_t vbytes = (size_t)nu * 4 * (size_t)width, fbytes = (size_t)nt * 13, foff = (vbytes + 255) & ~(size_t)255;
-    char *base = nullptr;
-    hipError_t e = dev_malloc((void **)&base, foff + ((fbytes + 255) & ~(size_t)255));
-    if (e != hipSuccess) return fail(std::string("sdf_mesh_emit_ply_host: hipMalloc(") + std::to_string(foff + fbytes) + "): " + hipGetErrorString(e));
-    const long long nfl = nu * width;
-    launch_k_ply_vertices(dim3((unsigned)((nfl + 255) / 256)), dim3(256), c->stream, m->weld_pts, with_normals ? m->nrm : nullptr, nfl, width, (float *)base);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        launch_k_ply_faces(dim3((unsigned)((nt + 255) / 256)), dim3(256), c->stream, m->weld_inv, nt, (unsigned char *)(base + foff));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_vertices, base, vbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_faces, base + foff, fbytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t ew = stream_wait(c->stream);
-    if (e == hipSuccess) e = ew;
-    (void)hipFree(base);
-    if (e != hipSuccess) return fail(std::string("sdf_mesh_emit_ply_host: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// ---- pinned host memory for results ----
-// A device-to-host copy into fresh pageable memory runs at ~10 GB/s (page faults + the runtime's staging);
-// into pinned memory it runs at the link rate.  Pinning is expensive (tens of ms for 200 MB), so the
-// blocks are recycled: sdf_host_free hands a block back to a small free list, sdf_host_alloc takes the
-// smallest block there that is large enough (and not more than twice the request) before pinning new
-// memory.  The host side wraps a block as an ndarray whose owner frees it (sdf_amd/engine.py).
-struct HostBlock { void *p; size_t bytes; };
-static std::mutex g_host_mu;
-static std::vector<HostBlock> g_host_free, g_host_live;
-static size_t g_host_cached = 0;
-
-int sdf_host_alloc(size_t bytes, void **out) {
-    if (!out) return fail("sdf_host_alloc: NULL argument");
-    *out = nullptr;
-    const size_t want = std::max<size_t>((bytes + 4095) & ~(size_t)4095, 4096);
-    {
-        std::lock_guard<std::mutex> g(g_host_mu);
-        int best = -1;
-        for (size_t i = 0; i < g_host_free.size(); i++)
-            if (g_host_free[i].bytes >= want && g_host_free[i].bytes <= 2 * want &&
-                (best < 0 || g_host_free[i].bytes < g_host_free[(size_t)best].bytes))
-                best = (int)i;
-        if (best >= 0) {
-            const HostBlock b = g_host_free[(size_t)best];
-            g_host_free.erase(g_host_free.begin() + best);
-            g_host_cached -= b.bytes;
-            g_host_live.push_back(b);
-            *out = b.p;
-            return 0;
-        }
-    }
-    void *p = nullptr;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e != hipSuccess) {   // give the cached blocks back and retry once
-        std::vector<HostBlock> drop;
-        { std::lock_guard<std::mutex> g(g_host_mu); drop.swap(g_host_free); g_host_cached = 0; }
-        for (auto &b : drop) (void)hipHostFree(b.p);
-        e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    }
-    if (e != hipSuccess) return fail(std::string("hipHostMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
-    std::lock_guard<std::mutex> g(g_host_mu);
-    g_host_live.push_back({p, want});
-    *out = p;
-    return 0;
-}
-
-int sdf_host_free(void *p) {
-    if (!p) return 0;
-    HostBlock b{nullptr, 0};
-    std::vector<HostBlock> drop;
-    {
-        std::lock_guard<std::mutex> g(g_host_mu);
-        for (size_t i = 0; i < g_host_live.size(); i++)
-            if (g_host_live[i].p == p) { b = g_host_live[i]; g_host_live.erase(g_host_live.begin() + (long)i); break; }
-        if (!b.p) return fail("sdf_host_free: not a block of sdf_host_alloc");
-        g_host_free.push_back(b);
-        g_host_cached += b.bytes;
-        // keep at most 8 blocks / 2 GiB cached: the oldest go back to the system
-        while (g_host_free.size() > 8 || g_host_cached > ((size_t)2 << 30)) {
-            drop.push_back(g_host_free.front());
-            g_host_cached -= g_host_free.front().bytes;
-            g_host_free.erase(g_host_free.begin());
-        }
-    }
-    for (auto &d : drop) (void)hipHostFree(d.p);
-    return 0;
-}
-
-int sdf_mesh_kinds(sdf_mesh *m, uint8_t *h_out) {
-    if (!m || !h_out) return fail("sdf_mesh_kinds: NULL argument");
-    MESH_READY(m);
-    if (m->st.n_batches == 0) return 0;
-    HIPCHK(set_device(m->ctx->device));
-    HIPCHK(hipMemcpyAsync(h_out, m->kinds.p, (size_t)m->st.n_batches, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(stream_wait(m->ctx->stream));
-    for (int64_t i = 0; i < m->st.n_batches; i++) if (h_out[i] == 255) h_out[i] = 3;
-    return 0;
-}
-
-int sdf_mesh_prune_masks(sdf_mesh *m, uint32_t *h_out) {
-    if (!m || !h_out) return fail("sdf_mesh_prune_masks: NULL argument");
-    MESH_READY(m);
-    if (!m->pruned) return fail("sdf_mesh_prune_masks: this mesh was generated without the interval prepass");
-    const size_t n = (size_t)m->st.n_batches;
-    if (n == 0) return 0;
-    HIPCHK(set_device(m->ctx->device));
-    HIPCHK(hipMemcpyAsync(h_out, m->prune.p, n * 64, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(stream_wait(m->ctx->stream));
-    return 0;
-}
-
-int sdf_mesh_destroy(sdf_mesh *m) {
-    if (!m) return 0;
-    sdf_ctx *c = m->ctx;
-    (void)hipSetDevice(c->device);
-    (void)stream_wait(c->stream);
-    if (m->stream) (void)stream_wait(m->stream);        // (a call slot's lane)
-    if (m->pend.active) { c->slots[m->pend.got.slot].busy = false; c->slots[m->pend.got.slot].owner = nullptr; m->pend.active = false; }   // (abandoned; the stream is idle now)
-    if (m->out.p) {   // keep one soup buffer around for the next call
-        if (c->arena_pool.empty()) c->arena_pool.push_back(m->out);
-        else if (c->arena_pool.back().bytes < m->out.bytes) { c->arena_pool.back().release(); c->arena_pool.back() = m->out; }
-        else m->out.release();
-        m->out.p = nullptr; m->out.bytes = 0;
-    }
-    if (m->counters.p) { c->counter_pool.push_back(m->counters); m->counters.p = nullptr; m->counters.bytes = 0; }
-    for (DevBuf *b : {&m->axes, &m->kinds, &m->worklist, &m->status, &m->prune, &m->tapes, &m->cull, &m->order, &m->desc, &m->cellrecs, &m->trilist, &m->blockidx, &m->slab}) b->release();
-    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv); (void)hipFree(m->nrm);
-    delete m;
-    return 0;
-}
-
 }  // extern "C"
-
-#include "sdf_comm.inc"

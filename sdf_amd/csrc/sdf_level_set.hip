@@ -26,7 +26,8 @@
 
 #include <algorithm>
 #include <string>
-#include <vector>
+
+#include "sdf_internal.h"
 
 namespace sdfk {
 
@@ -262,27 +263,24 @@ __global__ __launch_bounds__(256) void k_ls_crop(const float *__restrict__ val, 
     out[s] = val[((unsigned long long)(c0 + i) * g.n[1] + (c1 + j)) * g.n[2] + (c2 + k)];
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int refuse(const std::string &why) { fail("sdf_mesh_level_set_host: " + why); return 2; }
 
-// the work grid of a validated mesh (all points finite, vs > 0): floor(min / vs) - hw - 1 .. ceil(max / vs) + hw + 1 per axis,
-// and the device memory one call needs; returns false (with a message) when the grid cannot be indexed
-static bool plan(const double *pts, long long np, long long nt, double vs, int hw, LsGrid &g, size_t &bytes, std::string &err) {
+// the work grid of a validated mesh (all points finite, vs > 0): floor(min / vs) - hw - 1 .. ceil(max / vs) + hw + 1 per axis;
+// refuses (2, with a message) a grid that cannot be indexed
+static int plan(const double *pts, long long np, double vs, int hw, LsGrid &g) {
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (long long p = 0; p < np; p++)
         for (int a = 0; a < 3; a++) { mn[a] = std::min(mn[a], pts[3 * p + a]); mx[a] = std::max(mx[a], pts[3 * p + a]); }
     double nvox = 1.0;
     for (int a = 0; a < 3; a++) {
         const double lo = floor(mn[a] / vs) - hw - 1, hi = ceil(mx[a] / vs) + hw + 1;
-        if (!(fabs(lo) < 4.5e15 && fabs(hi) < 4.5e15) || hi - lo + 1 > 2147483647.0) {
-            err = "work grid axis " + std::to_string(a) + " spans " + std::to_string(hi - lo + 1) + " voxels: voxel size too small for this mesh";
-            return false;
-        }
+        if (!(fabs(lo) < 4.5e15 && fabs(hi) < 4.5e15) || hi - lo + 1 > 2147483647.0)
+            return refuse("work grid axis " + std::to_string(a) + " spans " + std::to_string(hi - lo + 1) + " voxels: voxel size too small for this mesh");
         g.lo[a] = (long long)lo;
         g.n[a] = (int)(hi - lo + 1);
         nvox *= hi - lo + 1;
     }
-    if (nvox > 4.0e12) { err = "work grid of " + std::to_string(nvox) + " voxels: voxel size too small for this mesh"; return false; }
-    const size_t n = (size_t)g.n[0] * g.n[1] * g.n[2];
+    if (nvox > 4.0e12) return refuse("work grid of " + std::to_string(nvox) + " voxels: voxel size too small for this mesh");
     g.nw = (g.n[2] + 31) / 32;
     g.vs = vs;
     g.bg = (float)(hw * vs);
@@ -290,74 +288,63 @@ static bool plan(const double *pts, long long np, long long nt, double vs, int h
     // the margin only adds voxels whose result is the background anyway)
     g.reach = (double)g.bg * (1.0 + 1e-9) + vs * 1e-9;
     g.skip_d2 = (double)g.bg * (double)g.bg * (1.0 + 1e-9);
-    bytes = align256(n * 8) + align256(n * 4) + align256((size_t)g.n[0] * g.n[1] * g.nw * 4) + align256((size_t)np * 24) +
-            align256((size_t)nt * 12) + 256;
-    return true;
+    return 0;
 }
 
-#define LSCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); rc = 1; goto done; } } while (0)
+}  // namespace sdfk
 
-// 0: done (dims reported; h_out filled when it holds them), 1: HIP error, 2: invalid arguments (nothing uploaded); `err` says why
-int level_set_host(hipStream_t st, const double *h_pts, long long np, const int32_t *h_tris, long long nt, double vs, int hw,
-                   int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, long long cap, std::string &err) {
+using namespace sdfk;
+
+// 0: done (dims reported; h_out filled when it holds them), 1: HIP error, 2: invalid arguments (nothing uploaded); sdf_last_error says why
+extern "C" int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t np, const int32_t *h_tris, int64_t nt, double vs, int hw,
+                                       int64_t out_ijk0[3], int64_t out_dims[3], float *h_out, int64_t cap) {
+    if (!c || !out_ijk0 || !out_dims) return fail("sdf_mesh_level_set_host: NULL argument");
+    HIPCHK(set_device(c->device));
+    hipStream_t st = c->stream;
     for (int a = 0; a < 3; a++) { out_ijk0[a] = 0; out_dims[a] = 0; }
-    if (np <= 0 || nt <= 0 || !h_pts || !h_tris) { err = "empty mesh: no points or no triangles"; return 2; }
-    if (!(vs > 0.0) || !std::isfinite(vs)) { err = "voxel size must be a positive finite number"; return 2; }
-    if (hw < 1 || hw > (1 << 20)) { err = "half width must be 1 .. 2^20 voxels"; return 2; }
-    if (np > (1ll << 31) || nt > (1ll << 31) / 3) { err = "mesh too large for 32-bit indices"; return 2; }
+    if (np <= 0 || nt <= 0 || !h_pts || !h_tris) return refuse("empty mesh: no points or no triangles");
+    if (!(vs > 0.0) || !std::isfinite(vs)) return refuse("voxel size must be a positive finite number");
+    if (hw < 1 || hw > (1 << 20)) return refuse("half width must be 1 .. 2^20 voxels");
+    if (np > (1ll << 31) || nt > (1ll << 31) / 3) return refuse("mesh too large for 32-bit indices");
     for (long long i = 0; i < 3 * np; i++)
-        if (!std::isfinite(h_pts[i])) { err = "point " + std::to_string(i / 3) + " is not finite"; return 2; }
+        if (!std::isfinite(h_pts[i])) return refuse("point " + std::to_string(i / 3) + " is not finite");
     for (long long i = 0; i < 3 * nt; i++)
-        if (h_tris[i] < 0 || h_tris[i] >= np) {
-            err = "triangle " + std::to_string(i / 3) + " indexes point " + std::to_string(h_tris[i]) + " of " + std::to_string(np);
-            return 2;
-        }
+        if (h_tris[i] < 0 || h_tris[i] >= np)
+            return refuse("triangle " + std::to_string(i / 3) + " indexes point " + std::to_string(h_tris[i]) + " of " + std::to_string((long long)np));
     LsGrid g = {};
-    size_t bytes = 0;
-    if (!plan(h_pts, np, nt, vs, hw, g, bytes, err)) return 2;
-    size_t free_b = 0, total_b = 0;
-    {
-        const hipError_t e = hipMemGetInfo(&free_b, &total_b);
-        if (e != hipSuccess) { err = std::string("hipMemGetInfo: ") + hipGetErrorString(e); return 1; }
-    }
-    if (bytes > free_b / 10 * 9) {
-        err = "work grid " + std::to_string(g.n[0]) + " x " + std::to_string(g.n[1]) + " x " + std::to_string(g.n[2]) + " needs " +
-              std::to_string(bytes) + " bytes of device memory, " + std::to_string(free_b) + " are free";
-        return 2;
-    }
+    if (plan(h_pts, np, vs, hw, g)) return 2;
     const size_t n = (size_t)g.n[0] * g.n[1] * g.n[2], ncol = (size_t)g.n[0] * g.n[1];
-    const size_t o_val = align256(n * 8), o_mask = o_val + align256(n * 4), o_pts = o_mask + align256(ncol * g.nw * 4);
-    const size_t o_tris = o_pts + align256((size_t)np * 24), o_box = o_tris + align256((size_t)nt * 12);
-    const int box_init[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
-    int box[6] = {};
-    char *base = nullptr;
-    int rc = 0;
     unsigned long long *d2;
     float *val;
     unsigned *mask;
     double *pts;
     int *tris, *dbox;
+    Scratch scratch(st);
+    scratch.part(&d2, n); scratch.part(&val, n); scratch.part(&mask, ncol * g.nw);
+    scratch.part(&pts, (size_t)np * 3); scratch.part(&tris, (size_t)nt * 3); scratch.part(&dbox, 6);
+    size_t free_b = 0;
+    bool fits = false;
+    HIPCHK_FN(mem_fits(scratch.bytes, &fits, &free_b));
+    if (!fits)
+        return refuse("work grid " + std::to_string(g.n[0]) + " x " + std::to_string(g.n[1]) + " x " + std::to_string(g.n[2]) + " needs " +
+                      std::to_string(scratch.bytes) + " bytes of device memory, " + std::to_string(free_b) + " are free");
+    const int box_init[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
+    int box[6] = {};
     const unsigned tri_blocks = (unsigned)((nt + 3) / 4);
-    LSCHK(hipMalloc((void **)&base, bytes));
-    d2 = (unsigned long long *)base;
-    val = (float *)(base + o_val);
-    mask = (unsigned *)(base + o_mask);
-    pts = (double *)(base + o_pts);
-    tris = (int *)(base + o_tris);
-    dbox = (int *)(base + o_box);
-    LSCHK(hipMemcpyAsync(pts, h_pts, (size_t)np * 24, hipMemcpyHostToDevice, st));
-    LSCHK(hipMemcpyAsync(tris, h_tris, (size_t)nt * 12, hipMemcpyHostToDevice, st));
-    LSCHK(hipMemcpyAsync(dbox, box_init, sizeof box_init, hipMemcpyHostToDevice, st));
-    LSCHK(hipMemsetAsync(d2, 0xff, n * 8, st));            // (all ones: above every non-negative double -> no triangle in reach)
-    LSCHK(hipMemsetAsync(mask, 0, ncol * g.nw * 4, st));
-    hipLaunchKernelGGL(k_ls_dist, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, nt, g, d2);
-    hipLaunchKernelGGL(k_ls_sign, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, nt, g, mask);
+    HIPCHK_FN(scratch.alloc());
+    HIPCHK_FN(hipMemcpyAsync(pts, h_pts, (size_t)np * 24, hipMemcpyHostToDevice, st));
+    HIPCHK_FN(hipMemcpyAsync(tris, h_tris, (size_t)nt * 12, hipMemcpyHostToDevice, st));
+    HIPCHK_FN(hipMemcpyAsync(dbox, box_init, sizeof box_init, hipMemcpyHostToDevice, st));
+    HIPCHK_FN(hipMemsetAsync(d2, 0xff, n * 8, st));            // (all ones: above every non-negative double -> no triangle in reach)
+    HIPCHK_FN(hipMemsetAsync(mask, 0, ncol * g.nw * 4, st));
+    hipLaunchKernelGGL(k_ls_dist, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, (long long)nt, g, d2);
+    hipLaunchKernelGGL(k_ls_sign, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, (long long)nt, g, mask);
     hipLaunchKernelGGL(k_ls_parity, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, mask, (long long)ncol, g.nw);
     hipLaunchKernelGGL(k_ls_compose, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, st, (const unsigned long long *)d2,
                        (const unsigned *)mask, g, val, dbox);
-    LSCHK(hipGetLastError());
-    LSCHK(hipMemcpyAsync(box, dbox, sizeof box, hipMemcpyDeviceToHost, st));
-    LSCHK(hipStreamSynchronize(st));
+    HIPCHK_FN(hipGetLastError());
+    HIPCHK_FN(hipMemcpyAsync(box, dbox, sizeof box, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(stream_wait(st));
     if (box[3] >= 0) {
         long long m = 1;
         for (int a = 0; a < 3; a++) {
@@ -369,15 +356,10 @@ int level_set_host(hipStream_t st, const double *h_pts, long long np, const int3
             float *out = (float *)d2;                           // (the squared distances are consumed: the crop goes there)
             hipLaunchKernelGGL(k_ls_crop, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float *)val, g, box[0], box[1], box[2],
                                (int)out_dims[1], (int)out_dims[2], m, out);
-            LSCHK(hipGetLastError());
-            LSCHK(hipMemcpyAsync(h_out, out, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-            LSCHK(hipStreamSynchronize(st));
+            HIPCHK_FN(hipGetLastError());
+            HIPCHK_FN(hipMemcpyAsync(h_out, out, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK_FN(stream_wait(st));
         }
     }
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    if (base) (void)hipFree(base);
-    return rc;
+    return 0;
 }
-
-}  // namespace sdfk

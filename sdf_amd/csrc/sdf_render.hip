@@ -15,7 +15,7 @@
 #include <string>
 
 #include "sdf_interp.h"
-#include "sdf_render.h"
+#include "sdf_internal.h"
 
 using namespace sdfk;
 
@@ -110,28 +110,29 @@ __global__ __launch_bounds__(256) void k_render(const uint32_t *__restrict__ cod
     status_out[p] = is_hit ? 1 : 0;
 }
 
-static size_t render_align256(size_t n) { return (n + 255) & ~(size_t)255; }
+static thread_local double g_render_kernel_ms = 0.0;
 
-namespace sdfk {
-
-#define RENDERCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); rc = 1; goto done; } } while (0)
-
-// 0: done, 1: HIP error, 2: refused (nothing allocated, nothing launched); `err` says why
-int render_host(hipStream_t st, const uint32_t *d_code, const double *d_consts, bool full, const double *frame18, int width, int height,
-                const double *params5, int max_steps, int refine, double *h_depth, double *h_normal, int32_t *h_steps, uint8_t *h_status,
-                double *kernel_ms, std::string &err) {
-    if (!d_code || !d_consts || !frame18 || !params5 || !h_depth || !h_normal || !h_steps || !h_status) { err = "NULL argument"; return 2; }
-    if (width < 1 || height < 1) { err = "empty image: " + std::to_string(width) + " x " + std::to_string(height); return 2; }
-    if ((long long)width * height > (1ll << 26)) { err = "image of " + std::to_string(width) + " x " + std::to_string(height) + ": more than 2^26 pixels"; return 2; }
-    if (max_steps < 1) { err = "max_steps must be at least 1"; return 2; }
-    if (refine < 0) { err = "refine must not be negative"; return 2; }
-    for (int i = 0; i < 18; i++) if (!std::isfinite(frame18[i])) { err = "the ray frame is not finite"; return 2; }
-    for (int i = 0; i < 5; i++) if (!std::isfinite(params5[i])) { err = "the march parameters are not finite"; return 2; }
+// 0: done, 1: HIP error, 2: refused (nothing allocated, nothing launched); sdf_last_error says why.  One device allocation, freed
+// before it returns; sdf_render_last_kernel_ms: the kernel alone, by HIP events on the context's stream.
+extern "C" int sdf_render_host(sdf_tape *t, const double *frame18, int width, int height, const double *params5, int max_steps, int refine,
+                               double *h_depth, double *h_normal, int32_t *h_steps, uint8_t *h_status) {
+    auto refuse = [](const std::string &why) { fail("sdf_render_host: " + why); return 2; };
+    if (!t) return refuse("NULL argument");
+    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip");
+    HIPCHK(set_device(t->ctx->device));
+    hipStream_t st = t->ctx->stream;
+    if (!t->d_code || !t->d_c64 || !frame18 || !params5 || !h_depth || !h_normal || !h_steps || !h_status) return refuse("NULL argument");
+    if (width < 1 || height < 1) return refuse("empty image: " + std::to_string(width) + " x " + std::to_string(height));
+    if ((long long)width * height > (1ll << 26)) return refuse("image of " + std::to_string(width) + " x " + std::to_string(height) + ": more than 2^26 pixels");
+    if (max_steps < 1) return refuse("max_steps must be at least 1");
+    if (refine < 0) return refuse("refine must not be negative");
+    for (int i = 0; i < 18; i++) if (!std::isfinite(frame18[i])) return refuse("the ray frame is not finite");
+    for (int i = 0; i < 5; i++) if (!std::isfinite(params5[i])) return refuse("the march parameters are not finite");
     const double t_near = params5[0], t_far = params5[1], hit_eps = params5[2], step_scale = params5[3], normal_eps = params5[4];
-    if (!(hit_eps > 0.0)) { err = "hit_eps must be positive"; return 2; }
-    if (!(normal_eps > 0.0)) { err = "normal_eps must be positive"; return 2; }
-    if (!(step_scale > 0.0 && step_scale <= 1.0)) { err = "step_scale must lie in (0, 1]"; return 2; }
-    if (t_far < t_near) { err = "t_far lies before t_near"; return 2; }
+    if (!(hit_eps > 0.0)) return refuse("hit_eps must be positive");
+    if (!(normal_eps > 0.0)) return refuse("normal_eps must be positive");
+    if (!(step_scale > 0.0 && step_scale <= 1.0)) return refuse("step_scale must lie in (0, 1]");
+    if (t_far < t_near) return refuse("t_far lies before t_near");
 
     RenderArgs a;
     for (int i = 0; i < 3; i++) {
@@ -143,37 +144,26 @@ int render_host(hipStream_t st, const uint32_t *d_code, const double *d_consts, 
     a.tiles_x = (width + 7) / 8;
     a.n_tiles = a.tiles_x * ((height + 7) / 8);                        // (at most 2^26 pixels: below 2^27 tiles even for a one-pixel-wide image)
     const size_t n = (size_t)width * (size_t)height;
-    const size_t o_normal = render_align256(n * 8), o_steps = o_normal + render_align256(n * 24), o_status = o_steps + render_align256(n * 4), bytes = o_status + render_align256(n);
-    char *base = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = 0;
-    float ms = 0.f;
     double *depth, *normal;
     int32_t *steps;
     uint8_t *status;
+    Scratch scratch(st);
+    scratch.part(&depth, n); scratch.part(&normal, 3 * n); scratch.part(&steps, n); scratch.part(&status, n);
+    EventTimer timer;
     const unsigned grid = (unsigned)((a.n_tiles + 3) / 4);
-    RENDERCHK(hipMalloc((void **)&base, bytes));
-    depth = (double *)base; normal = (double *)(base + o_normal); steps = (int32_t *)(base + o_steps); status = (uint8_t *)(base + o_status);
-    RENDERCHK(hipEventCreate(&e0));
-    RENDERCHK(hipEventCreate(&e1));
-    RENDERCHK(hipEventRecord(e0, st));
-    if (full) hipLaunchKernelGGL((k_render<double, true>), dim3(grid), dim3(256), 0, st, d_code, d_consts, a, depth, normal, steps, status);
-    else hipLaunchKernelGGL((k_render<double, false>), dim3(grid), dim3(256), 0, st, d_code, d_consts, a, depth, normal, steps, status);
-    RENDERCHK(hipGetLastError());
-    RENDERCHK(hipEventRecord(e1, st));
-    RENDERCHK(hipMemcpyAsync(h_depth, depth, n * 8, hipMemcpyDeviceToHost, st));
-    RENDERCHK(hipMemcpyAsync(h_normal, normal, n * 24, hipMemcpyDeviceToHost, st));
-    RENDERCHK(hipMemcpyAsync(h_steps, steps, n * 4, hipMemcpyDeviceToHost, st));
-    RENDERCHK(hipMemcpyAsync(h_status, status, n, hipMemcpyDeviceToHost, st));
-    RENDERCHK(hipStreamSynchronize(st));
-    RENDERCHK(hipEventElapsedTime(&ms, e0, e1));
-    if (kernel_ms) *kernel_ms = (double)ms;
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (base) (void)hipFree(base);
-    return rc;
+    HIPCHK_FN(scratch.alloc());
+    HIPCHK_FN(timer.start(st));
+    if (t->full) hipLaunchKernelGGL((k_render<double, true>), dim3(grid), dim3(256), 0, st, (const uint32_t *)t->d_code, (const double *)t->d_c64, a, depth, normal, steps, status);
+    else hipLaunchKernelGGL((k_render<double, false>), dim3(grid), dim3(256), 0, st, (const uint32_t *)t->d_code, (const double *)t->d_c64, a, depth, normal, steps, status);
+    HIPCHK_FN(hipGetLastError());
+    HIPCHK_FN(timer.stop(st));
+    HIPCHK_FN(hipMemcpyAsync(h_depth, depth, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_normal, normal, n * 24, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_steps, steps, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_status, status, n, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(stream_wait(st));
+    HIPCHK_FN(timer.ms(&g_render_kernel_ms));
+    return 0;
 }
 
-}  // namespace sdfk
+extern "C" double sdf_render_last_kernel_ms(void) { return g_render_kernel_ms; }

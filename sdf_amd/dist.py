@@ -184,7 +184,7 @@ def _all_gather(td, g, mine, group, world, sb, async_op):
         return td.all_gather([g[r * sb:(r + 1) * sb] for r in range(world)], mine, group=group, async_op=async_op)
 
 
-# ---- the native path: RCCL called from inside the library (csrc/sdf_comm.inc) ----
+# ---- the native path: RCCL called from inside the library (csrc/sdf_comm.hip) ----
 _COMMS = {}      # (engine id, group id) -> engine.Comm
 _NATIVE_BROKEN = []   # why the native path was given up in this process (empty: it was not)
 
@@ -276,7 +276,7 @@ def submit_sharded(eng, tape, X, Y, Z, batch_size, sparse, device=None, group=No
     waiting for any of it; `collect_sharded` finishes the step.  Steps submitted on different `lane`s (0 / 1) run on
     streams of their own, so step i + 1's meshing overlaps step i's collective.
 
-    On GPUs under the "nccl" backend the step runs INSIDE the library (csrc/sdf_comm.inc: ncclAllGather called from
+    On GPUs under the "nccl" backend the step runs INSIDE the library (csrc/sdf_comm.hip: ncclAllGather called from
     there, persistent buffers, no interpreter between submit and collect; SDF_DIST_NATIVE=0 keeps the torch.distributed
     path below, which is also what every other backend / engine uses).  The soup of a native step lives in library
     memory and stays valid until the next step is submitted on the same lane."""

@@ -1,5 +1,5 @@
 // mock_rccl.cpp -- TEST INFRASTRUCTURE: a stand-in for librccl's five entry points that libsdf_hip.so uses
-// (csrc/sdf_comm.inc: ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather / ncclGetErrorString), so
+// (csrc/sdf_comm.hip: ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather / ncclGetErrorString), so
 // that the library's own multi-GPU step can be driven by SEVERAL PROCESSES ON ONE GPU.  (RCCL itself refuses two
 // ranks on one device; the boxes this repository is built on have one.)  The ranks meet in a POSIX shared-memory
 // segment named by the "unique id"; an all-gather synchronises the caller's stream, copies the rank's piece to its

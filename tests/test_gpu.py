@@ -377,7 +377,7 @@ def test_generate_to_device_matches_host_path(ns, eng):
 @pytest.mark.parametrize('driver', ['native', 'native-sharded-skip', 'torch'])
 def test_sharded_generate_over_rccl_single_rank(driver, ns, eng, monkeypatch):
     """the multi-GPU code path with a one-rank `nccl` process group must reproduce the plain path bit for bit:
-    `native` = the exchange step inside the library (csrc/sdf_comm.inc: ncclAllGather through the dlopen'ed librccl,
+    `native` = the exchange step inside the library (csrc/sdf_comm.hip: ncclAllGather through the dlopen'ed librccl,
     persistent buffers, the default under nccl); `native-sharded-skip` = the same with the skip test shared out and its
     verdicts all-gathered (SDF_SKIP_SHARD_MIN: every grid takes that path); `torch` = sdf_amd/dist.py's protocol through
     torch.distributed (SDF_DIST_NATIVE=0: what other backends and engines use)"""
@@ -439,7 +439,7 @@ def test_sharded_generate_over_rccl_single_rank(driver, ns, eng, monkeypatch):
 
 
 def test_skip_test_in_pieces_and_generate_from_its_verdicts(ns, eng):
-    """what the ranks of a sharded step do between them (csrc/sdf_comm.inc): each runs `_skip` for a share of the
+    """what the ranks of a sharded step do between them (csrc/sdf_comm.hip): each runs `_skip` for a share of the
     batches (sdf_skip_kinds), the one-byte verdicts are gathered, and every rank meshes its share of the work list
     from them (sdf_generate_from_kinds).  Here one device plays the three ranks: the assembled verdicts must equal the
     plain call's classification and the soups must be the plain call's, whole and in shards"""
@@ -478,7 +478,7 @@ def test_bench_two_ranks_on_one_device_exchange_slabs_between_processes(driver, 
     itself), both ranks on THIS device (RCCL refuses two ranks on one GPU, so torch's own collectives go over gloo), the
     slabs kept in device memory.  `torch-gloo`: two real processes run sdf_amd.dist's device side --
     sdf_generate_compact_async into a slab, the all-gather, sdf_expand_slabs on the step's own stream; `native-mock-rccl`:
-    the step inside the library (csrc/sdf_comm.inc, what N > 1 runs under nccl) with tests/native/mock_rccl.cpp standing
+    the step inside the library (csrc/sdf_comm.hip, what N > 1 runs under nccl) with tests/native/mock_rccl.cpp standing
     in for librccl.  Rank 0's line must carry the reference's soup hash."""
     import json
     import shutil
@@ -1751,7 +1751,7 @@ def _native_exchange_worker(rank, world, port, q, mock, skip_shard, first_cap):
 @pytest.mark.parametrize('world,skip_shard,first_cap', [(2, False, 0), (3, True, 0), (2, True, 700)],
                          ids=['2-ranks', '3-ranks-sharded-skip', '2-ranks-sharded-skip-tiny-first-capacity'])
 def test_native_exchange_between_processes_on_one_device(world, skip_shard, first_cap, tmp_path):
-    """The library's OWN multi-GPU step (csrc/sdf_comm.inc: sdf_generate_sharded_async / sdf_exchange_wait -- shards of
+    """The library's OWN multi-GPU step (csrc/sdf_comm.hip: sdf_generate_sharded_async / sdf_exchange_wait -- shards of
     the work list, skip test shared out and its verdicts gathered, slabs, expansion, capacity hints, the retry every
     rank takes on the same gathered headers, two lanes) between several real processes.  RCCL refuses two ranks on one
     GPU, so the five RCCL entry points the library dlopens are provided by tests/native/mock_rccl.cpp (shared-memory
