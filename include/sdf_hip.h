@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 14
+#define SDF_ABI_VERSION 15
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -371,6 +371,40 @@ double sdf_mesh_normals_last_kernel_ms(void);
  * NULL argument, a mesh that is not welded, with_normals without normals, 2^31 or more vertices.  One device allocation, freed
  * before it returns. */
 int sdf_mesh_emit_ply_host(sdf_mesh *mesh, int with_normals, void *h_vertices, void *h_faces);
+/* The mesh measured on the device (ABI 15; DESIGN.md section 4g, defined by tests/measure_ref.py and reproduced bit for bit).
+ * sdf_mesh_moments streams the float64 soup once (after one pass for its bounding box) and returns RAW totals over the triangles
+ * (A, B, C), taken relative to a reference point o: a = A - o, b = B - o, c = C - o, n = (b - a) x (c - a), det = a . (b x c),
+ * s = a + b + c.  sums[0] = sum |n| (twice the area), sums[1] = sum det (six times the volume), sums[2..4] = sum det s_k (24 times
+ * the first moments about o), sums[5..10] = sum det (a_i a_j + b_i b_j + c_i c_j + s_i s_j) for ij = xx, yy, zz, xy, xz, yz (120
+ * times the second moments about o).  Every multiply and add is rounded separately, and the sums run through a fixed tree (chunks
+ * of 1024 triangles, 256 lanes, halving): the totals depend on the order of the triangles and on nothing else.  origin = 3 doubles,
+ * or NULL for the midpoint of the bounding box, lo + (hi - lo) / 2 ((0, 0, 0) for an empty box); the point used comes back in
+ * `origin`.  A triangle with a non-finite vertex adds +0.0 to every sum, is left out of the box and is counted in n_nonfinite;
+ * n_zero_area counts the others whose |n| is 0.  A zero of the box is +0.0; an empty box (no triangles, or none finite) is
+ * lo = +inf, hi = -inf.  Needs no weld; serves every mesh that has (or can make) a soup on the device, adopted ones included.
+ * One device allocation, freed before it returns.  A NULL mesh or out returns 2, other failures 1. */
+typedef struct sdf_moments {
+    double sums[11];
+    double origin[3];
+    double box_lo[3], box_hi[3];
+    int64_t n_triangles, n_zero_area, n_nonfinite;
+} sdf_moments;
+int sdf_mesh_moments(sdf_mesh *mesh, const double *origin, sdf_moments *out);
+/* The edge census of the welded mesh (cells of sdf_mesh_weld): a cell with two equal indices is COLLAPSED (counted, no edges);
+ * every other cell gives three directed half-edges, and an undirected edge is PAIRED (two uses, opposite directions), BOUNDARY
+ * (one use), MISORIENTED (two uses, one direction) or NONMANIFOLD (three or more uses).  edges = the sum of the four, faces =
+ * T - collapsed, vertices = n_unique, euler = vertices - edges + faces, closed = (boundary == 0 and nonmanifold == 0), oriented =
+ * (misoriented == 0).  One kernel for the keys, one library radix sort over 3T 64-bit keys, one kernel for the classes; one device
+ * allocation (48 bytes per triangle + the sort's), freed before it returns.  Refused on the host before anything is allocated or
+ * launched, with return value 2: a NULL argument, a mesh that is not welded, 3T >= 2^31 or 2^31 or more vertices.  Other failures
+ * return 1. */
+typedef struct sdf_edge_census {
+    int64_t vertices, faces, collapsed, edges, paired, boundary, misoriented, nonmanifold, euler, closed, oriented;
+} sdf_edge_census;
+int sdf_mesh_edge_census(sdf_mesh *mesh, sdf_edge_census *out);
+/* the kernels of this thread's last sdf_mesh_moments or sdf_mesh_edge_census alone (box + moments + partials; keys + sort +
+ * classes), milliseconds by HIP events (tools/measure_time.py) */
+double sdf_mesh_measure_last_kernel_ms(void);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -158,8 +158,8 @@ def generate(
     callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512).  (`_stl=True` is what `save` uses for .stl files: the soup
     stays on the device and the 50-byte STL records come back instead of the points; `_weld=True` is
     what `save` uses for every other format: the soup is welded on the device and the indexed mesh
-    (unique points, cells) comes back; `_export` is what `generate_mesh` and the native PLY / OBJ writers of `save` use: see
-    `_export_mesh`.)"""
+    (unique points, cells) comes back; `_export` is what `generate_mesh`, `measure` and the native PLY / OBJ writers of `save`
+    use: see `_export_mesh`.)"""
 
     from . import engine, dist
     start = time.time()
@@ -259,6 +259,9 @@ def _export_mesh(mesh, tape, want):
     or None), `n_flat` and -- want['ply']: the device-packed PLY body `ply` = (vertex_bytes, face_bytes); otherwise `points`,
     `cells` of the weld"""
     out = {'normals': None, 'n_flat': 0}
+    if want.get('measure'):          # (`measure`: nothing but the totals and the counts leaves the device)
+        import importlib
+        return {'measure': importlib.import_module(__package__ + '.measure').measure_mesh(mesh, want.get('origin'))}
     if want.get('normals'):
         out['normals'], out['n_flat'] = mesh.vertex_normals(tape, want['eps'])
     if want.get('ply'):
@@ -280,6 +283,9 @@ def _export_host(eng, tape, welded, want):
     """the same for a soup that was gathered and welded on the host (multi-process runs): the normals come from the
     definition over eval_points, the PLY body from the host packer"""
     from . import meshfile
+    if want.get('measure'):
+        raise NotImplementedError('measure: the soup of this multi-process run was gathered on the host; the measurements are made '
+                                  'on the device only (run it in one process, or with a device-resident exchange)')
     pts, cells = welded
     out = {'points': pts, 'cells': cells, 'normals': None, 'n_flat': 0, 'n_vertices': len(pts), 'n_faces': len(cells)}
     if want.get('normals'):

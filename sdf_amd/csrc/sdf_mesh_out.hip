@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals at the welded vertices,
-// binary PLY records, kinds, prune masks, and the end of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h
-// and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// binary PLY records, the moments and the edge census, kinds, prune masks, and the end of a mesh.  Launches only through the launchers
+// of sdf_plain.h, sdf_normals.h, sdf_measure.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -9,6 +9,7 @@
 
 #include "sdf_internal.h"
 #include "sdf_expand_host.h"   // (+ <chrono>, <cstring>, <mutex>, <thread>)
+#include "sdf_measure.h"
 #include "sdf_normals.h"
 #include "sdf_plain.h"
 
@@ -344,6 +345,36 @@ int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_norm
 }
 
 double sdf_mesh_normals_last_kernel_ms(void) { return g_normals_kernel_ms; }
+
+// ---- the mesh measured on the device: moments of the soup, edge census of the welded cells ----
+static thread_local double g_measure_kernel_ms = 0.0;
+
+int sdf_mesh_moments(sdf_mesh *m, const double *origin, sdf_moments *out) {
+    if (!m || !out) { fail("sdf_mesh_moments: NULL argument"); return 2; }
+    MESH_READY(m);
+    *out = sdf_moments();
+    for (int k = 0; k < 3; k++) { out->origin[k] = origin ? origin[k] : 0.0; out->box_lo[k] = INFINITY; out->box_hi[k] = -INFINITY; }
+    if (m->st.n_triangles == 0) return 0;
+    MESH_SOUP_READY(m);
+    HIPCHK(set_device(m->ctx->device));
+    return measure_moments(m->ctx->stream, (const double *)mesh_soup(m), (long long)m->st.n_triangles, origin, out, &g_measure_kernel_ms);
+}
+
+int sdf_mesh_edge_census(sdf_mesh *m, sdf_edge_census *out) {
+    if (!m || !out) { fail("sdf_mesh_edge_census: NULL argument"); return 2; }
+    if (m->weld_n < 0) { fail("sdf_mesh_edge_census: call sdf_mesh_weld first"); return 2; }
+    const long long nt = (long long)m->st.n_triangles;
+    if (3 * nt >= (1ll << 31) || m->weld_n >= (1ll << 31)) { fail("sdf_mesh_edge_census: 2^31 or more half-edges or vertices"); return 2; }
+    *out = sdf_edge_census();
+    out->vertices = (int64_t)m->weld_n;
+    out->euler = out->vertices;
+    out->closed = out->oriented = 1;
+    if (nt == 0) return 0;
+    HIPCHK(set_device(m->ctx->device));
+    return measure_edge_census(m->ctx->stream, m->weld_inv, nt, m->weld_n, out, &g_measure_kernel_ms);
+}
+
+double sdf_mesh_measure_last_kernel_ms(void) { return g_measure_kernel_ms; }
 
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
     if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }

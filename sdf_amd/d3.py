@@ -72,6 +72,10 @@ class SDF3(SDFBase):
         from . import core
         return core.generate_mesh(self, *args, **kwargs)
 
+    def measure(self, *args, **kwargs):
+        import importlib
+        return importlib.import_module(__package__ + '.measure').measure(self, *args, **kwargs)
+
     def render(self, path=None, **kwargs):
         import importlib
         return importlib.import_module(__package__ + '.render').render(self, path, **kwargs)

@@ -38,6 +38,21 @@ class SdfExchangeStats(ctypes.Structure):
                [('per_rank_triangles', ctypes.c_int64 * 64)]
 
 
+class SdfMoments(ctypes.Structure):
+    """mirror of `sdf_moments` in include/sdf_hip.h"""
+    _fields_ = [('sums', ctypes.c_double * 11), ('origin', ctypes.c_double * 3), ('box_lo', ctypes.c_double * 3),
+                ('box_hi', ctypes.c_double * 3), ('n_triangles', _c_i64), ('n_zero_area', _c_i64), ('n_nonfinite', _c_i64)]
+
+
+CENSUS_FIELDS = ('vertices', 'faces', 'collapsed', 'edges', 'paired', 'boundary', 'misoriented', 'nonmanifold', 'euler', 'closed',
+                 'oriented')
+
+
+class SdfEdgeCensus(ctypes.Structure):
+    """mirror of `sdf_edge_census` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in CENSUS_FIELDS]
+
+
 class SdfStats(ctypes.Structure):
     """mirror of `sdf_stats` in include/sdf_hip.h"""
     _fields_ = [
@@ -142,13 +157,16 @@ ABI = {
     'sdf_mesh_vertex_normals': (ctypes.c_int, [_vp, _vp, ctypes.c_double, _f64p, ctypes.POINTER(ctypes.c_int64)]),
     'sdf_mesh_normals_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_emit_ply_host': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    'sdf_mesh_moments': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(SdfMoments)]),
+    'sdf_mesh_edge_census': (ctypes.c_int, [_vp, ctypes.POINTER(SdfEdgeCensus)]),
+    'sdf_mesh_measure_last_kernel_ms': (ctypes.c_double, []),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def build_info():
@@ -438,6 +456,42 @@ class Mesh:
             raise ValueError(eng.lib.sdf_last_error().decode())
         _check(eng.lib, rc)
         return vb, fb
+
+    def moments(self, origin=None):
+        """the raw moments of the soup, summed on the device (sdf_mesh_moments, csrc/sdf_measure.hip; defined
+        by tests/measure_ref.py and reproduced bit for bit): a dict of `sums` (11 float64: sum |n|, sum det, 3 first-moment and 6
+        second-moment totals about `origin`), `origin` (3,), `box` (2, 3) and the counts `triangles`, `zero_area`, `nonfinite`.
+        origin=None takes the midpoint of the bounding box.  `measure.derive` turns the totals into volume, area, centroid and
+        inertia.  Needs no weld."""
+        eng = self.engine
+        o = None
+        if origin is not None:
+            o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+            if o.shape != (3,):
+                raise ValueError('origin must have 3 components, got %r' % (origin,))
+        out = SdfMoments()
+        rc = eng.lib.sdf_mesh_moments(self.handle, _dp(o, _f64p) if o is not None else None, ctypes.byref(out))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        return {'sums': np.array(out.sums[:], np.float64), 'origin': np.array(out.origin[:], np.float64),
+                'box': np.array([out.box_lo[:], out.box_hi[:]], np.float64), 'triangles': int(out.n_triangles),
+                'zero_area': int(out.n_zero_area), 'nonfinite': int(out.n_nonfinite)}
+
+    def edge_census(self):
+        """the edge census of the welded mesh, counted on the device (sdf_mesh_edge_census; welds first if that has not happened):
+        a dict of the integers `vertices`, `faces`, `collapsed`, `edges`, `paired`, `boundary`, `misoriented`, `nonmanifold`,
+        `euler` and the booleans `closed`, `oriented` (tests/measure_ref.py defines them)"""
+        eng = self.engine
+        self._welded()
+        out = SdfEdgeCensus()
+        rc = eng.lib.sdf_mesh_edge_census(self.handle, ctypes.byref(out))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        d = {k: int(getattr(out, k)) for k in CENSUS_FIELDS}
+        d['closed'], d['oriented'] = bool(d['closed']), bool(d['oriented'])
+        return d
 
     def stl_records(self):
         """T x 50-byte binary STL records (normals computed on the device)"""

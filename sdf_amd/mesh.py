@@ -96,6 +96,12 @@ class Mesh:
         points, cells = np.unique(rec['points'].reshape(-1, 3).astype(np.float64), axis=0, return_inverse=True)
         return cls(points, np.asarray(cells).reshape((-1, 3)))
 
+    def measure(self, origin=None):
+        """volume, area, centroid, inertia and the edge census of this mesh, taken on the device (sdf_amd/measure.py)"""
+        import importlib
+        soup = np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)]
+        return importlib.import_module(__package__ + '.measure').measure_soup(soup, origin)
+
     @property
     def bounding_box(self):
         lo, hi = self.points.min(axis=0), self.points.max(axis=0)
