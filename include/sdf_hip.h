@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 15
+#define SDF_ABI_VERSION 16
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -405,6 +405,41 @@ int sdf_mesh_edge_census(sdf_mesh *mesh, sdf_edge_census *out);
 /* the kernels of this thread's last sdf_mesh_moments or sdf_mesh_edge_census alone (box + moments + partials; keys + sort +
  * classes), milliseconds by HIP events (tools/measure_time.py) */
 double sdf_mesh_measure_last_kernel_ms(void);
+/* The connected shells of the welded mesh (ABI 16; DESIGN.md section 4h, defined by tests/components_ref.py and reproduced exactly).
+ * Every cell joins its three welded indices -- a collapsed cell (a, a, b) joins a and b like any other --, the LABEL of a vertex is
+ * the smallest welded index of its connected component, and the shells are numbered 0 .. K - 1 by ascending label, that is by their
+ * lexicographically smallest vertex.  vertex_shell[v] is the shell of welded vertex v, triangle_shell[t] the shell of the first
+ * vertex of cell t; per shell: its triangles, its vertices and the bounding box of its vertices (a zero reads +0.0).  The result is
+ * a function of the cells alone: nothing in it depends on launch geometry, timing or the order of atomics.
+ * sdf_mesh_components welds first if that has not happened, labels on the device (a 32-bit parent word per vertex: root hooking by
+ * compare-and-swap, compression, and a verifying pass over every cell behind a kernel boundary -- `rounds` counts the passes, at most
+ * ceil(log2(max(V, 2))) + 2), numbers the roots with a library scan and takes the counts and boxes with integer atomics.  It serves
+ * generated meshes, meshes of sdf_generate_records and adopted soups.  The arrays stay on the device in one block of the mesh's own
+ * until it is destroyed; a second call reuses them.  One scratch allocation, freed before it returns.  A mesh of 0 triangles has 0
+ * shells, and nothing is launched.  ms_label / ms_number: the kernels of the labelling (with the host's look at the counter between
+ * the rounds) and of numbering + counts + boxes of the call that computed, by HIP events.  Refused with return value 2: a NULL
+ * argument, 2^31 or more triangles or vertices.  Other failures return 1. */
+typedef struct sdf_components {
+    int64_t n_shells, n_vertices, n_triangles, rounds;
+    double ms_label, ms_number;
+} sdf_components;
+int sdf_mesh_components(sdf_mesh *mesh, sdf_components *out);
+/* ... copied out: h_vertex_shell n_vertices x int32, h_triangle_shell n_triangles x int32, h_triangles and h_vertices n_shells x
+ * int64, h_bounds n_shells x 2 x 3 float64 (lo x, y, z, hi x, y, z).  Any pointer may be NULL.  Return value 2: a NULL mesh, a mesh
+ * that has not been through sdf_mesh_components. */
+int sdf_mesh_components_fetch(sdf_mesh *mesh, int32_t *h_vertex_shell, int32_t *h_triangle_shell, int64_t *h_triangles,
+                              int64_t *h_vertices, double *h_bounds);
+/* A new mesh of the triangles whose shell k has h_keep[k] != 0, in soup order, bit for bit (a flag per triangle, a library scan, one
+ * copy kernel).  The new mesh OWNS its soup, which goes back to the library's pool when it is destroyed; for every reader it is what
+ * an adopted soup is (sdf_mesh_emit_stl_host, sdf_mesh_weld, sdf_mesh_emit_ply_host, sdf_mesh_vertex_normals, sdf_mesh_moments,
+ * sdf_mesh_edge_census, sdf_mesh_emit_host*, and sdf_mesh_components itself).  The source mesh stays valid and unchanged.  Keeping
+ * nothing gives a mesh of 0 triangles without a launch.  Refused on the host before anything is allocated or launched, with return
+ * value 2: a NULL argument, a mesh that has not been through sdf_mesh_components, n_keep != n_shells.  Other failures return 1, and
+ * *out is NULL. */
+int sdf_mesh_select_shells(sdf_mesh *mesh, const unsigned char *h_keep, int64_t n_keep, sdf_mesh **out);
+/* the kernels of this thread's last sdf_mesh_components that computed (labelling + numbering + counts) or sdf_mesh_select_shells
+ * (flags + scan + copy) alone, milliseconds by HIP events (tools/shells_time.py) */
+double sdf_mesh_components_last_kernel_ms(void);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

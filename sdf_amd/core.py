@@ -152,16 +152,23 @@ def generate(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, _stl=False, _weld=False, _export=None):
+        verbose=True, sparse=True, _stl=False, _weld=False, _export=None, _keep=None):
     """reference sdf/core.py:84-150.  `batch_size` up to 512 (the reference takes any: a larger one is refused with a message; up
     to 32 runs the fused kernels, above that the batches go through device memory -- a model with user closures then hands its
     callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512).  (`_stl=True` is what `save` uses for .stl files: the soup
     stays on the device and the 50-byte STL records come back instead of the points; `_weld=True` is
     what `save` uses for every other format: the soup is welded on the device and the indexed mesh
     (unique points, cells) comes back; `_export` is what `generate_mesh`, `measure` and the native PLY / OBJ writers of `save`
-    use: see `_export_mesh`.)"""
+    use: see `_export_mesh`; `_keep` is their `keep=`: the device mesh is split into its connected shells, the shells that
+    `shells.resolve_keep` names are compacted into a mesh of their own, and that SELECTION goes through the same three paths --
+    DESIGN.md section 4h.)"""
 
     from . import engine, dist
+    if _keep is not None:
+        import importlib
+        if not (_stl or _weld or _export is not None):
+            raise ValueError('keep= goes with save, generate_mesh and measure')
+        importlib.import_module(__package__ + '.shells').check_keep(_keep)      # (before anything is meshed)
     start = time.time()
     eng = engine.get_engine()
     tape = eng.tape_for(sdf)
@@ -199,17 +206,23 @@ def generate(
             torch.cuda.current_stream(soup.device).synchronize()
             mesh = eng.adopt_soup(soup.data_ptr(), soup.numel() // 9)
             try:
-                if _stl:
+                if _keep is not None:
+                    records, welded, exported, points = _read_kept(mesh, tape, _keep, _stl, _export)
+                elif _stl:
                     records = mesh.stl_records()
                 elif _export is not None:
                     exported = _export_mesh(mesh, tape, _export)
                 else:
                     welded = mesh.weld()
-                points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
+                if _keep is None:
+                    points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
             finally:
                 mesh.close()
             del soup
         else:
+            if _keep is not None:
+                raise NotImplementedError('keep: the soup of this multi-process run was gathered on the host; shells are found and '
+                                          'selected on the device only (run it in one process, or with a device-resident exchange)')
             points = soup.cpu().numpy().reshape(-1, 3)
     else:
         # (the soup is wanted on the host: it travels as 16-byte records and `workers` host threads make the float64
@@ -217,7 +230,9 @@ def generate(
         mesh = eng.generate(tape, X, Y, Z, batch_size, sparse, records=not (_stl or _weld))
         try:
             stats = mesh.stats()
-            if _stl:
+            if _keep is not None:
+                records, welded, exported, points = _read_kept(mesh, tape, _keep, _stl, _export)
+            elif _stl:
                 records = mesh.stl_records()
                 points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
             elif _export is not None:
@@ -251,6 +266,28 @@ def generate(
 
 
 generate.last_stats = None
+
+
+def _read_kept(mesh, tape, keep, _stl, _export):
+    """`generate` with keep=: the shells of the device mesh are labelled, the kept ones compacted into a mesh of their own
+    (shells.resolve_keep, Mesh.select), and the selection is read like any device mesh: its STL records, its export or its weld.
+    Returns (records, welded, exported, points) as `generate` holds them.  Choosing by size brings the per-shell counts over the
+    link and nothing else; a callable is handed the whole `Shells`."""
+    import importlib
+    shells = importlib.import_module(__package__ + '.shells')
+    got = shells.shells_of_mesh(mesh) if callable(keep) else mesh.shell_summary()['triangles']
+    sel = mesh.select(shells.resolve_keep(keep, got))
+    try:
+        records = welded = exported = None
+        if _stl:
+            records = sel.stl_records()
+        elif _export is not None:
+            exported = _export_mesh(sel, tape, _export)
+        else:
+            welded = sel.weld()
+        return records, welded, exported, np.empty((3 * sel.n_triangles, 0))
+    finally:
+        sel.close()
 
 
 def _export_mesh(mesh, tape, want):
@@ -295,12 +332,15 @@ def _export_host(eng, tape, welded, want):
     return out
 
 
-def generate_mesh(sdf, normals=False, normal_eps=None, **generate_kwargs):
+def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, **generate_kwargs):
     """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
     welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
     difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
     value).  The normals point outward for this library's winding; a vertex where the field has no gradient gets (0, 0, 0)
-    (`generate_mesh.last_flat` counts them).  Not in the reference."""
+    (`generate_mesh.last_flat` counts them).  keep: only these connected shells of the mesh (`shells.resolve_keep`: 'largest', a
+    count, a boolean mask over the shells, a callable).  Not in the reference."""
+    if keep is not None:
+        generate_kwargs['_keep'] = keep
     got = generate(sdf, _export={'normals': bool(normals), 'eps': normal_eps}, **generate_kwargs)
     generate_mesh.last_flat = got['n_flat']
     return got['points'], got['cells'], got['normals']
@@ -309,12 +349,16 @@ def generate_mesh(sdf, normals=False, normal_eps=None, **generate_kwargs):
 generate_mesh.last_flat = 0
 
 
-def save(path, *args, normals=False, normal_eps=None, writer=None, **kwargs):
+def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
-    'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native."""
+    'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
+    these connected shells of the mesh -- 'largest', the n largest, a boolean mask over the shells, a callable (`shells.resolve_keep`;
+    DESIGN.md section 4h) --, selected on the device before anything is written."""
     from . import meshfile
     path = os.fspath(path)
+    if keep is not None:
+        kwargs['_keep'] = keep
     how = meshfile.choose_writer(path, writer, normals)
     if how == 'native':
         ply = path.lower().endswith('.ply')

@@ -141,6 +141,12 @@ struct sdf_mesh {
     unsigned long long nrm_model = 0;
     double nrm_eps = 0.0;
     long long nrm_flat = 0;
+    // sdf_mesh_components: the shells of the welded mesh -- per vertex, per triangle, the counts and the boxes -- in one block of its
+    // own (sdf_components.h ShellParts; dev_malloc, freed with the mesh); n_shells >= 0: labelled, a second call reuses them
+    void *shells = nullptr;
+    long long n_shells = -1;
+    int shell_rounds = 0;
+    double shell_ms[2] = {0.0, 0.0};
     // sdf_generate_records: the triangles were written as 16-byte records into a slab of the library's (sdf_slab.h); the float64 soup
     // is made on the host threads (sdf_mesh_emit_host_workers) or, for the readers that want it on the device, by k_expand on demand
     bool records = false;

@@ -34,14 +34,6 @@ constexpr int MOMENT_CHUNK = 1024;                 // triangles per chunk (tests
 constexpr int BOX_MAX_BLOCKS = 1024;                 // workgroups that stride over the soup (k_soup_box) or the keys (k_edge_classes)
 constexpr unsigned long long EDGE_COLLAPSED = ~0ull;
 
-// float64 -> u64 whose unsigned order is the float order; both zeros give the key of +0.0
-__device__ __forceinline__ unsigned long long box_key(double v) {
-    if (v == 0.0) v = 0.0;
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __host__ __forceinline__ unsigned long long box_bits(unsigned long long k) { return (k >> 63) ? (k & ~(1ull << 63)) : ~k; }
-
 // triangles [t0, t0 + cnt) of the soup into LDS, contiguous: 16-byte loads where the soup's base allows them
 template <bool WIDE>
 __device__ __forceinline__ void stage_tile(const double *__restrict__ soup, long long t0, int cnt, double *tile) {

@@ -1,13 +1,14 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals at the welded vertices,
-// binary PLY records, the moments and the edge census, kinds, prune masks, and the end of a mesh.  Launches only through the launchers
-// of sdf_plain.h, sdf_normals.h, sdf_measure.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// binary PLY records, the moments and the edge census, the connected shells and a selection of them, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 #include "sdf_internal.h"
+#include "sdf_components.h"
 #include "sdf_expand_host.h"   // (+ <chrono>, <cstring>, <mutex>, <thread>)
 #include "sdf_measure.h"
 #include "sdf_normals.h"
@@ -376,6 +377,88 @@ int sdf_mesh_edge_census(sdf_mesh *m, sdf_edge_census *out) {
 
 double sdf_mesh_measure_last_kernel_ms(void) { return g_measure_kernel_ms; }
 
+// ---- the connected shells of the welded mesh, and a selection of them as a mesh of its own ----
+static thread_local double g_components_kernel_ms = 0.0;
+
+int sdf_mesh_components(sdf_mesh *m, sdf_components *out) {
+    if (!m || !out) { fail("sdf_mesh_components: NULL argument"); return 2; }
+    MESH_READY(m);
+    *out = sdf_components();
+    int64_t nu = 0;
+    if (sdf_mesh_weld(m, &nu)) return 1;
+    const long long nt = (long long)m->st.n_triangles;
+    if (nt >= (1ll << 31) || m->weld_n >= (1ll << 31)) { fail("sdf_mesh_components: 2^31 or more triangles or vertices"); return 2; }
+    out->n_vertices = (int64_t)m->weld_n;
+    out->n_triangles = (int64_t)nt;
+    if (nt == 0) { m->n_shells = 0; return 0; }
+    if (m->n_shells < 0) {
+        HIPCHK(set_device(m->ctx->device));
+        long long k = 0;
+        if (components_label(m->ctx->stream, m->weld_inv, m->weld_pts, nt, m->weld_n, &m->shells, &k, &m->shell_rounds, m->shell_ms)) return 1;
+        m->n_shells = k;
+        g_components_kernel_ms = m->shell_ms[0] + m->shell_ms[1];
+    }
+    out->n_shells = (int64_t)m->n_shells;
+    out->rounds = (int64_t)m->shell_rounds;
+    out->ms_label = m->shell_ms[0];
+    out->ms_number = m->shell_ms[1];
+    return 0;
+}
+
+int sdf_mesh_components_fetch(sdf_mesh *m, int32_t *h_vertex_shell, int32_t *h_triangle_shell, int64_t *h_triangles, int64_t *h_vertices,
+                              double *h_bounds) {
+    if (!m) { fail("sdf_mesh_components_fetch: NULL argument"); return 2; }
+    if (m->n_shells < 0) { fail("sdf_mesh_components_fetch: call sdf_mesh_components first"); return 2; }
+    if (m->n_shells == 0) return 0;
+    static const char who[] = "sdf_mesh_components_fetch: ";
+    sdf_ctx *c = m->ctx;
+    const long long k = m->n_shells, nt = (long long)m->st.n_triangles;
+    const ShellParts sp = shell_parts(m->shells, m->weld_n, nt, k);
+    std::vector<unsigned long long> keys(h_bounds ? (size_t)(6 * k) : 0);
+    HIPCHK(set_device(c->device));
+    if (h_vertex_shell) HIPCHK_MSG(who, hipMemcpyAsync(h_vertex_shell, sp.vertex_shell, (size_t)m->weld_n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_triangle_shell) HIPCHK_MSG(who, hipMemcpyAsync(h_triangle_shell, sp.triangle_shell, (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_triangles) HIPCHK_MSG(who, hipMemcpyAsync(h_triangles, sp.triangles, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_vertices) HIPCHK_MSG(who, hipMemcpyAsync(h_vertices, sp.vertices, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_bounds) HIPCHK_MSG(who, hipMemcpyAsync(keys.data(), sp.box, (size_t)k * 48, hipMemcpyDeviceToHost, c->stream));
+    const hipError_t e = stream_wait(c->stream);                      // (before `keys` goes, whatever the copies said)
+    HIPCHK_MSG(who, e);
+    if (h_bounds) shell_bounds(keys.data(), k, h_bounds);
+    return 0;
+}
+
+int sdf_mesh_select_shells(sdf_mesh *m, const unsigned char *h_keep, int64_t n_keep, sdf_mesh **out) {
+    if (!m || !out || (n_keep > 0 && !h_keep)) { fail("sdf_mesh_select_shells: NULL argument"); return 2; }
+    *out = nullptr;
+    if (m->n_shells < 0) { fail("sdf_mesh_select_shells: call sdf_mesh_components first"); return 2; }
+    if (n_keep != (int64_t)m->n_shells) {
+        fail("sdf_mesh_select_shells: the mask has " + std::to_string((long long)n_keep) + " entries, the mesh has " + std::to_string(m->n_shells) + " shells");
+        return 2;
+    }
+    bool any = false;
+    for (int64_t k = 0; k < n_keep; k++) any = any || h_keep[k] != 0;
+    DevBuf soup;                                                       // the selection's own soup: the new mesh's `out`
+    long long kept = 0;
+    if (any) {                                                         // (keeping nothing: a mesh of 0 triangles, no launch)
+        MESH_SOUP_READY(m);
+        HIPCHK(set_device(m->ctx->device));
+        const ShellParts sp = shell_parts(m->shells, m->weld_n, (long long)m->st.n_triangles, m->n_shells);
+        if (components_select(m->ctx->stream, (const double *)mesh_soup(m), (long long)m->st.n_triangles, sp.triangle_shell, h_keep, m->n_shells,
+                              &soup, &kept, &g_components_kernel_ms)) {
+            soup.release();
+            return 1;
+        }
+    }
+    sdf_mesh *sel = new sdf_mesh();                                    // (like an adopted soup for every reader, but it owns the soup:
+    sel->ctx = m->ctx;                                                 // `out` goes back to the pool with the mesh)
+    sel->out = soup;
+    sel->st.n_triangles = (int64_t)kept;
+    *out = sel;
+    return 0;
+}
+
+double sdf_mesh_components_last_kernel_ms(void) { return g_components_kernel_ms; }
+
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
     if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }
     if (m->weld_n < 0) { fail("sdf_mesh_emit_ply_host: call sdf_mesh_weld first"); return 2; }
@@ -443,7 +526,7 @@ int sdf_mesh_destroy(sdf_mesh *m) {
     }
     if (m->counters.p) { c->counter_pool.push_back(m->counters); m->counters.p = nullptr; m->counters.bytes = 0; }
     for (DevBuf *b : {&m->axes, &m->kinds, &m->worklist, &m->status, &m->prune, &m->tapes, &m->cull, &m->order, &m->desc, &m->cellrecs, &m->trilist, &m->blockidx, &m->slab}) b->release();
-    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv); (void)hipFree(m->nrm);
+    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv); (void)hipFree(m->nrm); (void)hipFree(m->shells);
     delete m;
     return 0;
 }

@@ -76,6 +76,14 @@ class SDF3(SDFBase):
         import importlib
         return importlib.import_module(__package__ + '.measure').measure(self, *args, **kwargs)
 
+    def shells(self, **kwargs):
+        import importlib
+        return importlib.import_module(__package__ + '.shells').shells(self, **kwargs)
+
+    def measure_shells(self, *args, **kwargs):
+        import importlib
+        return importlib.import_module(__package__ + '.shells').measure_shells(self, *args, **kwargs)
+
     def render(self, path=None, **kwargs):
         import importlib
         return importlib.import_module(__package__ + '.render').render(self, path, **kwargs)

@@ -53,6 +53,12 @@ class SdfEdgeCensus(ctypes.Structure):
     _fields_ = [(k, _c_i64) for k in CENSUS_FIELDS]
 
 
+class SdfComponents(ctypes.Structure):
+    """mirror of `sdf_components` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in ('n_shells', 'n_vertices', 'n_triangles', 'rounds')] + \
+               [(k, ctypes.c_double) for k in ('ms_label', 'ms_number')]
+
+
 class SdfStats(ctypes.Structure):
     """mirror of `sdf_stats` in include/sdf_hip.h"""
     _fields_ = [
@@ -160,13 +166,18 @@ ABI = {
     'sdf_mesh_moments': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(SdfMoments)]),
     'sdf_mesh_edge_census': (ctypes.c_int, [_vp, ctypes.POINTER(SdfEdgeCensus)]),
     'sdf_mesh_measure_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_components': (ctypes.c_int, [_vp, ctypes.POINTER(SdfComponents)]),
+    'sdf_mesh_components_fetch': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _f64p]),
+    'sdf_mesh_select_shells': (ctypes.c_int, [_vp, _u8p, _c_i64, ctypes.POINTER(_vp)]),
+    'sdf_mesh_components_last_kernel_ms': (ctypes.c_double, []),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def build_info():
@@ -492,6 +503,67 @@ class Mesh:
         d = {k: int(getattr(out, k)) for k in CENSUS_FIELDS}
         d['closed'], d['oriented'] = bool(d['closed']), bool(d['oriented'])
         return d
+
+    def _labelled(self):
+        """the `sdf_components` of this mesh; labels (and welds) on the device if that has not happened yet"""
+        eng = self.engine
+        out = SdfComponents()
+        rc = eng.lib.sdf_mesh_components(self.handle, ctypes.byref(out))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        return out
+
+    def components(self):
+        """the connected shells of the welded mesh, labelled on the device (sdf_mesh_components, csrc/sdf_components.hip; DESIGN.md
+        section 4h; defined by tests/components_ref.py and reproduced exactly): a dict of `count` K, `rounds` (the passes the
+        labelling took, the verifying one included), `vertex_shell` (U,) int32, `triangle_shell` (T,) int32 and per shell
+        `triangles` (K,) int64, `vertices` (K,) int64, `bounds` (K, 2, 3) float64.  Shells are numbered by their lexicographically
+        smallest vertex.  The arrays stay on the device with the mesh: a second call only copies them."""
+        eng = self.engine
+        c = self._labelled()
+        k, i32p, i64p = int(c.n_shells), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_c_i64)
+        out = {'count': k, 'rounds': int(c.rounds),
+               'vertex_shell': pinned_empty(eng.lib, (int(c.n_vertices),), np.int32),
+               'triangle_shell': pinned_empty(eng.lib, (int(c.n_triangles),), np.int32),
+               'triangles': np.empty(k, np.int64), 'vertices': np.empty(k, np.int64), 'bounds': np.empty((k, 2, 3), np.float64)}
+        if k:
+            rc = eng.lib.sdf_mesh_components_fetch(self.handle, _dp(out['vertex_shell'], i32p), _dp(out['triangle_shell'], i32p),
+                                                   _dp(out['triangles'], i64p), _dp(out['vertices'], i64p), _dp(out['bounds'], _f64p))
+            if rc == 2:
+                raise ValueError(eng.lib.sdf_last_error().decode())
+            _check(eng.lib, rc)
+        return out
+
+    def shell_summary(self):
+        """`components()` without the per-vertex and per-triangle arrays: `count`, `rounds`, `triangles`, `vertices`, `bounds` --
+        all that choosing shells by size needs to bring over the link"""
+        eng = self.engine
+        c = self._labelled()
+        k, i64p = int(c.n_shells), ctypes.POINTER(_c_i64)
+        out = {'count': k, 'rounds': int(c.rounds), 'triangles': np.empty(k, np.int64), 'vertices': np.empty(k, np.int64),
+               'bounds': np.empty((k, 2, 3), np.float64)}
+        if k:
+            _check(eng.lib, eng.lib.sdf_mesh_components_fetch(self.handle, None, None, _dp(out['triangles'], i64p),
+                                                              _dp(out['vertices'], i64p), _dp(out['bounds'], _f64p)))
+        return out
+
+    def select(self, keep_mask):
+        """a new Mesh of the triangles whose shell is kept (keep_mask: K booleans, one per shell of `components()`), in soup order,
+        bit for bit, compacted on the device (sdf_mesh_select_shells).  The selection owns its soup and serves every reader --
+        points, stl_records, weld, ply_records, vertex_normals, moments, edge_census, components; this mesh stays valid.  A mask
+        of another length raises ValueError before any launch; an all-False mask gives a mesh of 0 triangles."""
+        eng = self.engine
+        mask = np.ascontiguousarray(np.asarray(keep_mask).reshape(-1) != 0, dtype=np.uint8)
+        self._labelled()
+        h = _vp()
+        rc = eng.lib.sdf_mesh_select_shells(self.handle, _dp(mask, _u8p), len(mask), ctypes.byref(h))
+        if rc == 2:
+            raise ValueError(eng.lib.sdf_last_error().decode())
+        _check(eng.lib, rc)
+        m = Mesh(eng, h)
+        m.emitted = False
+        return m
 
     def stl_records(self):
         """T x 50-byte binary STL records (normals computed on the device)"""

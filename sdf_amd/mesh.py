@@ -102,6 +102,12 @@ class Mesh:
         soup = np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)]
         return importlib.import_module(__package__ + '.measure').measure_soup(soup, origin)
 
+    def shells(self):
+        """the connected shells of this mesh (sdf_amd/shells.py `Shells`), labelled on the device.  The soup is welded there again:
+        `vertex_shell` is over THAT weld's vertices (lexicographic order), `triangle_shell` over this mesh's triangles"""
+        import importlib
+        return importlib.import_module(__package__ + '.shells').shells_of_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)])
+
     @property
     def bounding_box(self):
         lo, hi = self.points.min(axis=0), self.points.max(axis=0)
