@@ -18,6 +18,8 @@ Differences a caller can observe:
   sharded over the ranks and the triangle buffers all-gathered (sdf_amd/dist.py), so
   every rank still returns the complete soup in reference order.
 """
+import collections
+import contextlib
 import multiprocessing
 import os
 import time
@@ -148,27 +150,26 @@ def grid_axes(bounds, step=None, samples=SAMPLES):
     return X, Y, Z, (dx, dy, dz)
 
 
-def generate(
+Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', 'bounds', 'stats'))
+Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=), or None when a multi-process
+run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape, engine, bounds, stats: the call's."""
+
+
+@contextlib.contextmanager
+def meshed(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, _stl=False, _weld=False, _export=None, _keep=None):
-    """reference sdf/core.py:84-150.  `batch_size` up to 512 (the reference takes any: a larger one is refused with a message; up
-    to 32 runs the fused kernels, above that the batches go through device memory -- a model with user closures then hands its
-    callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512).  (`_stl=True` is what `save` uses for .stl files: the soup
-    stays on the device and the 50-byte STL records come back instead of the points; `_weld=True` is
-    what `save` uses for every other format: the soup is welded on the device and the indexed mesh
-    (unique points, cells) comes back; `_export` is what `generate_mesh`, `measure` and the native PLY / OBJ writers of `save`
-    use: see `_export_mesh`; `_keep` is their `keep=`: the device mesh is split into its connected shells, the shells that
-    `shells.resolve_keep` names are compacted into a mesh of their own, and that SELECTION goes through the same three paths --
-    DESIGN.md section 4h.)"""
-
+        verbose=True, sparse=True, *, keep=None, to_host=False):
+    """the one path from a model to its mesh on the device: the arguments of `generate`, `keep` (only these
+    connected shells, `shells.resolve_keep`: the device mesh is labelled, the kept shells are compacted into a mesh of their own
+    and THAT is yielded; section 4h) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
+    16-byte records).  Yields a `Meshed`, which the readers below take; closes what it opened on the way out, and after a body
+    that did not raise prints the two closing lines of the reference and sets `generate.last_stats`."""
     from . import engine, dist
-    if _keep is not None:
-        import importlib
-        if not (_stl or _weld or _export is not None):
-            raise ValueError('keep= goes with save, generate_mesh and measure')
-        importlib.import_module(__package__ + '.shells').check_keep(_keep)      # (before anything is meshed)
+    if keep is not None:
+        from .shells import check_keep, resolve_keep, shells_of_mesh
+        check_keep(keep)      # (before anything is meshed)
     start = time.time()
     eng = engine.get_engine()
     tape = eng.tape_for(sdf)
@@ -191,145 +192,127 @@ def generate(
         num_samples = overlapped(len(X)) * overlapped(len(Y)) * overlapped(len(Z))
         print('%d samples in %d batches with %d workers' % (num_samples, num_batches, workers))
 
-    records = welded = exported = None
-    if _export is not None:
-        _weld = True
-        if _export.get('normals') and _export.get('eps') is None:
-            # (the preview's value, render.render_buffers: a file and a preview of one model show the same normals)
-            lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
-            _export = dict(_export, eps=1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2))
-    if dist.world_size() > 1:
-        soup, stats = dist.generate_sharded_device(eng, tape, X, Y, Z, batch_size, sparse)
-        if (_stl or _weld) and getattr(soup, 'is_cuda', False) and hasattr(eng, 'adopt_soup'):
-            # the gathered soup stays on the device: STL records / the weld are made there, as for one GPU
-            import torch
-            torch.cuda.current_stream(soup.device).synchronize()
-            mesh = eng.adopt_soup(soup.data_ptr(), soup.numel() // 9)
-            try:
-                if _keep is not None:
-                    records, welded, exported, points = _read_kept(mesh, tape, _keep, _stl, _export)
-                elif _stl:
-                    records = mesh.stl_records()
-                elif _export is not None:
-                    exported = _export_mesh(mesh, tape, _export)
-                else:
-                    welded = mesh.weld()
-                if _keep is None:
-                    points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
-            finally:
-                mesh.close()
-            del soup
+    mesh = points = soup = None
+    try:
+        if dist.world_size() > 1:
+            soup, stats = dist.generate_sharded_device(eng, tape, X, Y, Z, batch_size, sparse)
+            if not to_host and getattr(soup, 'is_cuda', False):
+                # the gathered soup stays on the device (and alive, as `soup`, while the mesh over it is read)
+                import torch
+                torch.cuda.current_stream(soup.device).synchronize()
+                mesh = eng.adopt_soup(soup.data_ptr(), soup.numel() // 9)
+            else:
+                points = soup.cpu().numpy().reshape(-1, 3)
         else:
-            if _keep is not None:
+            mesh = eng.generate(tape, X, Y, Z, batch_size, sparse, records=to_host)
+            stats = mesh.stats()
+        if keep is not None:
+            if mesh is None:
                 raise NotImplementedError('keep: the soup of this multi-process run was gathered on the host; shells are found and '
                                           'selected on the device only (run it in one process, or with a device-resident exchange)')
-            points = soup.cpu().numpy().reshape(-1, 3)
-    else:
-        # (the soup is wanted on the host: it travels as 16-byte records and `workers` host threads make the float64
-        # rows from them -- the one place the reference's `workers=` still means something here)
-        mesh = eng.generate(tape, X, Y, Z, batch_size, sparse, records=not (_stl or _weld))
-        try:
-            stats = mesh.stats()
-            if _keep is not None:
-                records, welded, exported, points = _read_kept(mesh, tape, _keep, _stl, _export)
-            elif _stl:
-                records = mesh.stl_records()
-                points = np.empty((3 * mesh.n_triangles, 0))     # only its length is used below
-            elif _export is not None:
-                exported = _export_mesh(mesh, tape, _export)
-                points = np.empty((3 * mesh.n_triangles, 0))
-            elif _weld:
-                welded = mesh.weld()
-                points = np.empty((3 * mesh.n_triangles, 0))
-            else:
-                points = mesh.points(min(int(workers), 32) if workers else 0)
-        finally:
+            # (choosing by size brings the per-shell counts over the link and nothing else; a callable is handed the whole `Shells`)
+            got = shells_of_mesh(mesh) if callable(keep) else mesh.shell_summary()['triangles']
+            sel = mesh.select(resolve_keep(keep, got))
+            mesh.close()
+            mesh = sel
+        yield Meshed(mesh, points, tape, eng, bounds, stats)
+        triangles = mesh.n_triangles if mesh is not None else len(points) // 3
+    finally:
+        if mesh is not None:
             mesh.close()
 
     if verbose:
         print('%d skipped, %d empty, %d nonempty' % (stats['skipped'], stats['empty'], stats['nonempty']))
-        triangles = len(points) // 3
         seconds = time.time() - start
         print('%d triangles in %g seconds' % (triangles, seconds))
-
     generate.last_stats = stats
-    if _stl:
-        return records if records is not None else stl.stl_records(points).view(np.uint8).reshape(-1)
-    if _weld:
-        if welded is None and exported is None:      # (multi-process: the gathered soup is welded like the reference does it)
-            pts, cells = np.unique(points, axis=0, return_inverse=True)
-            welded = (pts, np.asarray(cells).reshape((-1, 3)))
-            if _export is not None:
-                exported = _export_host(eng, tape, welded, _export)
-        return welded if _export is None else exported
-    return points
 
 
-generate.last_stats = None
-
-
-def _read_kept(mesh, tape, keep, _stl, _export):
-    """`generate` with keep=: the shells of the device mesh are labelled, the kept ones compacted into a mesh of their own
-    (shells.resolve_keep, Mesh.select), and the selection is read like any device mesh: its STL records, its export or its weld.
-    Returns (records, welded, exported, points) as `generate` holds them.  Choosing by size brings the per-shell counts over the
-    link and nothing else; a callable is handed the whole `Shells`."""
-    import importlib
-    shells = importlib.import_module(__package__ + '.shells')
-    got = shells.shells_of_mesh(mesh) if callable(keep) else mesh.shell_summary()['triangles']
-    sel = mesh.select(shells.resolve_keep(keep, got))
+@contextlib.contextmanager
+def adopted(soup):
+    """a float64 soup (T, 3, 3) on the host as an `engine.Mesh`: uploaded (torch) and adopted for the life of the context"""
+    import torch
+    from . import engine
+    eng = engine.get_engine()
+    host = np.ascontiguousarray(soup, dtype=np.float64).reshape(-1, 9)
+    buf = torch.from_numpy(host).to('cuda:%d' % eng.device) if len(host) else None
+    torch.cuda.synchronize()
+    mesh = eng.adopt_soup(buf.data_ptr() if len(host) else 0, len(host))
     try:
-        records = welded = exported = None
-        if _stl:
-            records = sel.stl_records()
-        elif _export is not None:
-            exported = _export_mesh(sel, tape, _export)
-        else:
-            welded = sel.weld()
-        return records, welded, exported, np.empty((3 * sel.n_triangles, 0))
+        yield mesh
     finally:
-        sel.close()
+        mesh.close()
 
 
-def _export_mesh(mesh, tape, want):
-    """what the indexed export takes from a device mesh: welds it, takes the field's normals at the welded vertices when
-    want['normals'] (step want['eps']: k_vertex_normals) and returns a dict of `n_vertices`, `n_faces`, `normals` ((U, 3) float64
-    or None), `n_flat` and -- want['ply']: the device-packed PLY body `ply` = (vertex_bytes, face_bytes); otherwise `points`,
-    `cells` of the weld"""
+# -- the readers of a `Meshed`: each one names what it does with a soup that a multi-process run gathered on the host --
+
+def read_soup(m, workers=0):
+    """(3T, 3) float64 on the host: the 16-byte records come over and `workers` host threads make the float64 rows from them --
+    the one place the reference's `workers=` still means something here"""
+    return m.mesh.points(min(int(workers), 32) if workers else 0) if m.mesh is not None else m.points
+
+
+def read_stl_records(m):
+    """T x 50 bytes, made on the device (k_stl); byte-identical to `stl.stl_records` of the soup -- tests/test_gpu.py"""
+    return m.mesh.stl_records() if m.mesh is not None else stl.stl_records(m.points).view(np.uint8).reshape(-1)
+
+
+def read_weld(m):
+    """(unique points, cells): sdf_mesh_weld, or the reference's np.unique over the 3T rows"""
+    if m.mesh is not None:
+        return m.mesh.weld()
+    pts, cells = np.unique(m.points, axis=0, return_inverse=True)
+    return pts, np.asarray(cells).reshape((-1, 3))
+
+
+def read_export(m, normals=False, eps=None, ply=False):
+    """what the indexed export takes: the weld, with `normals` the field's normals at the welded vertices (step eps, default 1e-4 x
+    the half-diagonal of the bounds; k_vertex_normals) -- a dict of `n_vertices`, `n_faces`, `normals` ((U, 3) float64 or None),
+    `n_flat` and, with `ply`, the device-packed PLY body `ply` = (vertex_bytes, face_bytes); otherwise `points`, `cells` of the weld.
+    A soup gathered on the host takes its normals from the definition over eval_points and its PLY body from the host packer."""
+    from . import meshfile
     out = {'normals': None, 'n_flat': 0}
-    if want.get('measure'):          # (`measure`: nothing but the totals and the counts leaves the device)
-        import importlib
-        return {'measure': importlib.import_module(__package__ + '.measure').measure_mesh(mesh, want.get('origin'))}
-    if want.get('normals'):
-        out['normals'], out['n_flat'] = mesh.vertex_normals(tape, want['eps'])
-    if want.get('ply'):
-        closures = out['normals'] is not None and bool(tape.tape.externs)      # (their normals were taken on the host)
-        if closures:
-            from . import meshfile
+    if normals and eps is None:
+        # (the preview's value, render.render_buffers: a file and a preview of one model show the same normals)
+        lo, hi = np.asarray(m.bounds[0], dtype=np.float64), np.asarray(m.bounds[1], dtype=np.float64)
+        eps = 1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2)
+    mesh = m.mesh
+    if mesh is None:
+        pts, cells = read_weld(m)
+        out.update(points=pts, cells=cells, n_vertices=len(pts), n_faces=len(cells))
+        if normals:
+            out['normals'], out['n_flat'] = meshfile.vertex_normals(lambda P: m.engine.eval_points(m.tape, P), pts, eps)
+        if ply:
+            out['ply'] = meshfile.ply_records(pts, cells, out['normals'])
+        return out
+    if normals:
+        out['normals'], out['n_flat'] = mesh.vertex_normals(m.tape, eps)
+    if ply:
+        if normals and m.tape.tape.externs:      # (closures: their normals were taken on the host)
             out['points'], out['cells'] = mesh.weld()
             out['ply'] = meshfile.ply_records(out['points'], out['cells'], out['normals'])
         else:
-            out['ply'] = mesh.ply_records(normals=bool(want.get('normals')))
-        out['n_vertices'], out['n_faces'] = len(out['ply'][0]) // (24 if want.get('normals') else 12), mesh.n_triangles
+            out['ply'] = mesh.ply_records(normals=bool(normals))
+        out['n_vertices'], out['n_faces'] = len(out['ply'][0]) // (24 if normals else 12), mesh.n_triangles
     else:
         out['points'], out['cells'] = mesh.weld()
         out['n_vertices'], out['n_faces'] = len(out['points']), len(out['cells'])
     return out
 
 
-def _export_host(eng, tape, welded, want):
-    """the same for a soup that was gathered and welded on the host (multi-process runs): the normals come from the
-    definition over eval_points, the PLY body from the host packer"""
-    from . import meshfile
-    if want.get('measure'):
-        raise NotImplementedError('measure: the soup of this multi-process run was gathered on the host; the measurements are made '
-                                  'on the device only (run it in one process, or with a device-resident exchange)')
-    pts, cells = welded
-    out = {'points': pts, 'cells': cells, 'normals': None, 'n_flat': 0, 'n_vertices': len(pts), 'n_faces': len(cells)}
-    if want.get('normals'):
-        out['normals'], out['n_flat'] = meshfile.vertex_normals(lambda P: eng.eval_points(tape, P), pts, want['eps'])
-    if want.get('ply'):
-        out['ply'] = meshfile.ply_records(pts, cells, out['normals'])
-    return out
+def generate(
+        sdf,
+        step=None, bounds=None, samples=SAMPLES,
+        workers=WORKERS, batch_size=BATCH_SIZE,
+        verbose=True, sparse=True):
+    """reference sdf/core.py:84-150.  `batch_size` up to 512 (the reference takes any: a larger one is refused with a message; up
+    to 32 runs the fused kernels, above that the batches go through device memory -- a model with user closures then hands its
+    callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512)."""
+    with meshed(sdf, step, bounds, samples, workers, batch_size, verbose, sparse, to_host=True) as m:
+        return read_soup(m, workers)
+
+
+generate.last_stats = None
 
 
 def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, **generate_kwargs):
@@ -339,9 +322,8 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, **generate_kwa
     value).  The normals point outward for this library's winding; a vertex where the field has no gradient gets (0, 0, 0)
     (`generate_mesh.last_flat` counts them).  keep: only these connected shells of the mesh (`shells.resolve_keep`: 'largest', a
     count, a boolean mask over the shells, a callable).  Not in the reference."""
-    if keep is not None:
-        generate_kwargs['_keep'] = keep
-    got = generate(sdf, _export={'normals': bool(normals), 'eps': normal_eps}, **generate_kwargs)
+    with meshed(sdf, keep=keep, **generate_kwargs) as m:
+        got = read_export(m, bool(normals), normal_eps)
     generate_mesh.last_flat = got['n_flat']
     return got['points'], got['cells'], got['normals']
 
@@ -357,32 +339,29 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, **
     DESIGN.md section 4h) --, selected on the device before anything is written."""
     from . import meshfile
     path = os.fspath(path)
-    if keep is not None:
-        kwargs['_keep'] = keep
     how = meshfile.choose_writer(path, writer, normals)
-    if how == 'native':
-        ply = path.lower().endswith('.ply')
-        got = generate(*args, _export={'normals': bool(normals), 'eps': normal_eps, 'ply': ply}, **kwargs)
-        if ply:
-            meshfile.write_ply(path, got['ply'][0], got['ply'][1], got['n_vertices'], got['n_faces'], bool(normals))
+    ply = path.lower().endswith('.ply')
+    with meshed(*args, keep=keep, **kwargs) as m:
+        if how == 'native':
+            got = read_export(m, bool(normals), normal_eps, ply)
+        elif how == 'stl':
+            records = read_stl_records(m)
         else:
-            meshfile.write_obj(path, got['points'], got['cells'], got['normals'])
-        return
-    if path.lower().endswith('.stl'):
-        # normals and the 50-byte records are made on the device (k_stl); byte-identical to
-        # stl.write_binary_stl(path, points) -- tests/test_gpu.py
-        records = generate(*args, _stl=True, **kwargs)
+            points, cells = read_weld(m)
+    if how == 'native' and ply:
+        meshfile.write_ply(path, got['ply'][0], got['ply'][1], got['n_vertices'], got['n_faces'], bool(normals))
+    elif how == 'native':
+        meshfile.write_obj(path, got['points'], got['cells'], got['normals'])
+    elif how == 'stl':
         stl.write_stl_records(path, records)
     else:
-        # the vertex weld (np.unique over 3T rows in the reference) runs on the device: sdf_mesh_weld
-        points, cells = generate(*args, _weld=True, **kwargs)
         import meshio
         meshio.Mesh(points, [('triangle', cells)]).write(path)
 
 
 def _mesh(points):
     """vertex weld of a host-side soup for non-STL formats (reference sdf/core.py:160-164; needs
-    meshio).  `save` does not come through here: it welds on the device (`generate(_weld=True)`)."""
+    meshio).  `save` does not come through here: it welds on the device (`read_weld`)."""
     import meshio
     points, cells = np.unique(points, axis=0, return_inverse=True)
     cells = [('triangle', np.asarray(cells).reshape((-1, 3)))]

@@ -73,20 +73,20 @@ class SDF3(SDFBase):
         return core.generate_mesh(self, *args, **kwargs)
 
     def measure(self, *args, **kwargs):
-        import importlib
-        return importlib.import_module(__package__ + '.measure').measure(self, *args, **kwargs)
+        from .measure import measure
+        return measure(self, *args, **kwargs)
 
     def shells(self, **kwargs):
-        import importlib
-        return importlib.import_module(__package__ + '.shells').shells(self, **kwargs)
+        from .shells import shells
+        return shells(self, **kwargs)
 
     def measure_shells(self, *args, **kwargs):
-        import importlib
-        return importlib.import_module(__package__ + '.shells').measure_shells(self, *args, **kwargs)
+        from .shells import measure_shells
+        return measure_shells(self, *args, **kwargs)
 
     def render(self, path=None, **kwargs):
-        import importlib
-        return importlib.import_module(__package__ + '.render').render(self, path, **kwargs)
+        from .render import render
+        return render(self, path, **kwargs)
 
     def show_slice(self, *args, **kwargs):
         from . import core

@@ -275,10 +275,15 @@ def load_library(path=None):
         return lib
 
 
+_REFUSED = 2          # an entry point's return value for arguments it refused before anything was allocated or launched (include/sdf_hip.h)
+
+
 def _check(lib, rc):
+    """nothing for 0; ValueError for a refusal (every `return 2` of csrc is an argument check); SdfHipError for any other failure --
+    both with the text of sdf_last_error"""
     if rc != 0:
         msg = lib.sdf_last_error()
-        raise SdfHipError(msg.decode() if msg else 'sdf_hip error %d' % rc)
+        raise (ValueError if rc == _REFUSED else SdfHipError)(msg.decode() if msg else 'sdf_hip error %d' % rc)
 
 
 def _dp(a, t):
@@ -446,10 +451,7 @@ class Mesh:
         nu = self._welded()
         out = pinned_empty(eng.lib, (nu, 3), np.float64)
         flat = ctypes.c_int64(0)
-        rc = eng.lib.sdf_mesh_vertex_normals(self.handle, dt.handle, eps, _dp(out, _f64p), ctypes.byref(flat))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_vertex_normals(self.handle, dt.handle, eps, _dp(out, _f64p), ctypes.byref(flat)))
         return out, int(flat.value)
 
     def ply_records(self, normals=False):
@@ -462,10 +464,7 @@ class Mesh:
         fb = pinned_empty(eng.lib, (13 * t,), np.uint8)
         if nu == 0 or t == 0:
             return vb, fb
-        rc = eng.lib.sdf_mesh_emit_ply_host(self.handle, 1 if normals else 0, vb.ctypes.data_as(_vp), fb.ctypes.data_as(_vp))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_emit_ply_host(self.handle, 1 if normals else 0, vb.ctypes.data_as(_vp), fb.ctypes.data_as(_vp)))
         return vb, fb
 
     def moments(self, origin=None):
@@ -481,10 +480,7 @@ class Mesh:
             if o.shape != (3,):
                 raise ValueError('origin must have 3 components, got %r' % (origin,))
         out = SdfMoments()
-        rc = eng.lib.sdf_mesh_moments(self.handle, _dp(o, _f64p) if o is not None else None, ctypes.byref(out))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_moments(self.handle, _dp(o, _f64p) if o is not None else None, ctypes.byref(out)))
         return {'sums': np.array(out.sums[:], np.float64), 'origin': np.array(out.origin[:], np.float64),
                 'box': np.array([out.box_lo[:], out.box_hi[:]], np.float64), 'triangles': int(out.n_triangles),
                 'zero_area': int(out.n_zero_area), 'nonfinite': int(out.n_nonfinite)}
@@ -496,10 +492,7 @@ class Mesh:
         eng = self.engine
         self._welded()
         out = SdfEdgeCensus()
-        rc = eng.lib.sdf_mesh_edge_census(self.handle, ctypes.byref(out))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_edge_census(self.handle, ctypes.byref(out)))
         d = {k: int(getattr(out, k)) for k in CENSUS_FIELDS}
         d['closed'], d['oriented'] = bool(d['closed']), bool(d['oriented'])
         return d
@@ -508,10 +501,7 @@ class Mesh:
         """the `sdf_components` of this mesh; labels (and welds) on the device if that has not happened yet"""
         eng = self.engine
         out = SdfComponents()
-        rc = eng.lib.sdf_mesh_components(self.handle, ctypes.byref(out))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_components(self.handle, ctypes.byref(out)))
         return out
 
     def components(self):
@@ -528,11 +518,8 @@ class Mesh:
                'triangle_shell': pinned_empty(eng.lib, (int(c.n_triangles),), np.int32),
                'triangles': np.empty(k, np.int64), 'vertices': np.empty(k, np.int64), 'bounds': np.empty((k, 2, 3), np.float64)}
         if k:
-            rc = eng.lib.sdf_mesh_components_fetch(self.handle, _dp(out['vertex_shell'], i32p), _dp(out['triangle_shell'], i32p),
-                                                   _dp(out['triangles'], i64p), _dp(out['vertices'], i64p), _dp(out['bounds'], _f64p))
-            if rc == 2:
-                raise ValueError(eng.lib.sdf_last_error().decode())
-            _check(eng.lib, rc)
+            _check(eng.lib, eng.lib.sdf_mesh_components_fetch(self.handle, _dp(out['vertex_shell'], i32p), _dp(out['triangle_shell'], i32p),
+                                                              _dp(out['triangles'], i64p), _dp(out['vertices'], i64p), _dp(out['bounds'], _f64p)))
         return out
 
     def shell_summary(self):
@@ -557,10 +544,7 @@ class Mesh:
         mask = np.ascontiguousarray(np.asarray(keep_mask).reshape(-1) != 0, dtype=np.uint8)
         self._labelled()
         h = _vp()
-        rc = eng.lib.sdf_mesh_select_shells(self.handle, _dp(mask, _u8p), len(mask), ctypes.byref(h))
-        if rc == 2:
-            raise ValueError(eng.lib.sdf_last_error().decode())
-        _check(eng.lib, rc)
+        _check(eng.lib, eng.lib.sdf_mesh_select_shells(self.handle, _dp(mask, _u8p), len(mask), ctypes.byref(h)))
         m = Mesh(eng, h)
         m.emitted = False
         return m
@@ -851,11 +835,8 @@ class Engine:
         ijk0, dims = (_c_i64 * 3)(), (_c_i64 * 3)()
         while True:
             out = np.empty(cap, np.float32)
-            rc = self.lib.sdf_mesh_level_set_host(self.ctx, _dp(pts, _f64p), len(pts), _dp(tri, ctypes.POINTER(ctypes.c_int32)), len(tri), vs,
-                                                  hw, ijk0, dims, _dp(out, _f32p), cap)
-            if rc == 2:
-                raise ValueError(self.lib.sdf_last_error().decode())
-            _check(self.lib, rc)
+            _check(self.lib, self.lib.sdf_mesh_level_set_host(self.ctx, _dp(pts, _f64p), len(pts), _dp(tri, ctypes.POINTER(ctypes.c_int32)),
+                                                              len(tri), vs, hw, ijk0, dims, _dp(out, _f32p), cap))
             n = int(np.prod(list(dims)))
             if n == 0:
                 raise ValueError('no voxel lies within the narrow band of this mesh')
@@ -876,10 +857,7 @@ class Engine:
             raise ValueError('empty mask: shape %s' % (a.shape,))
         a = np.ascontiguousarray(a != 0, dtype=np.uint8)
         out = np.empty(a.shape, np.float64)
-        rc = self.lib.sdf_distance_texture_host(self.ctx, _dp(a, _u8p), a.shape[0], a.shape[1], _dp(out, _f64p))
-        if rc == 2:
-            raise ValueError(self.lib.sdf_last_error().decode())
-        _check(self.lib, rc)
+        _check(self.lib, self.lib.sdf_distance_texture_host(self.ctx, _dp(a, _u8p), a.shape[0], a.shape[1], _dp(out, _f64p)))
         return out
 
     def render_buffers(self, sdf, frame, width, height, t_near=0.0, t_far=1e9, hit_eps=1e-4, step_scale=1.0, normal_eps=1e-4,
@@ -903,12 +881,9 @@ class Engine:
         params = np.array([t_near, t_far, hit_eps, step_scale, normal_eps], dtype=np.float64)
         out = {'depth': np.empty((h, w), np.float64), 'normal': np.empty((h, w, 3), np.float64), 'steps': np.empty((h, w), np.int32),
                'status': np.empty((h, w), np.uint8)}
-        rc = self.lib.sdf_render_host(dt.handle, _dp(frame, _f64p), w, h, _dp(params, _f64p), int(max_steps), int(refine),
-                                      _dp(out['depth'], _f64p), _dp(out['normal'], _f64p),
-                                      _dp(out['steps'], ctypes.POINTER(ctypes.c_int32)), _dp(out['status'], _u8p))
-        if rc == 2:
-            raise ValueError(self.lib.sdf_last_error().decode())
-        _check(self.lib, rc)
+        _check(self.lib, self.lib.sdf_render_host(dt.handle, _dp(frame, _f64p), w, h, _dp(params, _f64p), int(max_steps), int(refine),
+                                                  _dp(out['depth'], _f64p), _dp(out['normal'], _f64p),
+                                                  _dp(out['steps'], ctypes.POINTER(ctypes.c_int32)), _dp(out['status'], _u8p)))
         return out
 
     def generate(self, sdf, X, Y, Z, batch_size=32, sparse=True, shard=(0, 1), out_ptr=None, out_cap=0, wait=True, records=False):

@@ -62,21 +62,15 @@ def measure(sdf, origin=None, keep=None, **generate_kwargs):
     about the centroid either way).  keep: measure only these connected shells of the mesh (`shells.resolve_keep`; `measure_shells`
     gives every shell its own Measurement).  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
     from . import core
-    if keep is not None:
-        generate_kwargs['_keep'] = keep
-    return core.generate(sdf, _export={'measure': True, 'origin': origin}, **generate_kwargs)['measure']
+    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
+        if m.mesh is None:
+            raise NotImplementedError('measure: the soup of this multi-process run was gathered on the host; the measurements are made '
+                                      'on the device only (run it in one process, or with a device-resident exchange)')
+        return measure_mesh(m.mesh, origin)
 
 
 def measure_soup(soup, origin=None):
     """the Measurement of a float64 soup (T, 3, 3) on the host: uploaded (torch), adopted and measured on the device"""
-    import torch
-    from . import engine
-    eng = engine.get_engine()
-    host = np.ascontiguousarray(soup, dtype=np.float64).reshape(-1, 9)
-    buf = torch.from_numpy(host).to('cuda:%d' % eng.device) if len(host) else None
-    torch.cuda.synchronize()
-    mesh = eng.adopt_soup(buf.data_ptr() if len(host) else 0, len(host))
-    try:
+    from . import core
+    with core.adopted(soup) as mesh:
         return measure_mesh(mesh, origin)
-    finally:
-        mesh.close()

@@ -98,15 +98,14 @@ class Mesh:
 
     def measure(self, origin=None):
         """volume, area, centroid, inertia and the edge census of this mesh, taken on the device (sdf_amd/measure.py)"""
-        import importlib
-        soup = np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)]
-        return importlib.import_module(__package__ + '.measure').measure_soup(soup, origin)
+        from .measure import measure_soup
+        return measure_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], origin)
 
     def shells(self):
         """the connected shells of this mesh (sdf_amd/shells.py `Shells`), labelled on the device.  The soup is welded there again:
         `vertex_shell` is over THAT weld's vertices (lexicographic order), `triangle_shell` over this mesh's triangles"""
-        import importlib
-        return importlib.import_module(__package__ + '.shells').shells_of_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)])
+        from .shells import shells_of_soup
+        return shells_of_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)])
 
     @property
     def bounding_box(self):

@@ -30,48 +30,25 @@ def shells_of_mesh(mesh):
 
 def shells_of_soup(soup):
     """the Shells of a float64 soup (T, 3, 3) on the host: uploaded (torch), adopted and labelled on the device"""
-    import torch
-    from . import engine
-    eng = engine.get_engine()
-    host = np.ascontiguousarray(soup, dtype=np.float64).reshape(-1, 9)
-    buf = torch.from_numpy(host).to('cuda:%d' % eng.device) if len(host) else None
-    torch.cuda.synchronize()
-    mesh = eng.adopt_soup(buf.data_ptr() if len(host) else 0, len(host))
-    try:
+    from . import core
+    with core.adopted(soup) as mesh:
         return shells_of_mesh(mesh)
-    finally:
-        mesh.close()
 
 
-def _device_mesh(sdf, generate_kwargs):
-    """`sdf` meshed on the device with the arguments of `generate` (step, bounds, samples, batch_size, sparse): the engine.Mesh"""
-    from . import core, dist, engine
+def _meshed(sdf, generate_kwargs):
+    """`core.meshed` for `shells` and `measure_shells`: the arguments of `generate`, nothing printed, one process"""
+    from . import core, dist
     if dist.world_size() > 1:
         raise NotImplementedError('shells: a multi-process run gathers its soup per step; label it in one process, or adopt the '
                                   'gathered soup (Engine.adopt_soup) and use shells_of_mesh')
-    kw = dict(generate_kwargs)
-    kw.pop('verbose', None)
-    kw.pop('workers', None)
-    batch_size, sparse = kw.pop('batch_size', core.BATCH_SIZE), kw.pop('sparse', True)
-    bounds, step, samples = kw.pop('bounds', None), kw.pop('step', None), kw.pop('samples', core.SAMPLES)
-    if kw:
-        raise TypeError('unexpected arguments: %s' % ', '.join(sorted(kw)))
-    eng = engine.get_engine()
-    tape = eng.tape_for(sdf)
-    if bounds is None:
-        bounds = core._estimate_bounds(tape)
-    X, Y, Z, _ = core.grid_axes(bounds, step, samples)
-    return eng.generate(tape, X, Y, Z, batch_size, sparse)
+    return core.meshed(sdf, keep=None, to_host=False, **dict(generate_kwargs, verbose=False))
 
 
 def shells(sdf, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`) and label the connected shells of the welded mesh there: only the
     Shells cross the link, not the soup"""
-    mesh = _device_mesh(sdf, generate_kwargs)
-    try:
-        return shells_of_mesh(mesh)
-    finally:
-        mesh.close()
+    with _meshed(sdf, generate_kwargs) as m:
+        return shells_of_mesh(m.mesh)
 
 
 def largest_first(triangles):
@@ -85,17 +62,13 @@ def measure_shells(sdf, limit=None, **generate_kwargs):
     `limit` bounds how many.  The model is meshed ONCE; then every shell costs one selection (a compaction of the soup) plus one
     measure (moments, weld, census) on the device, so ask for `limit` shells when the crumbs are many.  A sealed cavity is
     recognisable by its negative `volume`."""
-    mesh = _device_mesh(sdf, generate_kwargs)
-    try:
-        return measure_shells_of_mesh(mesh, limit)
-    finally:
-        mesh.close()
+    with _meshed(sdf, generate_kwargs) as m:
+        return measure_shells_of_mesh(m.mesh, limit)
 
 
 def measure_shells_of_mesh(mesh, limit=None):
     """`measure_shells` of a device mesh"""
-    import importlib
-    measure = importlib.import_module(__package__ + '.measure')      # (the package's `measure` attribute is the function)
+    from .measure import measure_mesh
     summary = mesh.shell_summary()
     order = largest_first(summary['triangles'])
     if limit is not None:
@@ -106,7 +79,7 @@ def measure_shells_of_mesh(mesh, limit=None):
         mask[k] = True
         sel = mesh.select(mask)
         try:
-            out.append(measure.measure_mesh(sel))
+            out.append(measure_mesh(sel))
         finally:
             sel.close()
     return out

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import normals_ref as ref
-from sdf_amd import core, engine, meshfile
+from sdf_amd import core, dist, engine, meshfile, stl
+from sdf_amd.measure import measure
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -205,7 +206,7 @@ def test_writer_selection(monkeypatch, have_meshio):
 
 
 NO_MESHIO = r'''
-import importlib.abc, sys
+import contextlib, importlib, importlib.abc, sys, types
 asked = []
 class Watch(importlib.abc.MetaPathFinder):
     def find_spec(self, name, path=None, target=None):
@@ -217,17 +218,34 @@ import numpy as np
 import sdf_amd
 from sdf_amd import core
 import normals_ref as ref
-import test_export_host as T
+T = importlib.import_module(sys.argv[2])          # this test module: PTS, CELLS, NRM
+TAPE = types.SimpleNamespace(tape=types.SimpleNamespace(externs=[]))
+BOUNDS = ((-1.0, -2.0, -3.0), (3.0, 1.0, 9.0))    # its diagonal is 13
+DEFAULT_EPS = 1e-4 * 6.5
+class StubMesh:
+    # a device mesh that holds T.PTS / T.CELLS and notes what is asked of it
+    def __init__(self):
+        self.log = []
+    @property
+    def n_triangles(self):
+        self.log.append('n_triangles')
+        return len(T.CELLS)
+    def weld(self):
+        self.log.append('weld')
+        return T.PTS, T.CELLS
+    def vertex_normals(self, tape, eps):
+        self.log.append(('vertex_normals', tape, eps))
+        return T.NRM, 1
+    def ply_records(self, normals=False):
+        self.log.append(('ply_records', normals))
+        return ref.ply_records(T.PTS, T.CELLS, T.NRM if normals else None)
 calls = []
-def fake_generate(sdf, *args, _export=None, **kw):          # `generate` is where the device begins: stand in for it
-    calls.append((_export, kw))
-    assert _export is not None
-    n = T.NRM if _export['normals'] else None
-    out = {'points': T.PTS, 'cells': T.CELLS, 'normals': n, 'n_flat': 1 if _export['normals'] else 0, 'n_vertices': 4, 'n_faces': 2}
-    if _export.get('ply'):
-        out['ply'] = ref.ply_records(T.PTS, T.CELLS, n)
-    return out
-core.generate = fake_generate
+@contextlib.contextmanager
+def fake_meshed(sdf, *args, keep=None, to_host=False, **kw):          # `meshed` is where the device begins: stand in for it
+    mesh = StubMesh()
+    calls.append((mesh.log, args, keep, to_host, kw))
+    yield core.Meshed(mesh, None, TAPE, None, BOUNDS, {})
+core.meshed = fake_meshed
 f = sdf_amd.sphere(1)
 try:
     f.save(sys.argv[1] + '/a.stl', normals=True)
@@ -238,9 +256,12 @@ assert not calls
 for name, kw in (('n.ply', dict(normals=True)), ('p.ply', dict(writer='native')), ('n.obj', dict(normals=True, normal_eps=0.5)),
                  ('p.obj', dict(writer='native', samples=64))):
     f.save(sys.argv[1] + '/' + name, **kw)
-assert [c[0] for c in calls] == [{'normals': True, 'eps': None, 'ply': True}, {'normals': False, 'eps': None, 'ply': True},
-                                 {'normals': True, 'eps': 0.5, 'ply': False}, {'normals': False, 'eps': None, 'ply': False}], calls
-assert calls[3][1] == {'samples': 64} and calls[0][1] == {}
+# normals taken or not and with which step; the PLY body packed by the mesh, the OBJ's weld fetched
+assert [c[0] for c in calls] == [[('vertex_normals', TAPE, DEFAULT_EPS), ('ply_records', True), 'n_triangles'],
+                                 [('ply_records', False), 'n_triangles'],
+                                 [('vertex_normals', TAPE, 0.5), 'weld'],
+                                 ['weld']], calls
+assert [c[1:] for c in calls] == [((), None, False, {})] * 3 + [((), None, False, {'samples': 64})], calls
 for name, wn in (('n.ply', True), ('p.ply', False)):
     p, n, c, head = ref.parse_ply(sys.argv[1] + '/' + name)
     assert np.array_equal(p, T.PTS.astype(np.float32)) and np.array_equal(c, T.CELLS) and (n is not None) == wn
@@ -248,17 +269,93 @@ for name, wn in (('n.obj', True), ('p.obj', False)):
     p, n, c = ref.parse_obj(sys.argv[1] + '/' + name)
     assert np.array_equal(p, T.PTS.astype(np.float32)) and np.array_equal(c, T.CELLS) and (n is not None) == wn
 pts, cells, nrm = f.generate_mesh(normals=True, samples=64)
-assert nrm is T.NRM and core.generate_mesh.last_flat == 1 and calls[-1] == ({'normals': True, 'eps': None}, {'samples': 64})
+assert pts is T.PTS and cells is T.CELLS and nrm is T.NRM and core.generate_mesh.last_flat == 1
+assert calls[-1] == ([('vertex_normals', TAPE, DEFAULT_EPS), 'weld'], (), None, False, {'samples': 64}), calls[-1]
 assert not asked and 'meshio' not in sys.modules, asked
 # the default writer keeps meshio where it is installed and, without it, writes the native file
 sys.modules['meshio'] = None
 f.save(sys.argv[1] + '/d.ply')
-assert calls[-1][0] == {'normals': False, 'eps': None, 'ply': True} and ref.parse_ply(sys.argv[1] + '/d.ply')[1] is None
+assert calls[-1][0] == [('ply_records', False), 'n_triangles'] and ref.parse_ply(sys.argv[1] + '/d.ply')[1] is None
 print('ok', len(calls))
 '''
 
 
 def test_native_path_never_imports_meshio(tmp_path):
     script = 'import sys\nsys.path[:0] = [%r, %r]\n' % (ROOT, os.path.join(ROOT, 'tests')) + NO_MESHIO
-    r = subprocess.run([sys.executable, '-c', script, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, '-c', script, str(tmp_path), __name__], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith('ok'), r.stdout + r.stderr
+
+
+# ---- a multi-process run whose soup was gathered on the host: `core.meshed` yields no device mesh and every reader says what it does then ----
+SOUP = PTS[CELLS].reshape(-1, 3)          # two triangles, six rows, four distinct points
+BOUNDS = ((-1.0, -2.0, -3.0), (3.0, 1.0, 9.0))          # its diagonal is 13
+STATS = {'skipped': 3, 'empty': 4, 'nonempty': 1}
+
+
+class StubEngine:
+    precision = engine.PRECISION_F64
+
+    def tape_for(self, sdf):
+        return ('tape of', sdf)
+
+    def eval_points(self, tape, P):
+        assert tape == ('tape of', 'model')
+        return np.sqrt((np.asarray(P) ** 2).sum(axis=1)) - 1.0
+
+
+@pytest.fixture
+def gathered(monkeypatch):
+    """a world of two ranks whose exchange hands back the soup in HOST memory; the list counts the engines asked for"""
+    import torch
+    asked = []
+    monkeypatch.setattr(dist, 'world_size', lambda: 2)
+    monkeypatch.setattr(dist, 'generate_sharded_device', lambda eng, tape, X, Y, Z, batch_size, sparse: (torch.from_numpy(SOUP.reshape(-1).copy()), STATS))
+    monkeypatch.setattr(engine, 'get_engine', lambda device=None: asked.append(device) or StubEngine())
+    return asked
+
+
+def test_host_gathered_soup_is_read_on_the_host(gathered, monkeypatch, tmp_path, capsys):
+    got = core.generate('model', bounds=BOUNDS, samples=64, workers=5)
+    assert got.dtype == np.float64 and np.array_equal(got, SOUP) and core.generate.last_stats is STATS
+    out = capsys.readouterr().out.split('\n')
+    assert out[0] == 'min -1, -2, -3' and out[1] == 'max 3, 1, 9' and out[2].startswith('step ') and out[3].endswith('with 5 workers')
+    assert out[4] == '3 skipped, 4 empty, 1 nonempty' and out[5].startswith('2 triangles in ')
+
+    core.save(str(tmp_path / 'x.stl'), 'model', bounds=BOUNDS, samples=64, verbose=False)
+    stl.write_binary_stl(str(tmp_path / 'want.stl'), SOUP)
+    assert (tmp_path / 'x.stl').read_bytes() == (tmp_path / 'want.stl').read_bytes()
+
+    wp, wc = np.unique(SOUP, axis=0, return_inverse=True)
+    wc = np.asarray(wc).reshape(-1, 3)
+    pts, cells, nrm = core.generate_mesh('model', bounds=BOUNDS, samples=64, verbose=False)
+    assert nrm is None and np.array_equal(pts, wp) and np.array_equal(cells, wc) and len(pts) == 4 and cells.shape == (2, 3)
+
+    seen = []
+    real = meshfile.vertex_normals
+    monkeypatch.setattr(meshfile, 'vertex_normals', lambda ev, P, eps: seen.append((P, eps)) or real(ev, P, eps))
+    pts, cells, nrm = core.generate_mesh('model', normals=True, bounds=BOUNDS, samples=64, verbose=False)
+    assert len(seen) == 1 and np.array_equal(seen[0][0], wp) and seen[0][1] == 1e-4 * 6.5
+    want, flat = real(lambda P: StubEngine().eval_points(('tape of', 'model'), P), wp, 1e-4 * 6.5)
+    assert np.array_equal(nrm, want) and core.generate_mesh.last_flat == flat and np.array_equal(pts, wp) and np.array_equal(cells, wc)
+    core.save(str(tmp_path / 'n.ply'), 'model', normals=True, normal_eps=0.5, bounds=BOUNDS, samples=64, verbose=False)
+    assert seen[-1][1] == 0.5 and (tmp_path / 'n.ply').read_bytes().endswith(b''.join(a.tobytes() for a in meshfile.ply_records(wp, wc, real(
+        lambda P: StubEngine().eval_points(('tape of', 'model'), P), wp, 0.5)[0])))
+
+
+def test_host_gathered_soup_cannot_be_measured_or_split(gathered, tmp_path):
+    with pytest.raises(NotImplementedError, match='measure: the soup of this multi-process run was gathered on the host'):
+        measure('model', bounds=BOUNDS, samples=64, verbose=False)
+    for call in (lambda: core.generate_mesh('model', keep='largest', bounds=BOUNDS, samples=64, verbose=False),
+                 lambda: core.save(str(tmp_path / 'k.stl'), 'model', keep=1, bounds=BOUNDS, samples=64, verbose=False),
+                 lambda: core.save(str(tmp_path / 'k.ply'), 'model', keep=[True], writer='native', bounds=BOUNDS, samples=64, verbose=False),
+                 lambda: measure('model', keep=lambda sh: sh.triangles > 1, bounds=BOUNDS, samples=64, verbose=False)):
+        with pytest.raises(NotImplementedError, match='keep: the soup of this multi-process run was gathered on the host'):
+            call()
+    assert not (tmp_path / 'k.stl').exists() and not (tmp_path / 'k.ply').exists()
+    # a keep that no mesh could satisfy is still refused first: no engine is asked for
+    del gathered[:]
+    for call in (lambda: core.generate_mesh('model', keep='smallest', bounds=BOUNDS), lambda: measure('model', keep=-3, bounds=BOUNDS),
+                 lambda: core.save(str(tmp_path / 'k.stl'), 'model', keep=2.5, bounds=BOUNDS)):
+        with pytest.raises(ValueError, match='keep'):
+            call()
+    assert gathered == []

@@ -388,3 +388,24 @@ if __name__ == '__main__':
         os.remove(path)
     assert r.returncode == 0 and r.stdout.strip().startswith('ok'), r.stdout[-1500:] + r.stderr[-3000:]
     assert time.time() - t0 < 60
+
+
+class FakeLib:
+    def __init__(self, text):
+        self.text = text
+
+    def sdf_last_error(self):
+        return self.text
+
+
+def test_check_tells_a_refusal_from_a_failure():
+    from sdf_amd import engine as _engine
+    lib = FakeLib(b'sdf_mesh_moments: NULL argument')
+    assert _engine._check(lib, 0) is None
+    with pytest.raises(ValueError, match='^sdf_mesh_moments: NULL argument$') as e:
+        _engine._check(lib, 2)
+    assert not isinstance(e.value, _engine.SdfHipError)
+    with pytest.raises(_engine.SdfHipError, match='^sdf_mesh_moments: NULL argument$'):
+        _engine._check(lib, 1)
+    with pytest.raises(_engine.SdfHipError, match='^sdf_hip error 7$'):
+        _engine._check(FakeLib(None), 7)

@@ -44,7 +44,7 @@ def meshes(ns):
     F[::2] = F[::2, ::-1]
     Pd = np.vstack([Pt, [[0.75, 0.0, 0.125], [1.0, 0.0, 0.125], [0.875, 0.0, 0.125]]])
     Td = np.vstack([Tt, [[8, 9, 10]]])
-    pts, cells = core.generate(ns['torus'](0.6, 0.25), samples=2 ** 13, verbose=False, _weld=True)
+    pts, cells = core.generate_mesh(ns['torus'](0.6, 0.25), samples=2 ** 13, verbose=False)[:2]
     return {
         'box': (P, T, (0.1, 0.07)),
         'box_ties': (Pt, Tt, (0.125, 0.0625)),
@@ -95,7 +95,7 @@ def test_end_to_end_through_the_fused_path(ns, oracle_lib, eng):
 
 
 def test_sphere_mesh_is_geometrically_sane(ns, eng):
-    pts, cells = core.generate(ns['sphere'](1), samples=2 ** 18, verbose=False, _weld=True)
+    pts, cells = core.generate_mesh(ns['sphere'](1), samples=2 ** 18, verbose=False)[:2]
     # how far the mesh lies from the unit sphere: its vertices outward, its facets inward (the distance of the origin to each)
     zero = (np.zeros((1, 1)),) * 3
     V = pts[cells]
@@ -158,7 +158,7 @@ def test_invalid_input_raises_and_nothing_is_held(eng):
 def test_large_mesh_band_voxels(ns, eng):
     import fixtures
     f = fixtures.build('ex_example', ns)
-    pts, cells = core.generate(f, samples=2 ** 24, verbose=False, _weld=True)
+    pts, cells = core.generate_mesh(f, samples=2 ** 24, verbose=False)[:2]
     assert len(cells) > 500000
     vs = float(np.ptp(pts, axis=0).max()) / 200
     g = mesh.Mesh(pts, cells).sdf(vs, voxelizer='device')

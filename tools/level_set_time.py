@@ -34,7 +34,7 @@ def main():
     f = sdf_amd.sphere(1) & sdf_amd.box(1.5)
     c = sdf_amd.cylinder(0.5)
     f -= c.orient(sdf_amd.X) | c.orient(sdf_amd.Y) | c.orient(sdf_amd.Z)
-    pts, cells = core.generate(f, samples=2 ** args.samples_log2, verbose=False, _weld=True)
+    pts, cells = core.generate_mesh(f, samples=2 ** args.samples_log2, verbose=False)[:2]
     vs = float(np.ptp(pts, axis=0).max()) / args.voxels
     hw = mesh.half_width_voxels(vs)
     eng = engine.get_engine(0)
