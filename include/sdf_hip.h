@@ -42,7 +42,9 @@ typedef struct sdf_stats {
     int64_t n_triangles;        /* within this call's shard */
     int64_t n_grid_voxels;      /* len(X)*len(Y)*len(Z)                                    */
     int64_t n_eval_voxels;      /* samples evaluated by the meshing kernel (this shard)    */
-    int64_t n_ambiguous_cells;  /* surface cells with an ambiguous sign configuration      */
+    int64_t n_ambiguous_cells;  /* surface cells with an ambiguous sign configuration (the ones Lewiner's tests tile), this
+                                 * shard's: counted by k_mesh, and by k_field_rows for batch_size > 32 and sdf_generate_field;
+                                 * the CPU checker's n_ambiguous                                                   */
     int64_t n_work_begin;       /* this shard's range in the surviving-batch work list     */
     int64_t n_work_end;
     int64_t n_retries;          /* meshing re-runs after a triangle-arena overflow         */

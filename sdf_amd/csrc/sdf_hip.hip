@@ -1335,24 +1335,27 @@ static FieldTile field_tile(const double *X, const double *Y, const double *Z, c
 
 // One chunk of nt <= FIELD_CHUNK_MAX tiles whose float32 volumes (the context's field_vol) and FieldTile table (field_tiles) are
 // on the device, marched into the ordered soup behind its first `total` triangles: k_field_rows / k_scan_rows number the
-// triangles, the host reads the offsets and classifies the chunk's `batches` (kinds 1 = empty, 2 = non-empty), the soup
-// grows, k_field_emit writes `points * scale + offset`; waits for the chunk.  prefix (or NULL): per tile its inclusive
+// triangles and count the ambiguous cells, the host reads the offsets and classifies the chunk's `batches` (kinds 1 = empty,
+// 2 = non-empty), the soup grows, k_field_emit writes `points * scale + offset`; waits for the chunk.  prefix (or NULL): per tile its inclusive
 // triangle prefix as a look-back word of the fused path.
 static int march_chunk(sdf_mesh *m, hipStream_t st, const int *batches, int nt, int slots, uint8_t *kinds, unsigned long long &total,
                        unsigned long long *prefix) {
     sdf_ctx *c = m->ctx;
     const size_t nslots = (size_t)nt * slots;
-    launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                        (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots);
+    // (behind the nslots row offsets: the chunk's triangle total, then its count of ambiguous cells)
     unsigned long long *d_total = (unsigned long long *)c->rows_off.p + nslots;
+    HIPCHK(hipMemsetAsync(d_total + 1, 0, 8, st));
+    launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
+                        (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots, d_total + 1);
     launch_k_scan_rows(dim3(1), dim3(1024), st, (const unsigned *)c->rows.p, (long long)nslots, (unsigned long long *)c->rows_off.p, d_total);
     HIPCHK(hipGetLastError());
-    // (per tile only its first slot's offset and the chunk's total are needed on the host)
-    unsigned long long offs[FIELD_CHUNK_MAX + 1];
+    // (per tile only its first slot's offset, the chunk's total and its ambiguous cells are needed on the host)
+    unsigned long long offs[FIELD_CHUNK_MAX + 2];
     HIPCHK(hipMemcpy2DAsync(offs, 8, c->rows_off.p, (size_t)slots * 8, 8, (size_t)nt, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&offs[nt], d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&offs[nt], d_total, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(st));
     const unsigned long long chunk_total = offs[nt];
+    m->st.n_ambiguous_cells += (int64_t)offs[nt + 1];
     for (int j = 0; j < nt; j++) {
         const unsigned long long cnt = offs[j + 1] - offs[j];
         kinds[(size_t)batches[j]] = cnt ? 2 : 1;
@@ -1428,7 +1431,7 @@ static int generate_big(sdf_mesh *m, const GenCall &call) {
     std::vector<FieldTile> tiles((size_t)CH);
     std::vector<int> org((size_t)CH * 3);
     if (c->field_vol.ensure((size_t)CH * tile_max * 4) || c->field_tiles.ensure(sizeof(FieldTile) * CH + (size_t)CH * 12) ||
-        c->rows.ensure((size_t)CH * slots * 4) || c->rows_off.ensure(((size_t)CH * slots + 1) * 8))
+        c->rows.ensure((size_t)CH * slots * 4) || c->rows_off.ensure(((size_t)CH * slots + 2) * 8))
         return 1;
     int *d_org = reinterpret_cast<int *>((char *)c->field_tiles.p + sizeof(FieldTile) * CH);
     unsigned long long total = 0;
@@ -1677,7 +1680,7 @@ int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double 
         if (field(user, pts, (int64_t)npts, vals)) return fail("sdf_generate_field: the field callback failed");
         const size_t nslots = (size_t)nt * slots;
         if (c->field_vals.ensure(npts * 8) || c->field_vol.ensure(npts * 4) || c->field_tiles.ensure(sizeof(FieldTile) * CH) ||
-            c->rows.ensure(nslots * 4) || c->rows_off.ensure((nslots + 1) * 8))
+            c->rows.ensure(nslots * 4) || c->rows_off.ensure((nslots + 2) * 8))
             return 1;
         HIPCHK(hipMemcpyAsync(c->field_vals.p, vals, npts * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->field_tiles.p, tiles.data(), sizeof(FieldTile) * (size_t)nt, hipMemcpyHostToDevice, c->stream));

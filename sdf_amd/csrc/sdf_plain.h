@@ -8,7 +8,8 @@
 // chunk of batches sampled by a host callback; generate_big: batch_size > 32, sampled by k_eval_tiles).  A tile
 // has at most `slots` rows of cells (1024 for batch_size <= 32; a multiple of 256); row slot tile * slots + t
 // carries the row's triangle count (0 beyond the tile's rows), so one scan over the slots numbers the triangles
-// of the whole chunk in reference order. ----
+// of the whole chunk in reference order.  k_field_rows also adds the chunk's ambiguous surface cells to *n_ambiguous,
+// which its caller clears (sdf_stats::n_ambiguous_cells). ----
 struct FieldTile {
     long long vol_off;      // first sample of the tile in the chunk's value buffer
     int n0, n1, n2, pad_;
@@ -23,7 +24,7 @@ void launch_k_mc_emit(dim3 grid, dim3 block, hipStream_t stream, const sdfk::McT
                       const unsigned long long *row_off, float *out, unsigned long long cap);
 void launch_k_cast_f32(dim3 grid, dim3 block, hipStream_t stream, const double *in, float *out, long long n);
 void launch_k_field_rows(dim3 grid, dim3 block, hipStream_t stream, const sdfk::McTables *mc, const float *vol, const FieldTile *tiles, unsigned int *row_count,
-                         int slots);
+                         int slots, unsigned long long *n_ambiguous);
 void launch_k_field_emit(dim3 grid, dim3 block, hipStream_t stream, const sdfk::McTables *mc, const float *vol, const FieldTile *tiles,
                          const unsigned long long *row_off, double *out, unsigned long long base, unsigned long long cap, int slots);
 void launch_k_scan_items(dim3 grid, dim3 block, hipStream_t stream, const sdfk::ItemDesc *desc, sdfk::MeshCounters *ctr, unsigned long long *status,

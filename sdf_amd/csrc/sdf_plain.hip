@@ -126,9 +126,11 @@ __global__ __launch_bounds__(256) void k_cast_f32(const double *__restrict__ in,
     if (i < n) out[i] = (float)in[i];     // volume.astype(float32) inside skimage
 }
 
-__device__ __forceinline__ unsigned mc_row_count(const McTables *__restrict__ mc, const float *__restrict__ row, int s0, int s1, int c2) {
+// triangles of one row of cells; n_amb: how many of its surface cells have an ambiguous sign configuration
+__device__ __forceinline__ unsigned mc_row_count(const McTables *__restrict__ mc, const float *__restrict__ row, int s0, int s1, int c2, unsigned &n_amb) {
     unsigned prev = plane_bits(row, s0, s1);
     unsigned cnt = 0;
+    n_amb = 0;
     for (int i2 = 0; i2 < c2; i2++) {
         const unsigned next = plane_bits(row + i2 + 1, s0, s1);
         const unsigned cfg = spread4(prev) | (spread4(next) << 1);
@@ -137,6 +139,7 @@ __device__ __forceinline__ unsigned mc_row_count(const McTables *__restrict__ mc
             int off;
             mc33_load_cell(row + i2, s0, s1, lv);
             cnt += (unsigned)mc33_cell(lv, mc->mc33, &off);
+            n_amb++;
         } else {
             cnt += mc->ntri[cfg];
         }
@@ -145,8 +148,10 @@ __device__ __forceinline__ unsigned mc_row_count(const McTables *__restrict__ mc
     return cnt;
 }
 
+// n_ambiguous (cleared by the caller): the chunk's ambiguous surface cells, one add per row that met any
 __global__ __launch_bounds__(256) void k_field_rows(const McTables *__restrict__ mc, const float *__restrict__ vol,
-                                                    const FieldTile *__restrict__ tiles, unsigned int *__restrict__ row_count, int slots) {
+                                                    const FieldTile *__restrict__ tiles, unsigned int *__restrict__ row_count, int slots,
+                                                    unsigned long long *__restrict__ n_ambiguous) {
     const FieldTile tl = tiles[blockIdx.y];
     const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);        // row slot 0 .. slots - 1 (1024 for tiles of <= 33^3 samples)
     const int c0 = tl.n0 - 1, c1 = tl.n1 - 1, c2 = tl.n2 - 1;
@@ -154,7 +159,9 @@ __global__ __launch_bounds__(256) void k_field_rows(const McTables *__restrict__
     if (c0 > 0 && c1 > 0 && c2 > 0 && t < c0 * c1) {
         const int i0 = t / c1, i1 = t - i0 * c1;
         const int s0 = tl.n1 * tl.n2, s1 = tl.n2;
-        cnt = mc_row_count(mc, vol + tl.vol_off + (long long)i0 * s0 + (long long)i1 * s1, s0, s1, c2);
+        unsigned n_amb;
+        cnt = mc_row_count(mc, vol + tl.vol_off + (long long)i0 * s0 + (long long)i1 * s1, s0, s1, c2, n_amb);
+        if (n_amb) atomicAdd(n_ambiguous, (unsigned long long)n_amb);
     }
     row_count[(size_t)blockIdx.y * (size_t)slots + t] = cnt;
 }
@@ -529,8 +536,8 @@ void launch_k_cast_f32(dim3 grid, dim3 block, hipStream_t stream, const double *
     hipLaunchKernelGGL(k_cast_f32, grid, block, 0, stream, in, out, n);
 }
 void launch_k_field_rows(dim3 grid, dim3 block, hipStream_t stream, const McTables *mc, const float *vol, const FieldTile *tiles, unsigned int *row_count,
-                         int slots) {
-    hipLaunchKernelGGL(k_field_rows, grid, block, 0, stream, mc, vol, tiles, row_count, slots);
+                         int slots, unsigned long long *n_ambiguous) {
+    hipLaunchKernelGGL(k_field_rows, grid, block, 0, stream, mc, vol, tiles, row_count, slots, n_ambiguous);
 }
 void launch_k_field_emit(dim3 grid, dim3 block, hipStream_t stream, const McTables *mc, const float *vol, const FieldTile *tiles,
                          const unsigned long long *row_off, double *out, unsigned long long base, unsigned long long cap, int slots) {
