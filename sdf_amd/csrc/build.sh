@@ -30,9 +30,10 @@ $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=0 -DMESH_NAME=sdf_launch_mesh_f64 -c -
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=1 -DMESH_NAME=sdf_launch_mesh_f64_full -c -o build/mesh_f64_full.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 # (every kernel that is not a tape interpreter: built WITHOUT the structurizer option, see sdf_plain.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_plain.o sdf_plain.hip "$@" & pids="$pids $!"
-# (host code only -- the runtime every unit shares, the readers of a finished mesh, the multi-GPU step: they launch through the
-# launchers of sdf_plain / sdf_normals / sdf_weld, so they take the plain flags)
-for u in sdf_runtime sdf_mesh_out sdf_comm; do
+# (host code only -- the runtime every unit shares, the meshing paths through device memory, the readers of a finished mesh, the
+# multi-GPU step: they launch through the launchers of sdf_plain / sdf_normals / sdf_weld and, for the one interpreter kernel
+# among them, k_eval_tiles, through enqueue_eval_tiles of sdf_hip.hip, so they take the plain flags)
+for u in sdf_runtime sdf_chunked sdf_mesh_out sdf_comm; do
     $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/$u.o $u.hip "$@" & pids="$pids $!"
 done
 # (the mesh-to-level-set voxelizer: plain kernels, float64 rounded like NumPy's, see sdf_level_set.hip)
@@ -48,4 +49,4 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
     build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o \
-    build/sdf_runtime.o build/sdf_mesh_out.o build/sdf_comm.o build/sdf_measure.o build/sdf_components.o
+    build/sdf_runtime.o build/sdf_chunked.o build/sdf_mesh_out.o build/sdf_comm.o build/sdf_measure.o build/sdf_components.o

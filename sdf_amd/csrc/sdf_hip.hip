@@ -1,11 +1,11 @@
 // sdf_hip.hip -- the tape-interpreter kernels (k_eval_*, k_skip, k_prune_list, k_cull) + the contexts, tapes and generate calls of
-// libsdf_hip.so's C ABI (gfx950 only; the rest of the ABI: sdf_runtime.hip, sdf_mesh_out.hip, sdf_comm.hip and the features' own units).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip, k_render in sdf_render.hip; every kernel that is not an
+// libsdf_hip.so's C ABI (gfx950 only; the rest of the ABI: sdf_runtime.hip, sdf_chunked.hip, sdf_mesh_out.hip, sdf_comm.hip and the features' own units).  k_mesh is instantiated in sdf_mesh_inst.hip, k_estimate_bounds in sdf_bounds.hip, k_render in sdf_render.hip; every kernel that is not an
 // interpreter (k_compact, k_scan_items, k_emit2, k_pack_slab, k_expand, k_mc_*, k_field_*, k_cast_f32, k_stl) in sdf_plain.hip.
 //
 // Kernels (one call of sdf_generate enqueues k_skip -> k_compact [-> k_prune_list] -> k_cull -> k_mesh
 // [-> k_scan_items -> k_emit2] on one stream, without a host round trip in between)
 //   k_eval_points / k_eval_grid   f(P): the tape interpreter alone; k_eval_points_ext: with user closures (L_EXTERN)
-//   k_eval_tiles                  the float32 volumes of a chunk of batches of more than 33^3 samples (batch_size > 32: generate_big)
+//   k_eval_tiles                  the float32 volumes of a chunk of batches of more than 33^3 samples (batch_size > 32: generate_big, sdf_chunked.hip)
 //   k_estimate_bounds             the reference's `_estimate_bounds` loop (sdf/core.py:62-82) as one launch (sdf_bounds.hip)
 //   k_skip                        the reference's `_skip` predicate for every batch at once
 //                                 (reference sdf/core.py:28-43), 9 lanes per batch, 7 batches per wave; its surplus
@@ -27,7 +27,8 @@
 //   k_pack_slab / k_expand        multi-GPU exchange: a shard's soup as a fixed-capacity slab / the gathered slabs
 //                                 expanded into the ordered float64 soup
 //   k_mc_rows / k_mc_emit         marching cubes of a caller-supplied volume (`_marching_cubes`);
-//   k_cast_f32 / k_field_*        the same for the batches of a host-evaluated field (user closures)
+//   k_cast_f32 / k_field_*        the same for the chunks of batches that go through device memory (sdf_chunked.hip: a
+//                                 host-evaluated field = user closures, and batch_size > 32)
 //   k_stl                         50-byte STL records (reference sdf/stl.py:4-24)
 //   k_vertex_normals              the field's gradient at the welded vertices (sdf_normals.hip); k_ply_vertices / k_ply_faces: binary PLY records
 #include <hip/hip_runtime.h>
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void k_eval_grid(const uint32_t *__restrict__ 
 }
 
 // `volume = sdf(P).reshape(...)`, cast to float32 as skimage does (reference sdf/core.py:50-54), for a chunk of whole tiles in
-// device memory: batch_size > 32, whose (batch_size + 1)^3 tile does not fit the LDS of a compute unit (generate_big).  One
+// device memory: batch_size > 32, whose (batch_size + 1)^3 tile does not fit the LDS of a compute unit (generate_big, sdf_chunked.hip).  One
 // lane per sample; blockIdx.y = the tile (FieldTile: its place in `vol`, its extents), `org` its first sample per axis.
 template <typename T, bool FULL>
 __global__ __launch_bounds__(256) void k_eval_tiles(const uint32_t *__restrict__ code, const T *__restrict__ consts,
@@ -783,16 +784,6 @@ int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, i
     return 0;
 }
 
-// a batch's first sample and its number of samples per axis: the host's copy of batch_origin (sdf_device.h)
-struct BatchBox { int ox, oy, oz, lx, ly, lz; };
-static BatchBox batch_box(const GridDesc &g, int b) {
-    const int ibz = b % g.nbz, iby = (b / g.nbz) % g.nby, ibx = b / (g.nbz * g.nby);
-    BatchBox o;
-    o.ox = ibx * g.bs; o.oy = iby * g.bs; o.oz = ibz * g.bs;
-    o.lx = std::min(g.bs + 1, g.nx - o.ox); o.ly = std::min(g.bs + 1, g.ny - o.oy); o.lz = std::min(g.bs + 1, g.nz - o.oz);
-    return o;
-}
-
 // k_mesh's dynamic LDS behind the fixed part: the float32 tile, the sign bits, the list region (which also receives the
 // batch's cull record) -- launch_mesh passes the layout to the kernel, generate_impl asks it whether a cull record fits
 struct MeshLds { size_t bits_off, list_off, list_cap; };
@@ -1319,157 +1310,12 @@ int generate_impl(sdf_mesh *m, const GenCall &call) {
     }
 }
 
-// at most this many batches per submission of the paths through device memory (generate_big, sdf_generate_field)
-enum { FIELD_CHUNK_MAX = 32 };
-
-// the tile of a batch at sample vol_off of a chunk's volume buffer
-static FieldTile field_tile(const double *X, const double *Y, const double *Z, const BatchBox &o, size_t vol_off) {
-    FieldTile tl;
-    tl.vol_off = (long long)vol_off; tl.n0 = o.lx; tl.n1 = o.ly; tl.n2 = o.lz; tl.pad_ = 0;
-    // scale = the batch's first axis step (reference sdf/core.py:58-59: `X[1] - X[0]` of the batch's slices);
-    // a one-sample axis has none and the tile has no cells, so its value is never used
-    tl.of[0] = X[o.ox]; tl.of[1] = Y[o.oy]; tl.of[2] = Z[o.oz];
-    tl.sc[0] = o.lx > 1 ? X[o.ox + 1] - X[o.ox] : 0.0; tl.sc[1] = o.ly > 1 ? Y[o.oy + 1] - Y[o.oy] : 0.0; tl.sc[2] = o.lz > 1 ? Z[o.oz + 1] - Z[o.oz] : 0.0;
-    return tl;
-}
-
-// One chunk of nt <= FIELD_CHUNK_MAX tiles whose float32 volumes (the context's field_vol) and FieldTile table (field_tiles) are
-// on the device, marched into the ordered soup behind its first `total` triangles: k_field_rows / k_scan_rows number the
-// triangles and count the ambiguous cells, the host reads the offsets and classifies the chunk's `batches` (kinds 1 = empty,
-// 2 = non-empty), the soup grows, k_field_emit writes `points * scale + offset`; waits for the chunk.  prefix (or NULL): per tile its inclusive
-// triangle prefix as a look-back word of the fused path.
-static int march_chunk(sdf_mesh *m, hipStream_t st, const int *batches, int nt, int slots, uint8_t *kinds, unsigned long long &total,
-                       unsigned long long *prefix) {
-    sdf_ctx *c = m->ctx;
-    const size_t nslots = (size_t)nt * slots;
-    // (behind the nslots row offsets: the chunk's triangle total, then its count of ambiguous cells)
-    unsigned long long *d_total = (unsigned long long *)c->rows_off.p + nslots;
-    HIPCHK(hipMemsetAsync(d_total + 1, 0, 8, st));
-    launch_k_field_rows(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                        (const FieldTile *)c->field_tiles.p, (unsigned *)c->rows.p, slots, d_total + 1);
-    launch_k_scan_rows(dim3(1), dim3(1024), st, (const unsigned *)c->rows.p, (long long)nslots, (unsigned long long *)c->rows_off.p, d_total);
-    HIPCHK(hipGetLastError());
-    // (per tile only its first slot's offset, the chunk's total and its ambiguous cells are needed on the host)
-    unsigned long long offs[FIELD_CHUNK_MAX + 2];
-    HIPCHK(hipMemcpy2DAsync(offs, 8, c->rows_off.p, (size_t)slots * 8, 8, (size_t)nt, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&offs[nt], d_total, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(stream_wait(st));
-    const unsigned long long chunk_total = offs[nt];
-    m->st.n_ambiguous_cells += (int64_t)offs[nt + 1];
-    for (int j = 0; j < nt; j++) {
-        const unsigned long long cnt = offs[j + 1] - offs[j];
-        kinds[(size_t)batches[j]] = cnt ? 2 : 1;
-        if (cnt) m->st.n_nonempty++; else m->st.n_empty++;
-        if (prefix) prefix[j] = MESH_FLAG_PFX | (total + offs[j + 1]);
-    }
-    if (!chunk_total) return 0;
-    if ((total + chunk_total) * 72 > m->out.bytes) {       // grow the soup (geometric), keeping what is there
-        DevBuf bigger;
-        if (bigger.ensure(std::max<size_t>((size_t)(total + chunk_total) * 72 * 2, (size_t)1 << 22))) return 1;
-        if (total) HIPCHK(hipMemcpyAsync(bigger.p, m->out.p, (size_t)total * 72, hipMemcpyDeviceToDevice, st));
-        HIPCHK(stream_wait(st));
-        m->out.release();
-        m->out = bigger;
-    }
-    launch_k_field_emit(dim3((unsigned)(slots / 256), (unsigned)nt), dim3(256), st, (const McTables *)c->mc.p, (const float *)c->field_vol.p,
-                        (const FieldTile *)c->field_tiles.p, (const unsigned long long *)c->rows_off.p, (double *)m->out.p, total,
-                        (unsigned long long)(m->out.bytes / 72), slots);
-    HIPCHK(hipGetLastError());
-    HIPCHK(stream_wait(st));   // (the chunk's buffers are refilled next)
-    total += chunk_total;
-    return 0;
-}
-
-// `generate` for batch_size > 32 (reference sdf/core.py:87, 114-119 takes any batch size): the (batch_size + 1)^3 float32 tile
-// of such a batch does not fit the LDS of a compute unit (33^3 = 144 KB of 160 KB does), so the fused kernels do not apply.  The
-// batches go through device memory instead, a chunk of them per submission: k_eval_tiles samples the chunk's tiles into float32
-// volumes (the interpreter, a lane per sample), k_field_rows / k_scan_rows / k_field_emit march them and write
-// `points * scale + offset` into the ordered float64 soup -- the kernels behind sdf_generate_field, with the tape instead of a
-// host callback.  The skip test is k_skip's, the work list k_compact's.  One host synchronisation per chunk: a chunk is
-// >= 2.7e5 samples per batch, the launches are long.  Synchronous; the soup lives in library memory.
-static int generate_big(sdf_mesh *m, const GenCall &call) {
-    sdf_tape *t = call.tape;
-    sdf_ctx *c = t->ctx;
-    hipStream_t st = c->stream;
-    const double *X = call.X, *Y = call.Y, *Z = call.Z;
-    const int nx = call.nx, ny = call.ny, nz = call.nz, bs = call.bs;
-    GridDesc &g = m->g;
-    int nb = 0;
-    if (grid_batches(nx, ny, nz, bs, "sdf_generate", g, nb)) return 1;
-    m->st.n_batches = nb;
-    m->st.n_grid_voxels = (int64_t)nx * ny * nz;
-    if (nb == 0) return 0;
-    if (m->axes.ensure((size_t)(nx + ny + nz) * 8) || m->kinds.ensure((size_t)nb) || m->worklist.ensure((size_t)nb * 4) ||
-        m->status.ensure((size_t)nb * 8) || m->counters.ensure(sizeof(MeshCounters)))
-        return 1;
-    double *dX = (double *)m->axes.p, *dY = dX + nx, *dZ = dY + ny;
-    g.X = dX; g.Y = dY; g.Z = dZ;
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    HIPCHK(hipMemcpyAsync(dX, X, (size_t)nx * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dY, Y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dZ, Z, (size_t)nz * 8, hipMemcpyHostToDevice, st));
-    if (call.sparse) { if (enqueue_skip(t, dX, nx, ny, nz, bs, 0, nb, call.precision, (unsigned char *)m->kinds.p, st)) return 1; }
-    else HIPCHK(hipMemsetAsync(m->kinds.p, 255, (size_t)nb, st));
-    launch_k_compact(dim3(1), dim3(1024), st, (const unsigned char *)m->kinds.p, nb, (int *)m->worklist.p, (MeshCounters *)m->counters.p,
-                     (unsigned long long *)m->status.p, (long long)call.shard_index, (long long)call.shard_count);
-    HIPCHK(hipGetLastError());
-    MeshCounters h;
-    HIPCHK(hipMemcpyAsync(&h, m->counters.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIPCHK(stream_wait(st));
-    std::vector<int> work((size_t)std::max(h.nwork, 1));
-    if (h.nwork) HIPCHK(hipMemcpy(work.data(), m->worklist.p, (size_t)h.nwork * 4, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> kinds((size_t)nb);
-    HIPCHK(hipMemcpy(kinds.data(), m->kinds.p, (size_t)nb, hipMemcpyDeviceToHost));
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    m->work_begin = h.work_begin; m->work_end = h.work_end;
-    m->st.n_skipped = nb - h.nwork;
-    m->st.n_work_begin = h.work_begin; m->st.n_work_end = h.work_end;
-
-    const size_t tile_max = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
-    const int slots = (bs * bs + 255) & ~255;                                          // row slots per tile
-    const int CH = (int)std::max<size_t>(1, std::min<size_t>(FIELD_CHUNK_MAX, ((size_t)256 << 20) / (tile_max * 4)));   // batches per submission: <= 256 MB of volumes
-    std::vector<FieldTile> tiles((size_t)CH);
-    std::vector<int> org((size_t)CH * 3);
-    if (c->field_vol.ensure((size_t)CH * tile_max * 4) || c->field_tiles.ensure(sizeof(FieldTile) * CH + (size_t)CH * 12) ||
-        c->rows.ensure((size_t)CH * slots * 4) || c->rows_off.ensure(((size_t)CH * slots + 2) * 8))
-        return 1;
-    int *d_org = reinterpret_cast<int *>((char *)c->field_tiles.p + sizeof(FieldTile) * CH);
-    unsigned long long total = 0;
-    // the look-back words of the fused path, written by the host here: per work item its inclusive triangle prefix, so that
-    // sdf_mesh_batch_offsets serves these meshes too (the counts come back per chunk anyway)
-    std::vector<unsigned long long> prefix((size_t)std::max(h.work_end - h.work_begin, 1));
-    for (int w0 = h.work_begin; w0 < h.work_end; w0 += CH) {
-        const int nt = std::min(CH, h.work_end - w0);
-        size_t npts = 0, big = 0;
-        for (int j = 0; j < nt; j++) {
-            const BatchBox o = batch_box(g, work[(size_t)(w0 + j)]);
-            tiles[(size_t)j] = field_tile(X, Y, Z, o, npts);
-            org[(size_t)3 * j] = o.ox; org[(size_t)3 * j + 1] = o.oy; org[(size_t)3 * j + 2] = o.oz;
-            const size_t n = (size_t)o.lx * o.ly * o.lz;
-            npts += n; big = std::max(big, n);
-            m->st.n_eval_voxels += (int64_t)n;
-        }
-        HIPCHK(hipMemcpyAsync(c->field_tiles.p, tiles.data(), sizeof(FieldTile) * (size_t)nt, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_org, org.data(), (size_t)nt * 12, hipMemcpyHostToDevice, st));
-        LAUNCH_TAPE_ON(st, k_eval_tiles, dim3((unsigned)((big + 255) / 256), (unsigned)nt), dim3(256), 0, t, call.precision, (const double *)dX,
-                       (const double *)dY, (const double *)dZ, (const FieldTile *)c->field_tiles.p, (const int *)d_org, (float *)c->field_vol.p);
-        if (march_chunk(m, st, &work[(size_t)w0], nt, slots, kinds.data(), total, &prefix[(size_t)(w0 - h.work_begin)])) return 1;
-    }
-    HIPCHK(hipEventRecord(c->ev[2], st));
-    m->st.n_triangles = (int64_t)total;
-    m->st.n_sampled_voxels = m->st.n_eval_voxels;
-    m->st.n_batch_instrs = (int64_t)(t->n_words / 2 - 1) * (h.work_end - h.work_begin);
-    // (work items of other shards stay 255 = "other shard", like the fused path)
-    HIPCHK(hipMemcpyAsync(m->kinds.p, kinds.data(), (size_t)nb, hipMemcpyHostToDevice, st));
-    if (h.work_end > h.work_begin)
-        HIPCHK(hipMemcpyAsync((unsigned long long *)m->status.p + h.work_begin, prefix.data(), (size_t)(h.work_end - h.work_begin) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(stream_wait(st));
-    float ms_pre = 0, ms_tot = 0;
-    HIPCHK(hipEventElapsedTime(&ms_pre, c->ev[0], c->ev[1]));
-    HIPCHK(hipEventElapsedTime(&ms_tot, c->ev[0], c->ev[2]));
-    m->st.ms_prepass = ms_pre; m->st.ms_total = ms_tot; m->st.ms_mesh = ms_tot - ms_pre;
-    m->emitted_to = nullptr;
-    return 0;
+// k_eval_tiles for the nt tiles of a chunk (sdf_chunked.hip), the largest of largest_tile samples, enqueued on `st`: the axes, the
+// tile table and the tiles' first samples `d_org` are on the device already; the caller checks the launch with the next ones
+void enqueue_eval_tiles(sdf_tape *t, int precision, const double *dX, const double *dY, const double *dZ, const FieldTile *d_tiles,
+                        const int *d_org, float *d_vol, size_t largest_tile, int nt, hipStream_t st) {
+    LAUNCH_TAPE_ON(st, k_eval_tiles, dim3((unsigned)((largest_tile + 255) / 256), (unsigned)nt), dim3(256), 0, t, precision, dX, dY, dZ,
+                   d_tiles, d_org, d_vol);
 }
 
 extern "C" {
@@ -1587,115 +1433,6 @@ int sdf_generate_records(sdf_tape *t, const double *X, int nx, const double *Y, 
     }
     m->st.n_retries = attempt;
     *out = m;
-    return 0;
-}
-
-// The batch loop of `generate` (reference sdf/core.py:114-141) around a field that lives on the HOST: a user-written
-// closure (reference README.md:258-295, sdf/d3.py:48-63), possibly calling device-resident sub-models itself.  The
-// library does what the reference's `_skip` / `_worker` do around `sdf(P)`: it builds the points of the skip test and
-// of every surviving batch (`_cartesian_product`, first axis slowest), hands them to the callback, and meshes the
-// returned values on the device -- a chunk of batches per submission: float32 cast, marching cubes of all tiles,
-// one scan for the order, `points * scale + offset` into the ordered float64 soup.
-int sdf_generate_field(sdf_ctx *c, sdf_field_fn field, void *user, const double *X, int nx, const double *Y, int ny,
-                       const double *Z, int nz, int bs, int sparse, int64_t shard_index, int64_t shard_count, sdf_mesh **out) {
-    if (!c || !field || !X || !Y || !Z || !out) return fail("sdf_generate_field: NULL argument");
-    *out = nullptr;
-    if (bs < 1 || bs > SDF_BATCH_SIZE_MAX) return fail("sdf_generate_field: batch_size must be in 1..512");
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return fail("sdf_generate_field: bad shard");
-    if (nx < 0 || ny < 0 || nz < 0) return fail("sdf_generate_field: negative axis length");
-    HIPCHK(set_device(c->device));
-    sdf_mesh *m = new sdf_mesh();
-    m->ctx = c;
-    void *h_pts = nullptr, *h_vals = nullptr;
-    struct Guard {
-        sdf_mesh *&m; void *&a; void *&b;
-        ~Guard() { const std::string keep = g_err; if (a) sdf_host_free(a); if (b) sdf_host_free(b); if (m) sdf_mesh_destroy(m); g_err = keep; }
-    } guard{m, h_pts, h_vals};
-    GridDesc &g = m->g;
-    int nb = 0;
-    if (grid_batches(nx, ny, nz, bs, "sdf_generate_field", g, nb)) return 1;
-    m->st.n_batches = nb;
-    m->st.n_grid_voxels = (int64_t)nx * ny * nz;
-    if (nb == 0) { *out = m; m = nullptr; return 0; }
-    const size_t tile_max = (size_t)(bs + 1) * (bs + 1) * (bs + 1);
-    const int slots = bs <= 32 ? 1024 : ((bs * bs + 255) & ~255);                      // row slots per tile (k_field_rows)
-    const int CH = (int)std::max<size_t>(1, std::min<size_t>(FIELD_CHUNK_MAX, ((size_t)64 << 20) / tile_max));   // batches per submission: <= 64 M points = 2 GB of pinned points + values -- except that ONE tile is always taken whole: (512 + 1)^3 points = 4.3 GB at the largest batch size
-    const size_t pts_cap = std::max<size_t>((size_t)CH * tile_max, (size_t)9 << 12);   // points per callback
-    if (sdf_host_alloc(pts_cap * 24, &h_pts) || sdf_host_alloc(pts_cap * 8, &h_vals)) return 1;
-    double *pts = (double *)h_pts, *vals = (double *)h_vals;
-    std::vector<uint8_t> kinds((size_t)nb, 255);
-
-    // ---- `_skip` (reference sdf/core.py:28-43): centre + the 8 corners of every batch through the field ----
-    if (sparse) {
-        const int per = (int)(pts_cap / 9);
-        for (int b0 = 0; b0 < nb; b0 += per) {
-            const int n = std::min(per, nb - b0);
-            for (int j = 0; j < n; j++) {
-                const BatchBox o = batch_box(g, b0 + j);
-                const double x0 = X[o.ox], x1 = X[o.ox + o.lx - 1], y0 = Y[o.oy], y1 = Y[o.oy + o.ly - 1], z0 = Z[o.oz], z1 = Z[o.oz + o.lz - 1];
-                double *p = pts + (size_t)j * 27;
-                p[0] = (x0 + x1) / 2; p[1] = (y0 + y1) / 2; p[2] = (z0 + z1) / 2;
-                for (int k = 0; k < 8; k++) {             // itertools.product((x0, x1), (y0, y1), (z0, z1))
-                    p[3 + 3 * k] = (k & 4) ? x1 : x0; p[4 + 3 * k] = (k & 2) ? y1 : y0; p[5 + 3 * k] = (k & 1) ? z1 : z0;
-                }
-            }
-            if (field(user, pts, (int64_t)n * 9, vals)) return fail("sdf_generate_field: the field callback failed");
-            for (int j = 0; j < n; j++) {
-                const BatchBox o = batch_box(g, b0 + j);
-                const double x0 = X[o.ox], y0 = Y[o.oy], z0 = Z[o.oz];
-                const double *p = pts + (size_t)j * 27, *v = vals + (size_t)j * 9;
-                const double r = fabs(v[0]);
-                const double d = sqrt(((p[0] - x0) * (p[0] - x0) + (p[1] - y0) * (p[1] - y0)) + (p[2] - z0) * (p[2] - z0));
-                bool same = true;
-                const bool pos = v[1] > 0.0;
-                for (int k = 1; k <= 8; k++) same = same && (pos ? v[k] > 0.0 : v[k] < 0.0);
-                kinds[(size_t)(b0 + j)] = (!(r <= d) && same) ? 0 : 255;
-            }
-        }
-    }
-    std::vector<int> work;
-    for (int b = 0; b < nb; b++) if (kinds[(size_t)b]) work.push_back(b);
-    const long long nwork = (long long)work.size();
-    const int w_begin = (int)((nwork * shard_index) / shard_count), w_end = (int)((nwork * (shard_index + 1)) / shard_count);
-    m->work_begin = w_begin; m->work_end = w_end;
-    m->st.n_skipped = nb - (int64_t)nwork;
-    m->st.n_work_begin = w_begin; m->st.n_work_end = w_end;
-
-    // ---- `_worker` for the shard's batches, CH at a time ----
-    std::vector<FieldTile> tiles((size_t)CH);
-    unsigned long long total = 0;
-    for (int w0 = w_begin; w0 < w_end; w0 += CH) {
-        const int nt = std::min(CH, w_end - w0);
-        size_t npts = 0;
-        for (int j = 0; j < nt; j++) {
-            const BatchBox o = batch_box(g, work[(size_t)(w0 + j)]);
-            tiles[(size_t)j] = field_tile(X, Y, Z, o, npts);
-            double *p = pts + npts * 3;
-            for (int ix = 0; ix < o.lx; ix++)
-                for (int iy = 0; iy < o.ly; iy++)
-                    for (int iz = 0; iz < o.lz; iz++, p += 3) { p[0] = X[o.ox + ix]; p[1] = Y[o.oy + iy]; p[2] = Z[o.oz + iz]; }
-            npts += (size_t)o.lx * o.ly * o.lz;
-            m->st.n_eval_voxels += (int64_t)o.lx * o.ly * o.lz;
-        }
-        if (field(user, pts, (int64_t)npts, vals)) return fail("sdf_generate_field: the field callback failed");
-        const size_t nslots = (size_t)nt * slots;
-        if (c->field_vals.ensure(npts * 8) || c->field_vol.ensure(npts * 4) || c->field_tiles.ensure(sizeof(FieldTile) * CH) ||
-            c->rows.ensure(nslots * 4) || c->rows_off.ensure((nslots + 2) * 8))
-            return 1;
-        HIPCHK(hipMemcpyAsync(c->field_vals.p, vals, npts * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->field_tiles.p, tiles.data(), sizeof(FieldTile) * (size_t)nt, hipMemcpyHostToDevice, c->stream));
-        launch_k_cast_f32(dim3((unsigned)((npts + 255) / 256)), dim3(256), c->stream, (const double *)c->field_vals.p,
-                           (float *)c->field_vol.p, (long long)npts);
-        if (march_chunk(m, c->stream, &work[(size_t)w0], nt, slots, kinds.data(), total, nullptr)) return 1;
-    }
-    m->st.n_triangles = (int64_t)total;
-    m->st.n_sampled_voxels = m->st.n_eval_voxels;
-    if (m->kinds.ensure((size_t)nb)) return 1;
-    // (work items of other shards stay 255 = "other shard", like sdf_generate)
-    HIPCHK(hipMemcpyAsync(m->kinds.p, kinds.data(), (size_t)nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(stream_wait(c->stream));
-    *out = m;
-    m = nullptr;
     return 0;
 }
 

@@ -1,11 +1,12 @@
 // sdf_internal.h -- what the handles of the C ABI (include/sdf_hip.h) point to: the context, a tape, a mesh, and the descriptor of a
-// generate call; plus the few functions of the generate pipeline (sdf_hip.hip) and of the mesh readers (sdf_mesh_out.hip) that
-// another translation unit calls.  With sdf_runtime.h, all a unit needs to define an extern "C" entry point that takes a handle.
+// generate call; plus the few functions of the generate pipeline (sdf_hip.hip), of its paths through device memory (sdf_chunked.hip)
+// and of the mesh readers (sdf_mesh_out.hip) that another translation unit calls.  With sdf_runtime.h, all a unit needs to define an extern "C" entry point that takes a handle.
 #pragma once
 #include <cstdint>
 #include <map>
 
 #include "../../include/sdf_hip.h"
+#include "sdf_chunk_plan.h"   // (SDF_BATCH_SIZE_MAX)
 #include "sdf_device.h"
 #include "sdf_runtime.h"
 
@@ -29,7 +30,6 @@ struct CallSlot {
     hipStream_t stream = nullptr;                                         // the lane asynchronous calls of this slot run on
     DevBuf park;                                                          // ... and its k_mesh staging slots
 };
-#define SDF_BATCH_SIZE_MAX 512   // (513^3 float32 = 540 MB per tile: generate_big takes one tile per submission there)
 #define SDF_PARK_TRIS 8192   // triangles per workgroup staging slot of k_mesh (36 bytes each); larger batches wait instead
                              // (16 slots per workgroup: 1.2 GB per call lane, allocated on a lane's first use; with 4096
                              // per slot weave at 2^33 has batches that cannot park: 30.3 instead of 27.7 ms)
@@ -42,7 +42,7 @@ struct sdf_ctx {
     size_t lds_max = 0;
     DevBuf scratch_in, scratch_out, rows, rows_off, mc;
     DevBuf ext;                       // closure points / values of sdf_eval_*extern* (L_EXTERN leaves)
-    DevBuf field_vals, field_vol, field_tiles;   // sdf_generate_field: a chunk's sampled values (f64), volumes (f32), tile table
+    DevBuf field_vals, field_vol, field_tiles;   // sdf_chunked.hip: a chunk's sampled values (f64, sdf_generate_field), volumes (f32), tile table
     DevBuf prof;                      // SDF_MESH_PROF=1: per-phase cycle counters of k_mesh (diagnostics)
     int prune = 1;                    // SDF_PRUNE=0 switches the interval prepass off (diagnostics)
     int parking = 1;                  // SDF_PARK=0: k_mesh waits for its predecessors instead of parking a batch (diagnostics)
@@ -179,8 +179,13 @@ inline GenCall gen_call(sdf_tape *t, const double *X, int nx, const double *Y, i
 int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb);
 int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
                  unsigned char *d_kinds, hipStream_t st);
+struct FieldTile;   // (sdf_plain.h)
+void enqueue_eval_tiles(sdf_tape *t, int precision, const double *dX, const double *dY, const double *dZ, const FieldTile *d_tiles,
+                        const int *d_org, float *d_vol, size_t largest_tile, int nt, hipStream_t st);
 int generate_impl(sdf_mesh *m, const GenCall &call);
 int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, sdfk::MeshCounters &h);
+// ---- sdf_chunked.hip (batch_size > 32: through device memory, a chunk of batches per submission) ----
+int generate_big(sdf_mesh *m, const GenCall &call);
 // ---- sdf_mesh_out.hip ----
 int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes);
 // ---- sdf_weld.hip: pts = n rows of 3 doubles on the device; on success *d_uniq (3 * *n_unique doubles) and *d_inv (n int64) are

@@ -4,8 +4,8 @@
 #pragma once
 #include "sdf_device.h"
 
-// ---- marching cubes of MANY caller-supplied tiles in one submission (sdf_generate_field: the volumes of a
-// chunk of batches sampled by a host callback; generate_big: batch_size > 32, sampled by k_eval_tiles).  A tile
+// ---- marching cubes of MANY caller-supplied tiles in one submission (sdf_chunked.hip -- sdf_generate_field: the volumes
+// of a chunk of batches sampled by a host callback; generate_big: batch_size > 32, sampled by k_eval_tiles).  A tile
 // has at most `slots` rows of cells (1024 for batch_size <= 32; a multiple of 256); row slot tile * slots + t
 // carries the row's triangle count (0 beyond the tile's rows), so one scan over the slots numbers the triangles
 // of the whole chunk in reference order.  k_field_rows also adds the chunk's ambiguous surface cells to *n_ambiguous,

@@ -165,7 +165,7 @@ def _job(eng, tape, X, Y, Z, batch_size, sparse, device, group, chunks):
         chunks = int(os.environ.get('SDF_DIST_CHUNKS', '1'))
     C = max(1, min(int(chunks), MAX_SLABS // max(world, 1)))
     # sdf_expand_slabs takes at most MAX_SLABS slabs per call: a larger world ships the float64 soup through host memory
-    # (batch_size > 32 goes through device memory in chunks, csrc generate_big: its soup comes back like a closure model's)
+    # (batch_size > 32 goes through device memory in chunks, csrc/sdf_chunked.hip generate_big: its soup comes back like a closure model's)
     on_device = device.type == 'cuda' and hasattr(eng, 'generate_compact') and not externs and world * C <= MAX_SLABS and int(batch_size) <= 32
     codec = DeviceCodec(eng) if on_device else HostCodec(eng)
     s = int(batch_size)

@@ -1,4 +1,4 @@
-"""batch_size > 32 (csrc/sdf_hip.hip generate_big / march_chunk: k_eval_tiles, k_field_rows / k_scan_rows / k_field_emit) and the
+"""batch_size > 32 (csrc/sdf_chunked.hip generate_big / march_chunk: k_eval_tiles, k_field_rows / k_scan_rows / k_field_emit) and the
 mesh readers behind it, against the CPU checker and the readers' host definitions: every model family and both tape families,
 every chunk length, a tile whose rows fill every row slot, a soup regrown while it holds triangles, ragged and degenerate grids,
 every reader on meshes of every producer, the public entry points, and the count of ambiguous cells on both paths.
