@@ -327,7 +327,9 @@ __global__ __launch_bounds__(256) void k_stl(const double *__restrict__ pts, lon
     const float bx = p[6] - p[0], by = p[7] - p[1], bz = p[8] - p[2];
     // np.cross / np.linalg.norm in float32: separate, individually rounded products, sums and the
     // quotient (the translation unit is built with -ffp-contract=off; sqrtf and '/' are the
-    // correctly rounded forms, the __f*_rn intrinsics map to native approximations here)
+    // correctly rounded forms, the __f*_rn intrinsics map to native approximations here).  A degenerate triangle's normal
+    // is 0/0: the division writes 0xffc00000 for it, the word NumPy writes on x86-64, and the float32 denormals of a tiny
+    // cross product are kept, not flushed (tests/test_mesh_readers_gpu.py holds both to the reference's bytes)
     float nx = ay * bz - az * by;
     float ny = az * bx - ax * bz;
     float nz = ax * by - ay * bx;

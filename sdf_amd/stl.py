@@ -13,7 +13,14 @@ _RECORD = np.dtype([
 
 
 def stl_records(points):
-    """the 50-byte records of `write_binary_stl` as a structured array"""
+    """the 50-byte records of `write_binary_stl` as a structured array.
+
+    The contract, for this function and for the device's records (`Mesh.stl_records`, k_stl) alike, against the file the reference
+    writes (tests/golden/stl_soups.npz, tests/test_mesh_readers_*.py).  Class A -- every coordinate finite and at most 2^60 in
+    magnitude after the float32 cast, which covers everything `generate` emits: byte-identical, the NaN normal of a degenerate
+    triangle included (0/0 in float32: the word 0xffc00000) and the +-inf normal of a triangle whose cross product is a float32
+    denormal.  Class B -- a coordinate that is NaN, +-inf or overflows float32, or so large that the cross product overflows:
+    NaN in the same 32-bit words, every other word bit-equal; WHICH NaN depends on the operand order inside NumPy's build."""
     tri = np.asarray(points, dtype='float32').reshape((-1, 3, 3))
     rec = np.zeros(len(tri), dtype=_RECORD)
     e1 = tri[:, 1] - tri[:, 0]
