@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SDF_ABI_VERSION 16
+#define SDF_ABI_VERSION 17
 
 #define SDF_PRECISION_F64 0 /* float64 evaluation like the reference's NumPy path: what every sdf_generate* entry point samples in */
 #define SDF_PRECISION_F32 1 /* float32 evaluation: sdf_eval_* and sdf_estimate_bounds only (the meshing path refuses it since round 5) */
@@ -442,6 +442,31 @@ int sdf_mesh_select_shells(sdf_mesh *mesh, const unsigned char *h_keep, int64_t 
 /* the kernels of this thread's last sdf_mesh_components that computed (labelling + numbering + counts) or sdf_mesh_select_shells
  * (flags + scan + copy) alone, milliseconds by HIP events (tools/shells_time.py) */
 double sdf_mesh_components_last_kernel_ms(void);
+/* The mesh simplified on the device (ABI 17; DESIGN.md section 4j, defined by tests/simplify_ref.py and reproduced bit for bit):
+ * vertex clustering on the uniform grid (origin3, cell3) -- the cluster of a welded vertex is floor((p - origin) / cell) per axis,
+ * clusters are numbered by ascending key x << 42 | y << 21 | z of their cell relative to the smallest one -- with one representative
+ * per cluster placed by a quadric error function: the planes of the triangles that touch the cluster, weighted by their squared
+ * area, regularised by reg x trace towards the mean of the cluster's vertices, solved in closed form; a representative that is not
+ * finite or leaves its cell is replaced by that mean (`mean_fallback`), a cluster of zero-area triangles only takes the mean too
+ * (`flat`).  A triangle survives if its three clusters differ; survivors keep their order and winding (`collapsed` counts the
+ * others).  Duplicate triangles and oppositely wound pairs are NOT removed (sdf_mesh_edge_census reports them), and topology is
+ * not preserved.  Every float sum is sequential in the definition's order (one lane per cluster): the result does not depend on
+ * launch geometry or the order of atomics.  sdf_mesh_simplify welds the source first if that has not happened; it serves generated
+ * meshes, meshes of sdf_generate_records, adopted soups and selections.  The new mesh OWNS its soup, like a selection's, and is what
+ * an adopted soup is for every reader; the source mesh stays valid and unchanged.  One scratch allocation, freed before the call
+ * returns whether it fails or not.  A mesh of 0 triangles gives a mesh of 0 triangles without a launch.  kernel_ms: the kernels
+ * alone, by HIP events.  Refused on the host before anything is allocated or launched, with return value 2: a NULL argument, a
+ * cell that is not positive and finite, an origin that is not finite, a reg that is negative or not finite, 2^31 or more corners
+ * (3 x triangles) or vertices.  Found after the first pass over the vertices, with return value 1 and nothing left allocated: a
+ * vertex that is not finite, clusters that span 2^21 or more cells on an axis.  *out is written on success only. */
+typedef struct sdf_simplify_stats {
+    int64_t clusters, triangles_in, triangles_out, collapsed, mean_fallback, flat;
+    double kernel_ms;
+} sdf_simplify_stats;
+int sdf_mesh_simplify(sdf_mesh *mesh, const double *origin3, const double *cell3, double reg, sdf_mesh **out, sdf_simplify_stats *stats);
+/* the kernels of this thread's last sdf_mesh_simplify, milliseconds by HIP events; parts4 (or NULL): keys and numbering, the item
+ * sort and its segments, k_cluster_vertex, live flags and emission (tools/simplify_time.py) */
+double sdf_mesh_simplify_last_kernel_ms(double *parts4);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -150,9 +150,10 @@ def grid_axes(bounds, step=None, samples=SAMPLES):
     return X, Y, Z, (dx, dy, dz)
 
 
-Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', 'bounds', 'stats'))
-Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=), or None when a multi-process
-run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape, engine, bounds, stats: the call's."""
+Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', 'bounds', 'stats', 'simplify_stats'), defaults=(None,))
+Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=, the simplified mesh under
+simplify=), or None when a multi-process run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape,
+engine, bounds, stats: the call's; simplify_stats: the dict of `engine.Mesh.simplify`, or None without simplify=."""
 
 
 @contextlib.contextmanager
@@ -160,16 +161,21 @@ def meshed(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, *, keep=None, to_host=False):
+        verbose=True, sparse=True, *, keep=None, simplify=None, to_host=False):
     """the one path from a model to its mesh on the device: the arguments of `generate`, `keep` (only these
     connected shells, `shells.resolve_keep`: the device mesh is labelled, the kept shells are compacted into a mesh of their own
-    and THAT is yielded; section 4h) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
+    and THAT is yielded; section 4h), `simplify` (a real number k > 0, `simplify.check_simplify`: after keep, the mesh is simplified on
+    the device in clusters of k^3 grid cells, `engine.Mesh.simplify`, and the simplified mesh is what is yielded and what the closing
+    line counts; section 4j) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
     16-byte records).  Yields a `Meshed`, which the readers below take; closes what it opened on the way out, and after a body
     that did not raise prints the two closing lines of the reference and sets `generate.last_stats`."""
     from . import engine, dist
     if keep is not None:
         from .shells import check_keep, resolve_keep, shells_of_mesh
         check_keep(keep)      # (before anything is meshed)
+    if simplify is not None:
+        from .simplify import check_simplify, resolve_cell
+        check_simplify(simplify)
     start = time.time()
     eng = engine.get_engine()
     tape = eng.tape_for(sdf)
@@ -192,7 +198,7 @@ def meshed(
         num_samples = overlapped(len(X)) * overlapped(len(Y)) * overlapped(len(Z))
         print('%d samples in %d batches with %d workers' % (num_samples, num_batches, workers))
 
-    mesh = points = soup = None
+    mesh = points = soup = simplify_stats = None
     try:
         if dist.world_size() > 1:
             soup, stats = dist.generate_sharded_device(eng, tape, X, Y, Z, batch_size, sparse)
@@ -215,7 +221,15 @@ def meshed(
             sel = mesh.select(resolve_keep(keep, got))
             mesh.close()
             mesh = sel
-        yield Meshed(mesh, points, tape, eng, bounds, stats)
+        if simplify is not None:
+            if mesh is None:
+                raise NotImplementedError('simplify: the soup of this multi-process run was gathered on the host; a mesh is simplified on '
+                                          'the device only (run it in one process, or with a device-resident exchange)')
+            small = mesh.simplify(*resolve_cell(simplify, X, Y, Z, (dx, dy, dz)))
+            mesh.close()
+            mesh = small
+            simplify_stats = small.simplify_stats
+        yield Meshed(mesh, points, tape, eng, bounds, stats, simplify_stats)
         triangles = mesh.n_triangles if mesh is not None else len(points) // 3
     finally:
         if mesh is not None:
@@ -315,32 +329,42 @@ def generate(
 generate.last_stats = None
 
 
-def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, **generate_kwargs):
+def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None, **generate_kwargs):
     """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
     welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
     difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
     value).  The normals point outward for this library's winding; a vertex where the field has no gradient gets (0, 0, 0)
     (`generate_mesh.last_flat` counts them).  keep: only these connected shells of the mesh (`shells.resolve_keep`: 'largest', a
-    count, a boolean mask over the shells, a callable).  Not in the reference."""
+    count, a boolean mask over the shells, a callable).  simplify: a real number k > 0 -- the mesh simplified on the
+    device in clusters of k^3 grid cells, after keep (`sdf_amd/simplify.py`; `generate_mesh.last_simplify` holds
+    its statistics); the normals are then the field's at the NEW vertices.  Not in the reference."""
+    if simplify is not None:      # (simplify=None is the call without the argument)
+        generate_kwargs['simplify'] = simplify
     with meshed(sdf, keep=keep, **generate_kwargs) as m:
         got = read_export(m, bool(normals), normal_eps)
+        generate_mesh.last_simplify = m.simplify_stats
     generate_mesh.last_flat = got['n_flat']
     return got['points'], got['cells'], got['normals']
 
 
 generate_mesh.last_flat = 0
+generate_mesh.last_simplify = None
 
 
-def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, **kwargs):
+def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
     these connected shells of the mesh -- 'largest', the n largest, a boolean mask over the shells, a callable (`shells.resolve_keep`;
-    DESIGN.md section 4h) --, selected on the device before anything is written."""
+    DESIGN.md section 4h) --, selected on the device before anything is written.  simplify: a real number k > 0 -- after keep, the mesh
+    is simplified on the device in clusters of k^3 grid cells and the file holds the simplified mesh: about k^2 times fewer triangles
+    cross the link and reach the disk (`sdf_amd/simplify.py`)."""
     from . import meshfile
     path = os.fspath(path)
     how = meshfile.choose_writer(path, writer, normals)
     ply = path.lower().endswith('.ply')
+    if simplify is not None:      # (simplify=None is the call without the argument)
+        kwargs['simplify'] = simplify
     with meshed(*args, keep=keep, **kwargs) as m:
         if how == 'native':
             got = read_export(m, bool(normals), normal_eps, ply)

@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals at the welded vertices,
-// binary PLY records, the moments and the edge census, the connected shells and a selection of them, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -13,6 +13,7 @@
 #include "sdf_measure.h"
 #include "sdf_normals.h"
 #include "sdf_plain.h"
+#include "sdf_simplify.h"
 
 using namespace sdfk;
 
@@ -458,6 +459,44 @@ int sdf_mesh_select_shells(sdf_mesh *m, const unsigned char *h_keep, int64_t n_k
 }
 
 double sdf_mesh_components_last_kernel_ms(void) { return g_components_kernel_ms; }
+
+// ---- the mesh simplified: clusters of the welded vertices, quadric representatives, the survivors as a mesh of its own ----
+static thread_local double g_simplify_kernel_ms[4] = {0.0, 0.0, 0.0, 0.0};
+
+int sdf_mesh_simplify(sdf_mesh *m, const double *origin3, const double *cell3, double reg, sdf_mesh **out, sdf_simplify_stats *stats) {
+    if (!m || !origin3 || !cell3 || !out || !stats) { fail("sdf_mesh_simplify: NULL argument"); return 2; }
+    for (int k = 0; k < 3; k++) {
+        if (!(std::isfinite(cell3[k]) && cell3[k] > 0.0)) { fail("sdf_mesh_simplify: cell must be positive and finite"); return 2; }
+        if (!std::isfinite(origin3[k])) { fail("sdf_mesh_simplify: origin must be finite"); return 2; }
+    }
+    if (!(std::isfinite(reg) && reg >= 0.0)) { fail("sdf_mesh_simplify: reg must be finite and not negative"); return 2; }
+    MESH_READY(m);
+    const long long nt = (long long)m->st.n_triangles;
+    if (3 * nt >= (1ll << 31)) { fail("sdf_mesh_simplify: 2^31 or more corners or vertices"); return 2; }
+    *stats = sdf_simplify_stats();
+    DevBuf soup;                                                       // the survivors' own soup: the new mesh's `out`
+    if (nt > 0) {                                                      // (no triangles: a mesh of 0 triangles, no launch)
+        int64_t nu = 0;
+        if (sdf_mesh_weld(m, &nu)) return 1;
+        HIPCHK(set_device(m->ctx->device));
+        if (simplify_device(m->ctx->stream, m->weld_pts, m->weld_inv, m->weld_n, nt, origin3, cell3, reg, &soup, stats, g_simplify_kernel_ms)) {
+            soup.release();
+            *stats = sdf_simplify_stats();
+            return 1;
+        }
+    }
+    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
+    s->ctx = m->ctx;
+    s->out = soup;
+    s->st.n_triangles = stats->triangles_out;
+    *out = s;
+    return 0;
+}
+
+double sdf_mesh_simplify_last_kernel_ms(double *parts4) {
+    for (int k = 0; parts4 && k < 4; k++) parts4[k] = g_simplify_kernel_ms[k];
+    return g_simplify_kernel_ms[0] + g_simplify_kernel_ms[1] + g_simplify_kernel_ms[2] + g_simplify_kernel_ms[3];
+}
 
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
     if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }

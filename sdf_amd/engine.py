@@ -59,6 +59,14 @@ class SdfComponents(ctypes.Structure):
                [(k, ctypes.c_double) for k in ('ms_label', 'ms_number')]
 
 
+SIMPLIFY_FIELDS = ('clusters', 'triangles_in', 'triangles_out', 'collapsed', 'mean_fallback', 'flat')
+
+
+class SdfSimplifyStats(ctypes.Structure):
+    """mirror of `sdf_simplify_stats` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in SIMPLIFY_FIELDS] + [('kernel_ms', ctypes.c_double)]
+
+
 class SdfStats(ctypes.Structure):
     """mirror of `sdf_stats` in include/sdf_hip.h"""
     _fields_ = [
@@ -171,13 +179,15 @@ ABI = {
                                                  ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _f64p]),
     'sdf_mesh_select_shells': (ctypes.c_int, [_vp, _u8p, _c_i64, ctypes.POINTER(_vp)]),
     'sdf_mesh_components_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_simplify': (ctypes.c_int, [_vp, _f64p, _f64p, ctypes.c_double, ctypes.POINTER(_vp), ctypes.POINTER(SdfSimplifyStats)]),
+    'sdf_mesh_simplify_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
     'sdf_mesh_prune_masks': (ctypes.c_int, [_vp, _u32p]),
     'sdf_mesh_destroy': (ctypes.c_int, [_vp]),
 }
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 def build_info():
@@ -547,6 +557,27 @@ class Mesh:
         _check(eng.lib, eng.lib.sdf_mesh_select_shells(self.handle, _dp(mask, _u8p), len(mask), ctypes.byref(h)))
         m = Mesh(eng, h)
         m.emitted = False
+        return m
+
+    def simplify(self, origin, cell, reg=1e-3):
+        """a new Mesh: this one simplified on the device (sdf_mesh_simplify, csrc/sdf_simplify.hip; defined by
+        tests/simplify_ref.py and reproduced bit for bit).  The welded vertices are clustered on the uniform grid (origin (3,), cell
+        (3,) > 0), every cluster gets one representative placed by its quadric (regularised by reg towards the mean of its vertices,
+        kept inside its cell), and the triangles whose three clusters differ survive, in order and winding.  Duplicates and
+        oppositely wound pairs are not removed (`edge_census` reports them).  The result owns its soup and serves every reader;
+        its `simplify_stats` is a dict of clusters, triangles_in, triangles_out, collapsed, mean_fallback, flat and kernel_ms.
+        This mesh stays valid.  ValueError, before any device work, for a cell that is not positive and finite, an origin that
+        is not finite or a negative reg; SdfHipError for a vertex that is not finite or a cell too small for the key."""
+        eng = self.engine
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(cell, dtype=np.float64).reshape(-1)
+        if o.shape != (3,) or c.shape != (3,):
+            raise ValueError('simplify: origin and cell have 3 components each, got %r and %r' % (origin, cell))
+        h, st = _vp(), SdfSimplifyStats()
+        _check(eng.lib, eng.lib.sdf_mesh_simplify(self.handle, _dp(o, _f64p), _dp(c, _f64p), float(reg), ctypes.byref(h), ctypes.byref(st)))
+        m = Mesh(eng, h)
+        m.emitted = False
+        m.simplify_stats = dict({k: int(getattr(st, k)) for k in SIMPLIFY_FIELDS}, kernel_ms=float(st.kernel_ms))
         return m
 
     def stl_records(self):

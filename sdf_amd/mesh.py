@@ -107,6 +107,22 @@ class Mesh:
         from .shells import shells_of_soup
         return shells_of_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)])
 
+    def simplify(self, cell, origin=None, reg=1e-3):
+        """this mesh simplified on the device (sdf_amd/simplify.py): a new Mesh of the welded result.  cell: the
+        edge of a cluster, a scalar or one per axis; origin: the corner of the clustering grid (default: the minimum of the bounding
+        box); reg: the regularisation of the quadric towards the mean of a cluster's vertices"""
+        from . import core
+        pts = np.asarray(self.points, dtype=np.float64)
+        c = np.broadcast_to(np.asarray(cell, dtype=np.float64), (3,)).copy()
+        o = pts.min(axis=0) if origin is None and len(pts) else np.zeros(3) if origin is None else np.asarray(origin, dtype=np.float64)
+        with core.adopted(pts[np.asarray(self.triangles)]) as mesh:
+            small = mesh.simplify(o, c, reg)
+            try:
+                points, cells = small.weld()
+                return Mesh(np.array(points), np.array(cells))
+            finally:
+                small.close()
+
     @property
     def bounding_box(self):
         lo, hi = self.points.min(axis=0), self.points.max(axis=0)

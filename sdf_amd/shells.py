@@ -35,19 +35,20 @@ def shells_of_soup(soup):
         return shells_of_mesh(mesh)
 
 
-def _meshed(sdf, generate_kwargs):
-    """`core.meshed` for `shells` and `measure_shells`: the arguments of `generate`, nothing printed, one process"""
+def _meshed(sdf, generate_kwargs, simplify=None):
+    """`core.meshed` for `shells` and `measure_shells`: the arguments of `generate`, nothing printed, one process; simplify: the
+    shells are those of the simplified mesh (`sdf_amd/simplify.py`)"""
     from . import core, dist
     if dist.world_size() > 1:
         raise NotImplementedError('shells: a multi-process run gathers its soup per step; label it in one process, or adopt the '
                                   'gathered soup (Engine.adopt_soup) and use shells_of_mesh')
-    return core.meshed(sdf, keep=None, to_host=False, **dict(generate_kwargs, verbose=False))
+    return core.meshed(sdf, keep=None, simplify=simplify, to_host=False, **dict(generate_kwargs, verbose=False))
 
 
-def shells(sdf, **generate_kwargs):
+def shells(sdf, simplify=None, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`) and label the connected shells of the welded mesh there: only the
-    Shells cross the link, not the soup"""
-    with _meshed(sdf, generate_kwargs) as m:
+    Shells cross the link, not the soup.  simplify: label the mesh simplified in clusters of simplify^3 grid cells"""
+    with _meshed(sdf, generate_kwargs, simplify) as m:
         return shells_of_mesh(m.mesh)
 
 
@@ -57,12 +58,12 @@ def largest_first(triangles):
     return np.lexsort((np.arange(len(t)), -t))
 
 
-def measure_shells(sdf, limit=None, **generate_kwargs):
+def measure_shells(sdf, limit=None, simplify=None, **generate_kwargs):
     """a list of `Measurement` (sdf_amd/measure.py), one per shell, largest first by triangle count (ties: the lower shell number);
     `limit` bounds how many.  The model is meshed ONCE; then every shell costs one selection (a compaction of the soup) plus one
     measure (moments, weld, census) on the device, so ask for `limit` shells when the crumbs are many.  A sealed cavity is
-    recognisable by its negative `volume`."""
-    with _meshed(sdf, generate_kwargs) as m:
+    recognisable by its negative `volume`.  simplify: the shells of the mesh simplified in clusters of simplify^3 grid cells."""
+    with _meshed(sdf, generate_kwargs, simplify) as m:
         return measure_shells_of_mesh(m.mesh, limit)
 
 
