@@ -16,11 +16,11 @@ struct ShellParts {
 size_t shell_block_bytes(long long n_vertices, long long n_tris, long long n_shells);
 ShellParts shell_parts(void *block, long long n_vertices, long long n_tris, long long n_shells);
 // d_cells: n_tris x 3 int64 indices below n_vertices, d_points: n_vertices x 3 float64 (the weld's; 1 <= n_tris, n_vertices < 2^31).
-// On success *d_block is a device block the caller owns (hipFree), laid out as above for *n_shells shells; *rounds: the hook passes
+// On success *block holds the device block laid out as above for *n_shells shells (a failed call leaves it empty); *rounds: the hook passes
 // run, the verifying one included; kernel_ms[0]: labelling (with the host's look at the counter between the rounds), kernel_ms[1]:
 // numbering, counts and boxes, by HIP events
 int components_label(hipStream_t st, const long long *d_cells, const double *d_points, long long n_tris, long long n_vertices,
-                     void **d_block, long long *n_shells, int *rounds, double kernel_ms[2]);
+                     DevBlock *block, long long *n_shells, int *rounds, double kernel_ms[2]);
 // the triangles of d_soup (n_tris x 9 float64) whose shell k has h_keep[k] != 0, in soup order, into `out` (grown as needed; left
 // alone when nothing is kept); *n_kept: how many
 int components_select(hipStream_t st, const double *d_soup, long long n_tris, const int *d_triangle_shell, const unsigned char *h_keep,

@@ -20,14 +20,15 @@
 //
 // Selection: a flag per triangle from keep[shell], a library exclusive scan, and a copy with one lane per double of the source soup.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include <cstring>
 #include <string>
+#include <utility>
 
 #include "sdf_components.h"
 #include "sdf_measure.h"
+#include "sdf_prims.h"
 
 namespace sdfk {
 
@@ -122,8 +123,7 @@ __global__ __launch_bounds__(256) void k_shell_clear(unsigned long long *__restr
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n_shells) { triangles[i] = 0ull; vertices[i] = 0ull; }
     if (i < 6 * n_shells) {
-        const unsigned long long pinf = 0x7ff0000000000000ull | (1ull << 63);
-        box[i] = (i % 6) < 3 ? pinf : ~pinf;
+        box[i] = (i % 6) < 3 ? BOX_EMPTY_LO : BOX_EMPTY_HI;
     }
 }
 
@@ -252,12 +252,10 @@ void shell_bounds(const unsigned long long *h_keys, long long n_shells, double *
     }
 }
 
-static unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
-
 int components_label(hipStream_t st, const long long *d_cells, const double *d_points, long long n_tris, long long n_vertices,
-                     void **d_block, long long *n_shells, int *rounds, double kernel_ms[2]) {
+                     DevBlock *block, long long *n_shells, int *rounds, double kernel_ms[2]) {
     static const char who[] = "sdf_mesh_components: ";
-    *d_block = nullptr; *n_shells = 0; *rounds = 0;
+    block->reset(); *n_shells = 0; *rounds = 0;
     if (n_tris < 1 || n_vertices < 1 || n_tris >= (1ll << 31) || n_vertices >= (1ll << 31))
         return fail(std::string(who) + "the triangle or vertex count is out of range");
     // one merging round and the verifying one are what the scheme needs; the loop allows what root hooking
@@ -266,70 +264,54 @@ int components_label(hipStream_t st, const long long *d_cells, const double *d_p
     for (long long x = 1; x < n_vertices; x <<= 1) max_rounds += 1;
     if (n_vertices < 2) max_rounds = 3;
     unsigned h_hooking = 0;
-    int h_last[2] = {0, 0};                                            // the last vertex: its rank, its flag
     unsigned *parent, *d_hooking;
     int *flags, *rank;
     unsigned char *tmp;
     size_t tmp_bytes = 0;
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, (int)n_vertices, st));
-    // the block the mesh keeps if all goes well; it goes back on every other path, once the stream has drained
-    struct Kept { hipStream_t st; void *p; ~Kept() { if (p) { (void)stream_wait(st); (void)hipFree(p); } } } kept{st, nullptr};
+    HIPCHK_MSG(who, scan_tmp_bytes(st, n_vertices, &tmp_bytes));
+    DevBlock kept;                                                     // the block the mesh keeps if all goes well; it goes back on every other path
     Scratch scratch(st);                                               // (declared after the host copies: it waits for the stream before they go)
     scratch.part(&parent, (size_t)n_vertices);
     scratch.part(&flags, (size_t)n_vertices);
     scratch.part(&rank, (size_t)n_vertices);
-    scratch.part(&tmp, tmp_bytes ? tmp_bytes : 1);
+    scratch.part(&tmp, tmp_bytes);
     scratch.part(&d_hooking, (size_t)max_rounds);
     HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
     HIPCHK_MSG(who, hipMemsetAsync(d_hooking, 0, (size_t)max_rounds * 4, st));
     EventTimer t_label, t_number;
     HIPCHK_MSG(who, t_label.start(st));
-    hipLaunchKernelGGL(k_shell_init, dim3(blocks_of(n_vertices)), dim3(256), 0, st, parent, n_vertices);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_shell_init, n_vertices, st, parent, n_vertices));
     int r = 0;
     for (;;) {
         if (r == max_rounds) return fail(std::string(who) + "the labelling did not settle within " + std::to_string(max_rounds) + " rounds");
-        hipLaunchKernelGGL(k_shell_hook, dim3(blocks_of(n_tris)), dim3(256), 0, st, d_cells, n_tris, parent, d_hooking + r);
-        HIPCHK_MSG(who, hipGetLastError());
+        HIPCHK_MSG(who, launch_rows(k_shell_hook, n_tris, st, d_cells, n_tris, parent, d_hooking + r));
         HIPCHK_MSG(who, hipMemcpyAsync(&h_hooking, d_hooking + r, 4, hipMemcpyDeviceToHost, st));
         HIPCHK_MSG(who, stream_wait(st));
         r += 1;
         if (h_hooking == 0) break;                                     // a full pass found every cell under one root: parent[] is as the last compression left it
-        hipLaunchKernelGGL(k_shell_compress, dim3(blocks_of(n_vertices)), dim3(256), 0, st, parent, n_vertices);
-        HIPCHK_MSG(who, hipGetLastError());
+        HIPCHK_MSG(who, launch_rows(k_shell_compress, n_vertices, st, parent, n_vertices));
     }
     HIPCHK_MSG(who, t_label.stop(st));
-    hipLaunchKernelGGL(k_shell_roots, dim3(blocks_of(n_vertices)), dim3(256), 0, st, (const unsigned *)parent, n_vertices, flags);
-    HIPCHK_MSG(who, hipGetLastError());
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, rank, (int)n_vertices, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[0], rank + (n_vertices - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[1], flags + (n_vertices - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, stream_wait(st));
-    const long long k = (long long)h_last[0] + h_last[1];
-    if (k < 1 || k > n_vertices) return fail(std::string(who) + "the scan of the roots is inconsistent");
+    HIPCHK_MSG(who, launch_rows(k_shell_roots, n_vertices, st, parent, n_vertices, flags));
+    long long k = 0;
+    if (number_flags(who, "roots", st, flags, rank, n_vertices, tmp, tmp_bytes, &k)) return 1;
+    if (k < 1) return fail(std::string(who) + "the scan of the roots is inconsistent");
     const size_t bytes = shell_block_bytes(n_vertices, n_tris, k);
-    HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(bytes) + "): ", dev_malloc(&kept.p, bytes));
-    const ShellParts sp = shell_parts(kept.p, n_vertices, n_tris, k);
+    HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(bytes) + "): ", kept.alloc(bytes, st));
+    const ShellParts sp = shell_parts(kept.as<void>(), n_vertices, n_tris, k);
     HIPCHK_MSG(who, t_number.start(st));
-    hipLaunchKernelGGL(k_shell_of_vertex, dim3(blocks_of(n_vertices)), dim3(256), 0, st, (const unsigned *)parent, (const int *)rank, n_vertices, sp.vertex_shell);
-    HIPCHK_MSG(who, hipGetLastError());
-    hipLaunchKernelGGL(k_shell_of_cell, dim3(blocks_of(n_tris)), dim3(256), 0, st, d_cells, (const int *)sp.vertex_shell, n_tris, sp.triangle_shell);
-    HIPCHK_MSG(who, hipGetLastError());
-    hipLaunchKernelGGL(k_shell_clear, dim3(blocks_of(6 * k)), dim3(256), 0, st, sp.triangles, sp.vertices, sp.box, k);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_shell_of_vertex, n_vertices, st, parent, rank, n_vertices, sp.vertex_shell));
+    HIPCHK_MSG(who, launch_rows(k_shell_of_cell, n_tris, st, d_cells, sp.vertex_shell, n_tris, sp.triangle_shell));
+    HIPCHK_MSG(who, launch_rows(k_shell_clear, 6 * k, st, sp.triangles, sp.vertices, sp.box, k));
     const unsigned v_grid = blocks_of(n_vertices) < TALLY_MAX_BLOCKS ? blocks_of(n_vertices) : TALLY_MAX_BLOCKS;
     const unsigned t_grid = blocks_of(n_tris) < TALLY_MAX_BLOCKS ? blocks_of(n_tris) : TALLY_MAX_BLOCKS;
-    hipLaunchKernelGGL(k_shell_tally<true>, dim3(v_grid), dim3(256), 0, st, (const int *)sp.vertex_shell, n_vertices, d_points, sp.vertices, sp.box);
-    HIPCHK_MSG(who, hipGetLastError());
-    hipLaunchKernelGGL(k_shell_tally<false>, dim3(t_grid), dim3(256), 0, st, (const int *)sp.triangle_shell, n_tris, (const double *)nullptr, sp.triangles,
-                       (unsigned long long *)nullptr);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_grid(k_shell_tally<true>, v_grid, st, sp.vertex_shell, n_vertices, d_points, sp.vertices, sp.box));
+    HIPCHK_MSG(who, launch_grid(k_shell_tally<false>, t_grid, st, sp.triangle_shell, n_tris, nullptr, sp.triangles, nullptr));
     HIPCHK_MSG(who, t_number.stop(st));
     HIPCHK_MSG(who, stream_wait(st));
     HIPCHK_MSG(who, t_label.ms(&kernel_ms[0]));
     HIPCHK_MSG(who, t_number.ms(&kernel_ms[1]));
-    *d_block = kept.p;
-    kept.p = nullptr;
+    *block = std::move(kept);
     *n_shells = k;
     *rounds = r;
     return 0;
@@ -340,33 +322,25 @@ int components_select(hipStream_t st, const double *d_soup, long long n_tris, co
     static const char who[] = "sdf_mesh_select_shells: ";
     *n_kept = 0;
     if (n_tris < 1 || n_shells < 1 || n_tris >= (1ll << 31)) return fail(std::string(who) + "the triangle or shell count is out of range");
-    int h_last[2] = {0, 0};                                            // the last triangle: its position, its flag
     unsigned char *keep, *tmp;
     int *flags, *pos;
     size_t tmp_bytes = 0;
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, (int)n_tris, st));
+    HIPCHK_MSG(who, scan_tmp_bytes(st, n_tris, &tmp_bytes));
     Scratch scratch(st);
     scratch.part(&keep, (size_t)n_shells);
     scratch.part(&flags, (size_t)n_tris);
     scratch.part(&pos, (size_t)n_tris);
-    scratch.part(&tmp, tmp_bytes ? tmp_bytes : 1);
+    scratch.part(&tmp, tmp_bytes);
     HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
     HIPCHK_MSG(who, hipMemcpyAsync(keep, h_keep, (size_t)n_shells, hipMemcpyHostToDevice, st));
     EventTimer timer;
     HIPCHK_MSG(who, timer.start(st));
-    hipLaunchKernelGGL(k_keep_flags, dim3(blocks_of(n_tris)), dim3(256), 0, st, d_triangle_shell, (const unsigned char *)keep, n_tris, flags);
-    HIPCHK_MSG(who, hipGetLastError());
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, pos, (int)n_tris, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[0], pos + (n_tris - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[1], flags + (n_tris - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, stream_wait(st));
-    const long long kept = (long long)h_last[0] + h_last[1];
-    if (kept < 0 || kept > n_tris) return fail(std::string(who) + "the scan of the flags is inconsistent");
+    HIPCHK_MSG(who, launch_rows(k_keep_flags, n_tris, st, d_triangle_shell, keep, n_tris, flags));
+    long long kept = 0;
+    if (number_flags(who, "flags", st, flags, pos, n_tris, tmp, tmp_bytes, &kept)) return 1;
     if (kept > 0) {
         if (out->ensure((size_t)kept * 72)) return 1;
-        hipLaunchKernelGGL(k_select_copy, dim3(blocks_of(9 * n_tris)), dim3(256), 0, st, d_soup, (const int *)flags, (const int *)pos, 9 * n_tris,
-                           (double *)out->p);
-        HIPCHK_MSG(who, hipGetLastError());
+        HIPCHK_MSG(who, launch_rows(k_select_copy, 9 * n_tris, st, d_soup, flags, pos, 9 * n_tris, out->p));
     }
     HIPCHK_MSG(who, timer.stop(st));
     HIPCHK_MSG(who, stream_wait(st));

@@ -156,7 +156,7 @@ extern "C" int sdf_distance_texture_host(sdf_ctx *c, const uint8_t *h_mask, int6
     const unsigned tiles = (unsigned)((sh.L + (1 << tl_log2) - 1) >> tl_log2);
     HIPCHK_FN(scratch.alloc());
     HIPCHK_FN(hipMemcpyAsync(mask, h_mask, n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_edt_scan, dim3((unsigned)sh.S), dim3(256), 0, st, (const uint8_t *)mask, sh, g);
+    HIPCHK_FN(launch_grid(k_edt_scan, (unsigned)sh.S, st, mask, sh, g));
     hipLaunchKernelGGL(k_edt_min, dim3(tiles), dim3(256), ((size_t)sh.S << tl_log2) * sizeof(int), st, (const int *)g, sh, tl_log2, out);
     HIPCHK_FN(hipGetLastError());
     HIPCHK_FN(hipMemcpyAsync(h_out, out, n * 8, hipMemcpyDeviceToHost, st));

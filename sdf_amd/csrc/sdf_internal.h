@@ -131,19 +131,18 @@ struct sdf_mesh {
         std::vector<double> axes;      // host copy (a soup that does not fit is re-run synchronously)
         CallState got;
     } pend;
-    double *weld_pts = nullptr;    // sdf_mesh_weld: unique rows / row -> unique row (dev_malloc'ed by sdf_weld.hip)
-    long long *weld_inv = nullptr;
+    sdfk::DevBlock weld_pts, weld_inv;   // sdf_mesh_weld: unique rows (float64 x 3) / row -> unique row (int64), made by sdf_weld.hip
     long long weld_n = -1;
-    // sdf_mesh_vertex_normals: weld_n x 3 float64 + the flat counter in one block of its own (dev_malloc, freed with the mesh); the
+    // sdf_mesh_vertex_normals: weld_n x 3 float64 + the flat counter in one block of its own (freed with the mesh); the
     // model (content hash) and eps they were taken with: a second call with the same ones reuses them
-    double *nrm = nullptr;
+    sdfk::DevBlock nrm;
     bool nrm_valid = false;
     unsigned long long nrm_model = 0;
     double nrm_eps = 0.0;
     long long nrm_flat = 0;
     // sdf_mesh_components: the shells of the welded mesh -- per vertex, per triangle, the counts and the boxes -- in one block of its
-    // own (sdf_components.h ShellParts; dev_malloc, freed with the mesh); n_shells >= 0: labelled, a second call reuses them
-    void *shells = nullptr;
+    // own (sdf_components.h ShellParts; freed with the mesh); n_shells >= 0: labelled, a second call reuses them
+    sdfk::DevBlock shells;
     long long n_shells = -1;
     int shell_rounds = 0;
     double shell_ms[2] = {0.0, 0.0};
@@ -188,8 +187,8 @@ int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats
 int generate_big(sdf_mesh *m, const GenCall &call);
 // ---- sdf_mesh_out.hip ----
 int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes);
-// ---- sdf_weld.hip: pts = n rows of 3 doubles on the device; on success *d_uniq (3 * *n_unique doubles) and *d_inv (n int64) are
-// device blocks the caller owns (hipFree).  0, or 1 with the message set ----
+// ---- sdf_weld.hip: pts = n rows of 3 doubles on the device; on success *d_uniq holds 3 * *n_unique doubles and *d_inv n int64; a
+// failed call leaves both empty.  0, or 1 with the message set ----
 namespace sdfk {
-int weld_device(hipStream_t stream, const double *pts, long long n, double **d_uniq, long long **d_inv, long long *n_unique);
+int weld_device(hipStream_t stream, const double *pts, long long n, DevBlock *d_uniq, DevBlock *d_inv, long long *n_unique);
 }

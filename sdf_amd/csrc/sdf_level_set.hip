@@ -337,12 +337,10 @@ extern "C" int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t 
     HIPCHK_FN(hipMemcpyAsync(dbox, box_init, sizeof box_init, hipMemcpyHostToDevice, st));
     HIPCHK_FN(hipMemsetAsync(d2, 0xff, n * 8, st));            // (all ones: above every non-negative double -> no triangle in reach)
     HIPCHK_FN(hipMemsetAsync(mask, 0, ncol * g.nw * 4, st));
-    hipLaunchKernelGGL(k_ls_dist, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, (long long)nt, g, d2);
-    hipLaunchKernelGGL(k_ls_sign, dim3(tri_blocks), dim3(256), 0, st, (const double *)pts, (const int *)tris, (long long)nt, g, mask);
-    hipLaunchKernelGGL(k_ls_parity, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, st, mask, (long long)ncol, g.nw);
-    hipLaunchKernelGGL(k_ls_compose, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, st, (const unsigned long long *)d2,
-                       (const unsigned *)mask, g, val, dbox);
-    HIPCHK_FN(hipGetLastError());
+    HIPCHK_FN(launch_grid(k_ls_dist, tri_blocks, st, pts, tris, nt, g, d2));
+    HIPCHK_FN(launch_grid(k_ls_sign, tri_blocks, st, pts, tris, nt, g, mask));
+    HIPCHK_FN(launch_rows(k_ls_parity, (long long)ncol, st, mask, ncol, g.nw));
+    HIPCHK_FN(launch_grid(k_ls_compose, (unsigned)std::min<size_t>((n + 255) / 256, 8192), st, d2, mask, g, val, dbox));
     HIPCHK_FN(hipMemcpyAsync(box, dbox, sizeof box, hipMemcpyDeviceToHost, st));
     HIPCHK_FN(stream_wait(st));
     if (box[3] >= 0) {
@@ -354,9 +352,7 @@ extern "C" int sdf_mesh_level_set_host(sdf_ctx *c, const double *h_pts, int64_t 
         }
         if (h_out && m <= cap) {
             float *out = (float *)d2;                           // (the squared distances are consumed: the crop goes there)
-            hipLaunchKernelGGL(k_ls_crop, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float *)val, g, box[0], box[1], box[2],
-                               (int)out_dims[1], (int)out_dims[2], m, out);
-            HIPCHK_FN(hipGetLastError());
+            HIPCHK_FN(launch_rows(k_ls_crop, m, st, val, g, box[0], box[1], box[2], out_dims[1], out_dims[2], m, out));
             HIPCHK_FN(hipMemcpyAsync(h_out, out, (size_t)m * 4, hipMemcpyDeviceToHost, st));
             HIPCHK_FN(stream_wait(st));
         }

@@ -300,14 +300,7 @@ int measure_moments(hipStream_t st, const double *d_soup, long long n_tris, cons
     scratch.part(&part_a, (size_t)n_chunks * MOMENT_SUMS);
     scratch.part(&part_b, (size_t)n_second * MOMENT_SUMS);
     HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
-    const double pinf = __builtin_inf();
-    for (int k = 0; k < 3; k++) {                                      // an empty box: min = the key of +inf, max = the key of -inf
-        h_head.origin[k] = 0.0;
-        unsigned long long u;
-        memcpy(&u, &pinf, 8);
-        h_head.box[k] = u | (1ull << 63);
-        h_head.box[3 + k] = ~(u | (1ull << 63));
-    }
+    for (int k = 0; k < 3; k++) { h_head.origin[k] = 0.0; h_head.box[k] = BOX_EMPTY_LO; h_head.box[3 + k] = BOX_EMPTY_HI; }
     h_head.counts[0] = h_head.counts[1] = 0;
     HIPCHK_MSG(who, hipMemcpyAsync(d_head, &h_head, sizeof(Head), hipMemcpyHostToDevice, st));
     const bool wide = (reinterpret_cast<uintptr_t>(d_soup) & 15u) == 0;
@@ -316,18 +309,12 @@ int measure_moments(hipStream_t st, const double *d_soup, long long n_tris, cons
     const double o0 = origin ? origin[0] : 0.0, o1 = origin ? origin[1] : 0.0, o2 = origin ? origin[2] : 0.0;
     EventTimer timer;
     HIPCHK_MSG(who, timer.start(st));
-    if (wide) hipLaunchKernelGGL(k_soup_box<true>, dim3(box_grid), dim3(256), 0, st, d_soup, n_tris, d_head->box);
-    else hipLaunchKernelGGL(k_soup_box<false>, dim3(box_grid), dim3(256), 0, st, d_soup, n_tris, d_head->box);
-    HIPCHK_MSG(who, hipGetLastError());
-    if (wide) hipLaunchKernelGGL(k_soup_moments<true>, dim3((unsigned)n_chunks), dim3(256), 0, st, d_soup, n_tris, (const unsigned long long *)d_head->box,
-                                 o0, o1, o2, origin ? 0 : 1, part_a, d_head->counts, d_head->origin);
-    else hipLaunchKernelGGL(k_soup_moments<false>, dim3((unsigned)n_chunks), dim3(256), 0, st, d_soup, n_tris, (const unsigned long long *)d_head->box,
-                            o0, o1, o2, origin ? 0 : 1, part_a, d_head->counts, d_head->origin);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_grid(wide ? k_soup_box<true> : k_soup_box<false>, box_grid, st, d_soup, n_tris, d_head->box));
+    HIPCHK_MSG(who, launch_grid(wide ? k_soup_moments<true> : k_soup_moments<false>, (unsigned)n_chunks, st, d_soup, n_tris, d_head->box, o0, o1, o2,
+                                origin ? 0 : 1, part_a, d_head->counts, d_head->origin));
     double *src = part_a, *dst = part_b;
     for (long long n = n_chunks; n > 1; n = (n + 255) / 256) {         // 256 partials to one, until one is left
-        hipLaunchKernelGGL(k_moment_partials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double *)src, n, dst);
-        HIPCHK_MSG(who, hipGetLastError());
+        HIPCHK_MSG(who, launch_rows(k_moment_partials, n, st, src, n, dst));
         double *t = src; src = dst; dst = t;
     }
     HIPCHK_MSG(who, timer.stop(st));
@@ -366,12 +353,9 @@ int measure_edge_census(hipStream_t st, const long long *d_cells, long long n_tr
     HIPCHK_MSG(who, hipMemsetAsync(d_counts, 0, sizeof(h_counts), st));
     EventTimer timer;
     HIPCHK_MSG(who, timer.start(st));
-    hipLaunchKernelGGL(k_edge_keys, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, st, d_cells, n_tris, k0, d_counts);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_edge_keys, n_tris, st, d_cells, n_tris, k0, d_counts));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, (const unsigned long long *)k0, k1, (int)n, 0, 64, st));
-    const long long key_tiles = (n + 255) / 256;
-    hipLaunchKernelGGL(k_edge_classes, dim3((unsigned)(key_tiles < BOX_MAX_BLOCKS ? key_tiles : BOX_MAX_BLOCKS)), dim3(256), 0, st, (const unsigned long long *)k1, n, d_counts + 1);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_grid(k_edge_classes, blocks_of(n) < BOX_MAX_BLOCKS ? blocks_of(n) : BOX_MAX_BLOCKS, st, k1, n, d_counts + 1));
     HIPCHK_MSG(who, timer.stop(st));
     HIPCHK_MSG(who, hipMemcpyAsync(h_counts, d_counts, sizeof(h_counts), hipMemcpyDeviceToHost, st));
     HIPCHK_MSG(who, stream_wait(st));

@@ -302,8 +302,8 @@ int sdf_mesh_weld_fetch(sdf_mesh *m, double *h_points, int64_t *h_cells) {
     if (m->weld_n == 0) return 0;
     sdf_ctx *c = m->ctx;
     HIPCHK(set_device(c->device));
-    HIPCHK(hipMemcpyAsync(h_points, m->weld_pts, (size_t)m->weld_n * 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_cells, m->weld_inv, (size_t)m->st.n_triangles * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_points, m->weld_pts.as<double>(), (size_t)m->weld_n * 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_cells, m->weld_inv.as<long long>(), (size_t)m->st.n_triangles * 24, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(stream_wait(c->stream));
     return 0;
 }
@@ -324,16 +324,14 @@ int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_norm
     HIPCHK(set_device(c->device));
     if (!(m->nrm_valid && m->nrm_model == t->content_hash && m->nrm_eps == eps)) {
         m->nrm_valid = false;
-        if (!m->nrm) {
-            const hipError_t e = dev_malloc((void **)&m->nrm, (size_t)nu * 24 + 8);
-            if (e != hipSuccess) { m->nrm = nullptr; return fail(std::string("sdf_mesh_vertex_normals: hipMalloc(") + std::to_string((size_t)nu * 24 + 8) + "): " + hipGetErrorString(e)); }
-        }
         static const char who[] = "sdf_mesh_vertex_normals: ";
-        unsigned long long *d_flat = reinterpret_cast<unsigned long long *>(m->nrm + 3 * nu);
+        if (!m->nrm) HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string((size_t)nu * 24 + 8) + "): ", m->nrm.alloc((size_t)nu * 24 + 8, c->stream));
+        double *nrm = m->nrm.as<double>();
+        unsigned long long *d_flat = reinterpret_cast<unsigned long long *>(nrm + 3 * nu);
         EventTimer timer;
         HIPCHK_MSG(who, hipMemsetAsync(d_flat, 0, 8, c->stream));
         HIPCHK_MSG(who, timer.start(c->stream));
-        HIPCHK_MSG(who, (hipError_t)launch_vertex_normals(c->stream, t->d_code, t->d_c64, t->full, m->weld_pts, nu, eps, m->nrm, d_flat));
+        HIPCHK_MSG(who, (hipError_t)launch_vertex_normals(c->stream, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, eps, nrm, d_flat));
         HIPCHK_MSG(who, timer.stop(c->stream));
         // (the count lands in the mesh, not on this stack: a call that fails on the way out leaves no copy in flight to a dead frame)
         HIPCHK_MSG(who, hipMemcpyAsync(&m->nrm_flat, d_flat, 8, hipMemcpyDeviceToHost, c->stream));
@@ -342,7 +340,7 @@ int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_norm
         m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps;
     }
     *n_flat = (int64_t)m->nrm_flat;
-    if (h_normals) return copy_to_host(c, h_normals, m->nrm, (size_t)nu * 24);
+    if (h_normals) return copy_to_host(c, h_normals, m->nrm.as<double>(), (size_t)nu * 24);
     return 0;
 }
 
@@ -373,7 +371,7 @@ int sdf_mesh_edge_census(sdf_mesh *m, sdf_edge_census *out) {
     out->closed = out->oriented = 1;
     if (nt == 0) return 0;
     HIPCHK(set_device(m->ctx->device));
-    return measure_edge_census(m->ctx->stream, m->weld_inv, nt, m->weld_n, out, &g_measure_kernel_ms);
+    return measure_edge_census(m->ctx->stream, m->weld_inv.as<long long>(), nt, m->weld_n, out, &g_measure_kernel_ms);
 }
 
 double sdf_mesh_measure_last_kernel_ms(void) { return g_measure_kernel_ms; }
@@ -395,7 +393,7 @@ int sdf_mesh_components(sdf_mesh *m, sdf_components *out) {
     if (m->n_shells < 0) {
         HIPCHK(set_device(m->ctx->device));
         long long k = 0;
-        if (components_label(m->ctx->stream, m->weld_inv, m->weld_pts, nt, m->weld_n, &m->shells, &k, &m->shell_rounds, m->shell_ms)) return 1;
+        if (components_label(m->ctx->stream, m->weld_inv.as<long long>(), m->weld_pts.as<double>(), nt, m->weld_n, &m->shells, &k, &m->shell_rounds, m->shell_ms)) return 1;
         m->n_shells = k;
         g_components_kernel_ms = m->shell_ms[0] + m->shell_ms[1];
     }
@@ -414,7 +412,7 @@ int sdf_mesh_components_fetch(sdf_mesh *m, int32_t *h_vertex_shell, int32_t *h_t
     static const char who[] = "sdf_mesh_components_fetch: ";
     sdf_ctx *c = m->ctx;
     const long long k = m->n_shells, nt = (long long)m->st.n_triangles;
-    const ShellParts sp = shell_parts(m->shells, m->weld_n, nt, k);
+    const ShellParts sp = shell_parts(m->shells.as<void>(), m->weld_n, nt, k);
     std::vector<unsigned long long> keys(h_bounds ? (size_t)(6 * k) : 0);
     HIPCHK(set_device(c->device));
     if (h_vertex_shell) HIPCHK_MSG(who, hipMemcpyAsync(h_vertex_shell, sp.vertex_shell, (size_t)m->weld_n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -443,7 +441,7 @@ int sdf_mesh_select_shells(sdf_mesh *m, const unsigned char *h_keep, int64_t n_k
     if (any) {                                                         // (keeping nothing: a mesh of 0 triangles, no launch)
         MESH_SOUP_READY(m);
         HIPCHK(set_device(m->ctx->device));
-        const ShellParts sp = shell_parts(m->shells, m->weld_n, (long long)m->st.n_triangles, m->n_shells);
+        const ShellParts sp = shell_parts(m->shells.as<void>(), m->weld_n, (long long)m->st.n_triangles, m->n_shells);
         if (components_select(m->ctx->stream, (const double *)mesh_soup(m), (long long)m->st.n_triangles, sp.triangle_shell, h_keep, m->n_shells,
                               &soup, &kept, &g_components_kernel_ms)) {
             soup.release();
@@ -479,7 +477,7 @@ int sdf_mesh_simplify(sdf_mesh *m, const double *origin3, const double *cell3, d
         int64_t nu = 0;
         if (sdf_mesh_weld(m, &nu)) return 1;
         HIPCHK(set_device(m->ctx->device));
-        if (simplify_device(m->ctx->stream, m->weld_pts, m->weld_inv, m->weld_n, nt, origin3, cell3, reg, &soup, stats, g_simplify_kernel_ms)) {
+        if (simplify_device(m->ctx->stream, m->weld_pts.as<double>(), m->weld_inv.as<long long>(), m->weld_n, nt, origin3, cell3, reg, &soup, stats, g_simplify_kernel_ms)) {
             soup.release();
             *stats = sdf_simplify_stats();
             return 1;
@@ -517,9 +515,9 @@ int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void
     scratch.part(&faces, fbytes);
     HIPCHK_MSG("sdf_mesh_emit_ply_host: hipMalloc(" + std::to_string(align256(vbytes) + fbytes) + "): ", scratch.alloc());
     static const char who[] = "sdf_mesh_emit_ply_host: ";
-    launch_k_ply_vertices(dim3((unsigned)((nfl + 255) / 256)), dim3(256), c->stream, m->weld_pts, with_normals ? m->nrm : nullptr, nfl, width, verts);
+    launch_k_ply_vertices(dim3((unsigned)((nfl + 255) / 256)), dim3(256), c->stream, m->weld_pts.as<double>(), with_normals ? m->nrm.as<double>() : nullptr, nfl, width, verts);
     HIPCHK_MSG(who, hipGetLastError());
-    launch_k_ply_faces(dim3((unsigned)((nt + 255) / 256)), dim3(256), c->stream, m->weld_inv, nt, faces);
+    launch_k_ply_faces(dim3((unsigned)((nt + 255) / 256)), dim3(256), c->stream, m->weld_inv.as<long long>(), nt, faces);
     HIPCHK_MSG(who, hipGetLastError());
     HIPCHK_MSG(who, hipMemcpyAsync(h_vertices, verts, vbytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK_MSG(who, hipMemcpyAsync(h_faces, faces, fbytes, hipMemcpyDeviceToHost, c->stream));
@@ -565,7 +563,6 @@ int sdf_mesh_destroy(sdf_mesh *m) {
     }
     if (m->counters.p) { c->counter_pool.push_back(m->counters); m->counters.p = nullptr; m->counters.bytes = 0; }
     for (DevBuf *b : {&m->axes, &m->kinds, &m->worklist, &m->status, &m->prune, &m->tapes, &m->cull, &m->order, &m->desc, &m->cellrecs, &m->trilist, &m->blockidx, &m->slab}) b->release();
-    (void)hipFree(m->weld_pts); (void)hipFree(m->weld_inv); (void)hipFree(m->nrm); (void)hipFree(m->shells);
     delete m;
     return 0;
 }

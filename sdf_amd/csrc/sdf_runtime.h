@@ -1,6 +1,8 @@
 // sdf_runtime.h -- the host runtime every translation unit of libsdf_hip.so shares (defined once, in sdf_runtime.hip): the last-error
 // slot behind sdf_last_error, waiting without going to sleep, the allocation hook of the tests, the pool of device blocks, and the
-// three small tools of a feature call -- a scratch block, the memory guard, an event-pair timer.
+// small tools of a feature call -- a scratch block (Scratch), the owner of a block the call leaves behind (DevBlock), the checked
+// launch of a 256-lane kernel (launch_rows, launch_grid), the memory guard, an event-pair timer (EventTimer).  The fifth tool of a
+// reader unit, number_flags, has device code behind it and lives in sdf_prims.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,7 +15,7 @@ namespace sdfk {
 // ---- errors: the message goes into this thread's slot (sdf_last_error reads it), the call returns 1 ----
 extern thread_local std::string g_err;
 int fail(const std::string &m);
-// a failed HIP call ends the function; what it holds goes back through destructors (DevBuf's owners, Scratch, EventTimer)
+// a failed HIP call ends the function; what it holds goes back through destructors (DevBuf's owners, Scratch, DevBlock, EventTimer)
 #define HIPCHK_MSG(prefix, x)                                                                       \
     do {                                                                                            \
         hipError_t e_ = (x);                                                                        \
@@ -75,22 +77,55 @@ struct Scratch {
     Scratch &operator=(const Scratch &) = delete;
     ~Scratch() { if (base) { (void)stream_wait(stream); (void)hipFree(base); } }
     template <typename T> void part(T **p, size_t count) {
-        parts[n_parts++] = {reinterpret_cast<void **>(p), bytes};
+        parts.push_back({reinterpret_cast<void **>(p), bytes});
         bytes += align256(count * sizeof(T));
     }
     hipError_t alloc() {
         const hipError_t e = dev_malloc((void **)&base, bytes);
-        for (int k = 0; k < n_parts && e == hipSuccess; k++) *parts[k].p = base + parts[k].off;
+        for (size_t k = 0; k < parts.size() && e == hipSuccess; k++) *parts[k].p = base + parts[k].off;
         return e;
     }
     size_t bytes = 0;
 private:
     struct Part { void **p; size_t off; };
-    Part parts[8];
-    int n_parts = 0;
+    std::vector<Part> parts;
     char *base = nullptr;
     hipStream_t stream;
 };
+
+// A device block that OUTLIVES the call that made it (the weld, the normals and the shells a mesh keeps): one hooked allocation, not
+// pooled, move-only.  It is freed with its owner or by reset(), after the stream that worked in it has drained -- so a producer
+// fills a local DevBlock and moves it out only when it has succeeded, and every other path hands the block back.
+struct DevBlock {
+    DevBlock() = default;
+    DevBlock(DevBlock &&o) noexcept : p(o.p), stream(o.stream) { o.p = nullptr; }
+    DevBlock &operator=(DevBlock &&o) noexcept {
+        if (this != &o) { reset(); p = o.p; stream = o.stream; o.p = nullptr; }
+        return *this;
+    }
+    ~DevBlock() { reset(); }
+    hipError_t alloc(size_t bytes, hipStream_t st) { reset(); stream = st; return dev_malloc(&p, bytes); }
+    void reset() { if (p) { (void)stream_wait(stream); (void)hipFree(p); p = nullptr; } }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+    explicit operator bool() const { return p != nullptr; }
+private:
+    void *p = nullptr;
+    hipStream_t stream = nullptr;
+};
+
+// The launch of a kernel of 256-lane workgroups, checked: HIPCHK_MSG(who, launch_rows(k_x, n, st, ...)).  launch_rows gives each of n
+// rows a lane and launches nothing when there are none; launch_grid takes the grid as it is (a capped grid whose workgroups stride).
+// The arguments are converted to the kernel's parameter types, so a pointer to const or a nullptr needs no cast where it is passed.
+static inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
+template <typename... P, typename... A>
+hipError_t launch_grid(void (*kernel)(P...), unsigned grid, hipStream_t st, A &&...args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+template <typename... P, typename... A>
+hipError_t launch_rows(void (*kernel)(P...), long long n, hipStream_t st, A &&...args) {
+    return n < 1 ? hipSuccess : launch_grid(kernel, blocks_of(n), st, static_cast<A &&>(args)...);
+}
 
 // the memory guard of the calls that size their scratch from their arguments: do `bytes` fit in 90 % of what is free now?
 // (*free_b: for the caller's message)

@@ -32,6 +32,7 @@
 #include <string>
 
 #include "sdf_measure.h"
+#include "sdf_prims.h"
 #include "sdf_simplify.h"
 
 namespace sdfk {
@@ -257,7 +258,6 @@ __global__ __launch_bounds__(256) void k_cluster_emit(const long long *__restric
     out[9ll * pos[t] + r] = verts[3ll * vertex_cluster[cells[3 * t + corner]] + (r - 3 * corner)];
 }
 
-static unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 static int bits_for(long long n) { int b = 1; while (b < 63 && (1ll << b) < n) b += 1; return b; }      // the bits that hold 0 .. n - 1
 
 int simplify_device(hipStream_t st, const double *d_points, const long long *d_cells, long long n_vertices, long long n_tris,
@@ -270,48 +270,39 @@ int simplify_device(hipStream_t st, const double *d_points, const long long *d_c
     for (int c = 0; c < 3; c++) { g.origin[c] = origin[c]; g.cell[c] = cell[c]; }
     g.reg = reg;
     SimplifyHead h_head = {};
-    int h_last[2] = {0, 0};                                            // the last vertex / triangle: its rank, its flag
     size_t tmp_bytes = 0, need = 0;
-    HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(nullptr, need, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (unsigned *)nullptr,
+    HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (unsigned *)nullptr,
                                                       (unsigned *)nullptr, (int)n_vertices, 0, 64, st));
-    tmp_bytes = need;
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(nullptr, need, (unsigned *)nullptr, (unsigned *)nullptr, (unsigned *)nullptr, (unsigned *)nullptr,
                                                       (int)n_items, 0, 32, st));
     tmp_bytes = need > tmp_bytes ? need : tmp_bytes;
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(nullptr, need, (int *)nullptr, (int *)nullptr, (int)(n_vertices > n_tris ? n_vertices : n_tris), st));
-    tmp_bytes = need > tmp_bytes ? need : tmp_bytes;
-    // one hooked block, carved here: [head | keys x 2 | idx x 2 | flags | rank | vertex_cluster | cluster_key | vstart | istart |
-    // item_cluster x 2 | item x 2 | verts | tflags | tpos | tmp]
+    HIPCHK_MSG(who, scan_tmp_bytes(st, n_vertices > n_tris ? n_vertices : n_tris, &tmp_bytes));
     const size_t nv = (size_t)n_vertices, ni = (size_t)n_items, nt = (size_t)n_tris;
-    const size_t sizes[] = {sizeof(SimplifyHead), nv * 8, nv * 8, nv * 4, nv * 4, nv * 4, nv * 4, nv * 4, nv * 8, (nv + 1) * 4, (nv + 1) * 4,
-                            ni * 4, ni * 4, ni * 4, ni * 4, nv * 24, nt * 4, nt * 4, tmp_bytes ? tmp_bytes : 1};
-    constexpr int N_PARTS = (int)(sizeof(sizes) / sizeof(sizes[0]));
-    size_t off[N_PARTS], total = 0;
-    for (int k = 0; k < N_PARTS; k++) { off[k] = total; total += align256(sizes[k]); }
-    unsigned char *base;
+    SimplifyHead *head;
+    unsigned long long *keys0, *keys1, *cluster_key;
+    unsigned *idx0, *idx1, *icl0, *icl1, *item0, *item1;
+    int *flags, *rank, *vertex_cluster, *vstart, *istart, *tflags, *tpos;
+    double *verts;
+    unsigned char *tmp;
     Scratch scratch(st);                                               // (declared after the host copies: it waits for the stream before they go)
-    scratch.part(&base, total);
+    scratch.part(&head, 1);
+    scratch.part(&keys0, nv); scratch.part(&keys1, nv);
+    scratch.part(&idx0, nv); scratch.part(&idx1, nv);
+    scratch.part(&flags, nv); scratch.part(&rank, nv); scratch.part(&vertex_cluster, nv);
+    scratch.part(&cluster_key, nv);
+    scratch.part(&vstart, nv + 1); scratch.part(&istart, nv + 1);
+    scratch.part(&icl0, ni); scratch.part(&icl1, ni); scratch.part(&item0, ni); scratch.part(&item1, ni);
+    scratch.part(&verts, 3 * nv);
+    scratch.part(&tflags, nt); scratch.part(&tpos, nt);
+    scratch.part(&tmp, tmp_bytes);
     HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
-    int part = 0;
-    auto next = [&](void) { return (void *)(base + off[part++]); };
-    SimplifyHead *head = (SimplifyHead *)next();
-    unsigned long long *keys0 = (unsigned long long *)next(), *keys1 = (unsigned long long *)next();
-    unsigned *idx0 = (unsigned *)next(), *idx1 = (unsigned *)next();
-    int *flags = (int *)next(), *rank = (int *)next(), *vertex_cluster = (int *)next();
-    unsigned long long *cluster_key = (unsigned long long *)next();
-    int *vstart = (int *)next(), *istart = (int *)next();
-    unsigned *icl0 = (unsigned *)next(), *icl1 = (unsigned *)next(), *item0 = (unsigned *)next(), *item1 = (unsigned *)next();
-    double *verts = (double *)next();
-    int *tflags = (int *)next(), *tpos = (int *)next();
-    void *tmp = next();
 
     EventTimer t_keys, t_items, t_vertex, t_emit;
     // ---- the box of the grid coordinates; the refusals that need it ----
     HIPCHK_MSG(who, t_keys.start(st));
     hipLaunchKernelGGL(k_cluster_head_init, dim3(1), dim3(64), 0, st, head);
     HIPCHK_MSG(who, hipGetLastError());
-    hipLaunchKernelGGL(k_cluster_box, dim3(blocks_of(n_vertices)), dim3(256), 0, st, d_points, n_vertices, g, head);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_cluster_box, n_vertices, st, d_points, n_vertices, g, head));
     HIPCHK_MSG(who, hipMemcpyAsync(&h_head, head, sizeof(SimplifyHead), hipMemcpyDeviceToHost, st));
     HIPCHK_MSG(who, stream_wait(st));
     if (h_head.n_bad) return fail(std::string(who) + std::to_string(h_head.n_bad) + " vertices are not finite");
@@ -327,53 +318,34 @@ int simplify_device(hipStream_t st, const double *d_points, const long long *d_c
         if (c == 0) x_bits = bits_for((long long)(hi - lo) + 1);
     }
     // ---- the clusters, numbered by ascending key ----
-    hipLaunchKernelGGL(k_cluster_keys, dim3(blocks_of(n_vertices)), dim3(256), 0, st, d_points, n_vertices, g, keys0, idx0);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_cluster_keys, n_vertices, st, d_points, n_vertices, g, keys0, idx0));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys0, keys1, idx0, idx1, (int)n_vertices, 0, 2 * KEY_BITS + x_bits, st));
-    hipLaunchKernelGGL(k_cluster_flags, dim3(blocks_of(n_vertices)), dim3(256), 0, st, (const unsigned long long *)keys1, n_vertices, flags);
-    HIPCHK_MSG(who, hipGetLastError());
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, rank, (int)n_vertices, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[0], rank + (n_vertices - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[1], flags + (n_vertices - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, stream_wait(st));
-    const long long n_clusters = (long long)h_last[0] + h_last[1];
-    if (n_clusters < 1 || n_clusters > n_vertices) return fail(std::string(who) + "the scan of the cluster flags is inconsistent");
-    hipLaunchKernelGGL(k_cluster_number, dim3(blocks_of(n_vertices)), dim3(256), 0, st, (const unsigned long long *)keys1, (const unsigned *)idx1,
-                       (const int *)flags, (const int *)rank, n_vertices, vertex_cluster, cluster_key, vstart);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_cluster_flags, n_vertices, st, keys1, n_vertices, flags));
+    long long n_clusters = 0, kept = 0;
+    if (number_flags(who, "cluster flags", st, flags, rank, n_vertices, tmp, tmp_bytes, &n_clusters)) return 1;
+    if (n_clusters < 1) return fail(std::string(who) + "the scan of the cluster flags is inconsistent");
+    HIPCHK_MSG(who, launch_rows(k_cluster_number, n_vertices, st, keys1, idx1, flags, rank, n_vertices, vertex_cluster, cluster_key, vstart));
     HIPCHK_MSG(who, t_keys.stop(st));
     // ---- the items of every cluster, in ascending item index ----
     HIPCHK_MSG(who, t_items.start(st));
     HIPCHK_MSG(who, hipMemsetAsync(istart, 0, (size_t)(n_clusters + 1) * 4, st));
-    hipLaunchKernelGGL(k_cluster_items, dim3(blocks_of(n_items)), dim3(256), 0, st, d_cells, (const int *)vertex_cluster, n_items, icl0, item0);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_cluster_items, n_items, st, d_cells, vertex_cluster, n_items, icl0, item0));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, icl0, icl1, item0, item1, (int)n_items, 0, bits_for(n_clusters), st));
-    hipLaunchKernelGGL(k_item_starts, dim3(blocks_of(n_items)), dim3(256), 0, st, (const unsigned *)icl1, n_items, istart);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_item_starts, n_items, st, icl1, n_items, istart));
     HIPCHK_MSG(who, t_items.stop(st));
     // ---- one representative per cluster ----
     HIPCHK_MSG(who, t_vertex.start(st));
-    hipLaunchKernelGGL(k_cluster_vertex, dim3(blocks_of(n_clusters)), dim3(256), 0, st, d_points, d_cells, n_vertices, n_items,
-                       (const unsigned long long *)cluster_key, (const int *)vstart, (const unsigned *)idx1, (const int *)istart,
-                       (const unsigned *)item1, n_clusters, g, verts, head);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, launch_rows(k_cluster_vertex, n_clusters, st, d_points, d_cells, n_vertices, n_items, cluster_key, vstart, idx1, istart, item1,
+                                n_clusters, g, verts, head));
     HIPCHK_MSG(who, t_vertex.stop(st));
     // ---- the survivors ----
     HIPCHK_MSG(who, t_emit.start(st));
-    hipLaunchKernelGGL(k_cluster_live, dim3(blocks_of(n_tris)), dim3(256), 0, st, d_cells, (const int *)vertex_cluster, n_tris, tflags);
-    HIPCHK_MSG(who, hipGetLastError());
-    HIPCHK_MSG(who, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tflags, tpos, (int)n_tris, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[0], tpos + (n_tris - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_last[1], tflags + (n_tris - 1), 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, hipMemcpyAsync(&h_head, head, sizeof(SimplifyHead), hipMemcpyDeviceToHost, st));
-    HIPCHK_MSG(who, stream_wait(st));
-    const long long kept = (long long)h_last[0] + h_last[1];
-    if (kept < 0 || kept > n_tris) return fail(std::string(who) + "the scan of the live flags is inconsistent");
+    HIPCHK_MSG(who, launch_rows(k_cluster_live, n_tris, st, d_cells, vertex_cluster, n_tris, tflags));
+    HIPCHK_MSG(who, hipMemcpyAsync(&h_head, head, sizeof(SimplifyHead), hipMemcpyDeviceToHost, st));    // (lands behind number_flags' wait)
+    if (number_flags(who, "live flags", st, tflags, tpos, n_tris, tmp, tmp_bytes, &kept)) return 1;
     if (kept > 0) {
         if (out->ensure((size_t)kept * 72)) return 1;
-        hipLaunchKernelGGL(k_cluster_emit, dim3(blocks_of(9 * n_tris)), dim3(256), 0, st, d_cells, (const int *)vertex_cluster, (const double *)verts,
-                           (const int *)tflags, (const int *)tpos, 9 * n_tris, (double *)out->p);
-        HIPCHK_MSG(who, hipGetLastError());
+        HIPCHK_MSG(who, launch_rows(k_cluster_emit, 9 * n_tris, st, d_cells, vertex_cluster, verts, tflags, tpos, 9 * n_tris, out->p));
     }
     HIPCHK_MSG(who, t_emit.stop(st));
     HIPCHK_MSG(who, stream_wait(st));

@@ -12,6 +12,8 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include <utility>
+
 #include "sdf_runtime.h"
 
 namespace sdfk {
@@ -55,52 +57,44 @@ __global__ __launch_bounds__(256) void k_weld_scatter(const double *__restrict__
     }
 }
 
-// pts: n rows of 3 doubles on the device.  On success *d_uniq (3 * *n_unique doubles) and *d_inv (n int64) are device blocks the
-// caller owns (hipFree).  Returns 0, or 1 with the message set; whatever a failed call had taken has gone back, and both are NULL.
-int weld_device(hipStream_t stream, const double *pts, long long n, double **d_uniq, long long **d_inv, long long *n_unique) {
+// pts: n rows of 3 doubles on the device.  On success *d_uniq holds 3 * *n_unique doubles and *d_inv n int64.  Returns 0, or 1 with
+// the message set; whatever a failed call had taken has gone back, and both blocks are empty.  Three hooked allocations: the
+// scratch, then the two results.
+int weld_device(hipStream_t stream, const double *pts, long long n, DevBlock *d_uniq, DevBlock *d_inv, long long *n_unique) {
     static const char who[] = "sdf_mesh_weld: ";
-    *d_uniq = nullptr; *d_inv = nullptr; *n_unique = 0;
+    d_uniq->reset(); d_inv->reset(); *n_unique = 0;
     if (n <= 0) return 0;
     HIPCHK_MSG(who, n >= (1ll << 31) ? hipErrorInvalidValue : hipSuccess);
     unsigned long long *k0 = nullptr, *k1 = nullptr;
     unsigned *p0 = nullptr, *p1 = nullptr;
-    void *tmp = nullptr;
-    // every block goes back when the call leaves -- the results too unless it succeeded -- once the stream has drained
-    struct Blocks {
-        hipStream_t st; void **held[5]; double **uniq; long long **inv; bool ok;
-        ~Blocks() {
-            if (!ok) (void)stream_wait(st);
-            for (void **q : held) (void)hipFree(*q);
-            if (!ok) { (void)hipFree(*uniq); (void)hipFree(*inv); *uniq = nullptr; *inv = nullptr; }
-        }
-    } blocks{stream, {(void **)&k0, (void **)&k1, (void **)&p0, (void **)&p1, &tmp}, d_uniq, d_inv, false};
+    unsigned char *tmp;
     size_t tmp_sort = 0, tmp_scan = 0;
-    const unsigned grid = (unsigned)((n + 255) / 256);
     int last = 0;
-    HIPCHK_MSG(who, dev_malloc((void **)&k0, (size_t)n * 8)); HIPCHK_MSG(who, dev_malloc((void **)&k1, (size_t)n * 8));
-    HIPCHK_MSG(who, dev_malloc((void **)&p0, (size_t)n * 4)); HIPCHK_MSG(who, dev_malloc((void **)&p1, (size_t)n * 4));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, k0, k1, p0, p1, (int)n, 0, 64, stream));
     HIPCHK_MSG(who, hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, (int *)nullptr, (int *)nullptr, (int)n, stream));
-    HIPCHK_MSG(who, dev_malloc(&tmp, tmp_sort > tmp_scan ? tmp_sort : tmp_scan));
+    Scratch scratch(stream);                                           // (declared after `last`: it waits for the stream before that goes)
+    scratch.part(&k0, (size_t)n); scratch.part(&k1, (size_t)n);
+    scratch.part(&p0, (size_t)n); scratch.part(&p1, (size_t)n);
+    scratch.part(&tmp, tmp_sort > tmp_scan ? tmp_sort : tmp_scan);
+    DevBlock uniq, inv;                                                // the results: moved out only when all has gone well
+    HIPCHK_MSG(who, scratch.alloc());
     // least significant field first; every pass is stable
-    hipLaunchKernelGGL(k_weld_keys, dim3(grid), dim3(256), 0, stream, pts, (const unsigned *)nullptr, n, 2, k0, p0);
+    HIPCHK_MSG(who, launch_rows(k_weld_keys, n, stream, pts, nullptr, n, 2, k0, p0));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_sort, k0, k1, p0, p1, (int)n, 0, 64, stream));
-    hipLaunchKernelGGL(k_weld_keys, dim3(grid), dim3(256), 0, stream, pts, (const unsigned *)p1, n, 1, k0, (unsigned *)nullptr);
+    HIPCHK_MSG(who, launch_rows(k_weld_keys, n, stream, pts, p1, n, 1, k0, nullptr));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_sort, k0, k1, p1, p0, (int)n, 0, 64, stream));
-    hipLaunchKernelGGL(k_weld_keys, dim3(grid), dim3(256), 0, stream, pts, (const unsigned *)p0, n, 0, k0, (unsigned *)nullptr);
+    HIPCHK_MSG(who, launch_rows(k_weld_keys, n, stream, pts, p0, n, 0, k0, nullptr));
     HIPCHK_MSG(who, hipcub::DeviceRadixSort::SortPairs(tmp, tmp_sort, k0, k1, p0, p1, (int)n, 0, 64, stream));
     // p1 = soup rows in lexicographic order; the key buffers are free now: flags and ids live in them
     int *flags = reinterpret_cast<int *>(k0), *uid = reinterpret_cast<int *>(k1);
-    hipLaunchKernelGGL(k_weld_flags, dim3(grid), dim3(256), 0, stream, pts, (const unsigned *)p1, n, flags);
+    HIPCHK_MSG(who, launch_rows(k_weld_flags, n, stream, pts, p1, n, flags));
     HIPCHK_MSG(who, hipcub::DeviceScan::InclusiveSum(tmp, tmp_scan, flags, uid, (int)n, stream));
     HIPCHK_MSG(who, hipMemcpyAsync(&last, uid + (n - 1), sizeof(int), hipMemcpyDeviceToHost, stream));
     HIPCHK_MSG(who, stream_wait(stream));
-    *n_unique = last;
-    HIPCHK_MSG(who, dev_malloc((void **)d_uniq, (size_t)last * 24)); HIPCHK_MSG(who, dev_malloc((void **)d_inv, (size_t)n * 8));
-    hipLaunchKernelGGL(k_weld_scatter, dim3(grid), dim3(256), 0, stream, pts, (const unsigned *)p1, (const int *)flags, (const int *)uid, n, *d_uniq, *d_inv);
-    HIPCHK_MSG(who, hipGetLastError());
+    HIPCHK_MSG(who, uniq.alloc((size_t)last * 24, stream)); HIPCHK_MSG(who, inv.alloc((size_t)n * 8, stream));
+    HIPCHK_MSG(who, launch_rows(k_weld_scatter, n, stream, pts, p1, flags, uid, n, uniq.as<double>(), inv.as<long long>()));
     HIPCHK_MSG(who, stream_wait(stream));
-    blocks.ok = true;
+    *d_uniq = std::move(uniq); *d_inv = std::move(inv); *n_unique = last;
     return 0;
 }
 

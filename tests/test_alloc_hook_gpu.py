@@ -1,5 +1,5 @@
 """The allocation hook (sdf_test_fail_alloc) walked through the feature calls whose device blocks go through the library's hooked
-allocator (csrc/sdf_runtime.h: the scratch block of sdf_render_host, sdf_distance_texture_host and sdf_mesh_level_set_host, the seven
+allocator (csrc/sdf_runtime.h: the scratch block of sdf_render_host, sdf_distance_texture_host and sdf_mesh_level_set_host, the three
 blocks of sdf_mesh_weld): every failing call returns 1 with the allocator's message, the free device memory is what it was, and the
 first call that gets through returns what the un-hooked call returned.  The shapes make every scratch block at least 16 MiB, so that
 a leaked one shows in hipMemGetInfo.  The hook injects a HOST-side allocation error: nothing on the device faults."""
@@ -96,7 +96,7 @@ def test_level_set_scratch_goes_through_the_hook(eng, monkeypatch):
 
 def test_weld_blocks_go_through_the_hook(eng):
     """sdf_mesh_weld on 400,000 random triangles (1.2 M rows: 9.6 MB per key block, 28.8 MB of unique rows): a failure at any of its
-    seven blocks -- the two results, taken after the sort, among them -- frees what was taken and leaves the mesh unwelded, so that
+    three blocks -- the two results, taken after the sort, among them -- frees what was taken and leaves the mesh unwelded, so that
     the next sdf_mesh_weld welds it"""
     lib = eng.lib
     n_tris = 400000
@@ -130,7 +130,7 @@ def test_weld_blocks_go_through_the_hook(eng):
             assert _free(lib) == f0, (n, f0, _free(lib))
             assert lib.sdf_mesh_weld_fetch(s.mesh.handle, pts.ctypes.data_as(f64p), cells.ctypes.data_as(i64p)) == 1   # no weld was left behind
             assert b'call sdf_mesh_weld first' in lib.sdf_last_error()
-        assert rc == 0 and failures == 7 and nu.value == 3 * n_tris, (rc, failures, nu.value)
+        assert rc == 0 and failures == 3 and nu.value == 3 * n_tris, (rc, failures, nu.value)
         held = f0 - _free(lib)                                  # the mesh owns the unique rows and the index now (32 B per row), and nothing else
         assert 96 * n_tris <= held <= 96 * n_tris + (8 << 20), (held, 96 * n_tris)
         got = s.mesh.weld()

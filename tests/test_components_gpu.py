@@ -281,6 +281,29 @@ def test_selection_of_an_adopted_soup_and_of_a_record_mesh(ns, eng):
         r.close()
 
 
+@pytest.mark.parametrize('n', (1, 256, 257))
+def test_selection_pins_the_last_triangle(n, eng):
+    """the count of a selection is the last triangle's position + its flag: with only the shell of the LAST soup triangle kept the
+    sum ends on flag 1 over position 0, with every shell but that one on flag 0 over position n - 1; 256 / 257: the last triangle
+    is the last lane of a workgroup / alone in the next one"""
+    tris = disjoint_triangles(n)
+    s = Soup(eng, tris)
+    try:
+        ts = s.mesh.components()['triangle_shell']
+        only_last = np.arange(n) == ts[-1]
+        for mask in (only_last, ~only_last):
+            sub = tris[mask[ts]]
+            assert len(sub) == (1 if mask is only_last else n - 1)
+            sel = s.mesh.select(mask)
+            try:
+                assert sel.n_triangles == len(sub)
+                assert sel.points().shape == (3 * len(sub), 3) and np.array_equal(bits(sel.points()), bits(sub.reshape(-1, 3)))
+            finally:
+                sel.close()
+    finally:
+        s.close()
+
+
 def test_refusals(eng):
     lib = eng.lib
     s = Soup(eng, tetrahedra(3))
