@@ -52,6 +52,25 @@ def lib():
     return _LIB
 
 
+_LIB_F32 = None
+
+
+def lib_f32():
+    """the float32 build of the evaluator (libsdf_oracle_f32.so, -DSDF_ORACLE_REAL=float): it has
+    `sdf_oracle_eval_tree` only, with the same float64 arguments as the float64 library's"""
+    global _LIB_F32
+    if _LIB_F32 is None:
+        path = os.path.join(_HERE, 'libsdf_oracle_f32.so')
+        if not os.path.exists(path):
+            build()
+        L = ctypes.CDLL(path)
+        L.sdf_oracle_eval_tree.argtypes = [_i32p, _f64p, _i32p, ctypes.c_int32, _f64p, ctypes.c_int64,
+                                           ctypes.c_int, _f64p]
+        L.sdf_oracle_eval_tree.restype = None
+        _LIB_F32 = L
+    return _LIB_F32
+
+
 def _tree(sdf):
     from sdf_amd.ir import flatten          # the front end only builds the tree; no device code
     nodes, params, children, root = flatten(sdf)
@@ -66,15 +85,25 @@ def _p(a, t):
     return a.ctypes.data_as(t)
 
 
-def evaluate(sdf, pts):
-    """f(P) -> (N,) float64"""
+def _evaluate(L, sdf, pts):
     nodes, params, children, root = _tree(sdf)
     pts = np.ascontiguousarray(pts, dtype=np.float64)
     n, dim = pts.shape
     out = np.empty(n, np.float64)
-    lib().sdf_oracle_eval_tree(_p(nodes, _i32p), _p(params, _f64p), _p(children, _i32p), root,
-                               _p(pts, _f64p), n, dim, _p(out, _f64p))
+    L.sdf_oracle_eval_tree(_p(nodes, _i32p), _p(params, _f64p), _p(children, _i32p), root,
+                           _p(pts, _f64p), n, dim, _p(out, _f64p))
     return out
+
+
+def evaluate(sdf, pts):
+    """f(P) -> (N,) float64"""
+    return _evaluate(lib(), sdf, pts)
+
+
+def evaluate_f32(sdf, pts):
+    """f(P) -> (N,) float64 holding float32 values: the same formulas with the points, the model's parameters,
+    every constant, every intermediate and the libm calls in float32"""
+    return _evaluate(lib_f32(), sdf, pts)
 
 
 def marching_cubes(volume):

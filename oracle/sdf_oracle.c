@@ -27,6 +27,9 @@
  * The tree comes from sdf_amd.ir.flatten(): nodes[n][5] = {op, param_off, nparams, child_off,
  * nchildren}, params[], children[].  It is evaluated by recursion, one point at a time -- on
  * purpose a different mechanism from the product's op tape + stack machine.
+ *
+ * The evaluator is typed over `real` (below): double here, float in the second library that
+ * oracle/Makefile builds from this file for the float32 tests.
  */
 #include <math.h>
 #include <stdint.h>
@@ -37,158 +40,196 @@
 #include "mc33.h"
 #include "node_ops.h"
 
+/* ---- the evaluator's number type ------------------------------------------------- */
+/* The evaluator (everything down to eval_node) is written over `real`.  The default build, libsdf_oracle.so,
+ * has real = double and is the checker the goldens pin.  -DSDF_ORACLE_REAL=float gives libsdf_oracle_f32.so:
+ * the SAME formulas with every constant, every intermediate and every libm call in float32 -- what the
+ * float32 interpreter of the product is measured against (tests/test_float32_host.py).  Literals with a
+ * fraction go through R(), libm through the r_* names; integer literals convert to `real` on their own.
+ * The float build is compiled with -Werror=double-promotion, so a literal or a call that slipped past
+ * the layer does not compile.  Only sdf_oracle_eval_tree exists in the float build. */
+#ifndef SDF_ORACLE_REAL
+#define SDF_ORACLE_REAL double
+#endif
+typedef SDF_ORACLE_REAL real;
+#define ORACLE_CAT_(a, b) a##b
+#define ORACLE_CAT(a, b) ORACLE_CAT_(a, b)
+#define ORACLE_IS_F32_double 0
+#define ORACLE_IS_F32_float 1
+#define ORACLE_F32 ORACLE_CAT(ORACLE_IS_F32_, SDF_ORACLE_REAL)
+#if ORACLE_F32
+#define R(x) x##f
+#define RM(fn) fn##f
+#else
+#define R(x) x
+#define RM(fn) fn
+#endif
+#define r_sqrt RM(sqrt)
+#define r_fabs RM(fabs)
+#define r_fmod RM(fmod)
+#define r_copysign RM(copysign)
+#define r_fma RM(fma)
+#define r_hypot RM(hypot)
+#define r_atan2 RM(atan2)
+#define r_cos RM(cos)
+#define r_sin RM(sin)
+#define r_pow RM(pow)
+#define r_floor RM(floor)
+#define r_nearbyint RM(nearbyint)
+#define R_NAN ((real)NAN)
+
 typedef struct {
     const int32_t *nodes;
-    const double *params;
+    const real *params;
     const int32_t *children;
     int32_t root;
 } tree_t;
 
 /* ---- NumPy scalar semantics ------------------------------------------------------ */
 /* np.minimum / np.maximum propagate NaN: (a < b || isnan(a)) ? a : b */
-static inline double np_min(double a, double b) { return (a < b || a != a) ? a : b; }
-static inline double np_max(double a, double b) { return (a >= b || a != a) ? a : b; }
+static inline real np_min(real a, real b) { return (a < b || a != a) ? a : b; }
+static inline real np_max(real a, real b) { return (a >= b || a != a) ? a : b; }
 /* np.clip = min(max(x, lo), hi) with NaN-propagating helpers (strict compares) */
-static inline double np_clip(double x, double lo, double hi) {
-    double t = (x != x || x > lo) ? x : lo;
+static inline real np_clip(real x, real lo, real hi) {
+    real t = (x != x || x > lo) ? x : lo;
     return (t != t || t < hi) ? t : hi;
 }
-static inline double np_sign(double x) { return x != x ? x : (x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0)); }
+static inline real np_sign(real x) { return x != x ? x : (x > 0 ? R(1.0) : (x < 0 ? -R(1.0) : R(0.0))); }
 /* Python/NumPy floored modulo (npy_divmod) */
-static inline double np_mod(double a, double b) {
-    double m = fmod(a, b);
+static inline real np_mod(real a, real b) {
+    real m = r_fmod(a, b);
     if (b == 0) return m;
     if (m != 0) { if ((b < 0) != (m < 0)) m += b; }
-    else m = copysign(0.0, b);
+    else m = r_copysign(R(0.0), b);
     return m;
 }
 /* np.linalg.norm(axis=1): sqrt of the left-to-right sum of squares */
-static inline double len2(double x, double y) { return sqrt(x * x + y * y); }
-static inline double len3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+static inline real len2(real x, real y) { return r_sqrt(x * x + y * y); }
+static inline real len3(real x, real y, real z) { return r_sqrt((x * x + y * y) + z * z); }
 /* np.dot((N,3),(3,)) and np.dot((N,3),(3,3)) go through BLAS; the summation used here (fused
  * multiply-adds, first term a plain product) is what OpenBLAS' Haswell kernels do for these
  * shapes; other BLAS builds differ in the last bit, which is why value parity is checked to a
  * few ulp and not bitwise (DESIGN.md section "numerics"). */
-static inline double dot3(double ax, double ay, double az, double bx, double by, double bz) {
-    return fma(az, bz, fma(ay, by, ax * bx));
+static inline real dot3(real ax, real ay, real az, real bx, real by, real bz) {
+    return r_fma(az, bz, r_fma(ay, by, ax * bx));
 }
-static inline double dot2(double ax, double ay, double bx, double by) { return fma(ay, by, ax * bx); }
+static inline real dot2(real ax, real ay, real bx, real by) { return r_fma(ay, by, ax * bx); }
 
 /* ---- easing curves: reference sdf/ease.py:3-162 ---------------------------------- */
-static double out_bounce(double t) {
-    if (t < 4.0 / 11) return (121 * t * t) / 16;
-    if (t < 8.0 / 11) return (363.0 / 40 * t * t) - (99.0 / 10 * t) + 17.0 / 5;
-    if (t < 9.0 / 10) return (4356.0 / 361 * t * t) - (35442.0 / 1805 * t) + 16061.0 / 1805;
-    return (54.0 / 5 * t * t) - (513.0 / 25 * t) + 268.0 / 25;
+static real out_bounce(real t) {
+    if (t < R(4.0) / 11) return (121 * t * t) / 16;
+    if (t < R(8.0) / 11) return (R(363.0) / 40 * t * t) - (R(99.0) / 10 * t) + R(17.0) / 5;
+    if (t < R(9.0) / 10) return (R(4356.0) / 361 * t * t) - (R(35442.0) / 1805 * t) + R(16061.0) / 1805;
+    return (R(54.0) / 5 * t * t) - (R(513.0) / 25 * t) + R(268.0) / 25;
 }
-static double ease_apply(int id, double t) {
-    const double pi = 3.141592653589793;
-    double u, v, a, b;
+static real ease_apply(int id, real t) {
+    const real pi = R(3.141592653589793);
+    real u, v, a, b;
     switch (id) {
     case EASE_linear: return t;
     case EASE_in_quad: return t * t;
     case EASE_out_quad: return -t * (t - 2);
     case EASE_in_out_quad:
-        u = 2 * t - 1; a = 2 * t * t; b = -0.5 * (u * (u - 2) - 1);
-        return t < 0.5 ? a : b;
+        u = 2 * t - 1; a = 2 * t * t; b = -R(0.5) * (u * (u - 2) - 1);
+        return t < R(0.5) ? a : b;
     case EASE_in_cubic: return t * t * t;
     case EASE_out_cubic: u = t - 1; return u * u * u + 1;
     case EASE_in_out_cubic:
         u = t * 2; v = u - 2;
-        return u < 1 ? 0.5 * u * u * u : 0.5 * (v * v * v + 2);
+        return u < 1 ? R(0.5) * u * u * u : R(0.5) * (v * v * v + 2);
     case EASE_in_quart: return t * t * t * t;
     case EASE_out_quart: u = t - 1; return -(u * u * u * u - 1);
     case EASE_in_out_quart:
         u = t * 2; v = u - 2;
-        return u < 1 ? 0.5 * u * u * u * u : -0.5 * (v * v * v * v - 2);
+        return u < 1 ? R(0.5) * u * u * u * u : -R(0.5) * (v * v * v * v - 2);
     case EASE_in_quint: return t * t * t * t * t;
     case EASE_out_quint: u = t - 1; return u * u * u * u * u + 1;
     case EASE_in_out_quint:
         u = t * 2; v = u - 2;
-        return u < 1 ? 0.5 * u * u * u * u * u : 0.5 * (v * v * v * v * v + 2);
-    case EASE_in_sine: return -cos(t * pi / 2) + 1;
-    case EASE_out_sine: return sin(t * pi / 2);
-    case EASE_in_out_sine: return -0.5 * (cos(pi * t) - 1);
-    case EASE_in_expo: return t == 0 ? 0.0 : pow(2.0, 10 * (t - 1));
-    case EASE_out_expo: return t == 1 ? 1.0 : 1 - pow(2.0, -10 * t);
+        return u < 1 ? R(0.5) * u * u * u * u * u : R(0.5) * (v * v * v * v * v + 2);
+    case EASE_in_sine: return -r_cos(t * pi / 2) + 1;
+    case EASE_out_sine: return r_sin(t * pi / 2);
+    case EASE_in_out_sine: return -R(0.5) * (r_cos(pi * t) - 1);
+    case EASE_in_expo: return t == 0 ? R(0.0) : r_pow(R(2.0), 10 * (t - 1));
+    case EASE_out_expo: return t == 1 ? R(1.0) : 1 - r_pow(R(2.0), -10 * t);
     case EASE_in_out_expo:
-        if (t == 0) return 0.0;
-        if (t == 1) return 1.0;
-        return t < 0.5 ? 0.5 * pow(2.0, 20 * t - 10) : 1 - 0.5 * pow(2.0, -20 * t + 10);
-    case EASE_in_circ: return -1 * (sqrt(1 - t * t) - 1);
-    case EASE_out_circ: u = t - 1; return sqrt(1 - u * u);
+        if (t == 0) return R(0.0);
+        if (t == 1) return R(1.0);
+        return t < R(0.5) ? R(0.5) * r_pow(R(2.0), 20 * t - 10) : 1 - R(0.5) * r_pow(R(2.0), -20 * t + 10);
+    case EASE_in_circ: return -1 * (r_sqrt(1 - t * t) - 1);
+    case EASE_out_circ: u = t - 1; return r_sqrt(1 - u * u);
     case EASE_in_out_circ:
         u = t * 2; v = u - 2;
-        return u < 1 ? -0.5 * (sqrt(1 - u * u) - 1) : 0.5 * (sqrt(1 - v * v) + 1);
+        return u < 1 ? -R(0.5) * (r_sqrt(1 - u * u) - 1) : R(0.5) * (r_sqrt(1 - v * v) + 1);
     case EASE_in_elastic: {
-        const double k = 0.5; u = t - 1;
-        return -1 * (pow(2.0, 10 * u) * sin((u - k / 4) * (2 * pi) / k)); }
+        const real k = R(0.5); u = t - 1;
+        return -1 * (r_pow(R(2.0), 10 * u) * r_sin((u - k / 4) * (2 * pi) / k)); }
     case EASE_out_elastic: {
-        const double k = 0.5;
-        return pow(2.0, -10 * t) * sin((t - k / 4) * (2 * pi / k)) + 1; }
+        const real k = R(0.5);
+        return r_pow(R(2.0), -10 * t) * r_sin((t - k / 4) * (2 * pi / k)) + 1; }
     case EASE_in_out_elastic: {
-        const double k = 0.5; u = t * 2; v = u - 1;
-        a = -0.5 * (pow(2.0, 10 * v) * sin((v - k / 4) * 2 * pi / k));
-        b = pow(2.0, -10 * v) * sin((v - k / 4) * 2 * pi / k) * 0.5 + 1;
+        const real k = R(0.5); u = t * 2; v = u - 1;
+        a = -R(0.5) * (r_pow(R(2.0), 10 * v) * r_sin((v - k / 4) * 2 * pi / k));
+        b = r_pow(R(2.0), -10 * v) * r_sin((v - k / 4) * 2 * pi / k) * R(0.5) + 1;
         return u < 1 ? a : b; }
-    case EASE_in_back: { const double k = 1.70158; return t * t * ((k + 1) * t - k); }
-    case EASE_out_back: { const double k = 1.70158; u = t - 1; return u * u * ((k + 1) * u + k) + 1; }
+    case EASE_in_back: { const real k = R(1.70158); return t * t * ((k + 1) * t - k); }
+    case EASE_out_back: { const real k = R(1.70158); u = t - 1; return u * u * ((k + 1) * u + k) + 1; }
     case EASE_in_out_back: {
-        const double k = 1.70158 * 1.525; u = t * 2; v = u - 2;
-        return u < 1 ? 0.5 * (u * u * ((k + 1) * u - k)) : 0.5 * (v * v * ((k + 1) * v + k) + 2); }
+        const real k = R(1.70158) * R(1.525); u = t * 2; v = u - 2;
+        return u < 1 ? R(0.5) * (u * u * ((k + 1) * u - k)) : R(0.5) * (v * v * ((k + 1) * v + k) + 2); }
     case EASE_in_bounce: return 1 - out_bounce(1 - t);
     case EASE_out_bounce: return out_bounce(t);
     case EASE_in_out_bounce:
-        return t < 0.5 ? (1 - out_bounce(1 - 2 * t)) * 0.5 : out_bounce(2 * t - 1) * 0.5 + 0.5;
-    case EASE_in_square: return t < 1 ? 0.0 : 1.0;
-    case EASE_out_square: return t > 0 ? 1.0 : 0.0;
-    case EASE_in_out_square: return t < 0.5 ? 0.0 : 1.0;
+        return t < R(0.5) ? (1 - out_bounce(1 - 2 * t)) * R(0.5) : out_bounce(2 * t - 1) * R(0.5) + R(0.5);
+    case EASE_in_square: return t < 1 ? R(0.0) : R(1.0);
+    case EASE_out_square: return t > 0 ? R(1.0) : R(0.0);
+    case EASE_in_out_square: return t < R(0.5) ? R(0.0) : R(1.0);
     }
-    return NAN;
+    return R_NAN;
 }
 
 /* ---- booleans: reference sdf/dn.py:7-58 ------------------------------------------ */
-static double fold_boolean(int op, double d1, double d2, int has_k, double K) {
-    double h, m;
+static real fold_boolean(int op, real d1, real d2, int has_k, real K) {
+    real h, m;
     switch (op) {
     case NODE_union:
         if (!has_k) return np_min(d1, d2);
-        h = np_clip(0.5 + 0.5 * (d2 - d1) / K, 0, 1);
+        h = np_clip(R(0.5) + R(0.5) * (d2 - d1) / K, 0, 1);
         m = d2 + (d1 - d2) * h;
         return m - K * h * (1 - h);
     case NODE_difference:
         if (!has_k) return np_max(d1, -d2);
-        h = np_clip(0.5 - 0.5 * (d2 + d1) / K, 0, 1);
+        h = np_clip(R(0.5) - R(0.5) * (d2 + d1) / K, 0, 1);
         m = d1 + (-d2 - d1) * h;
         return m + K * h * (1 - h);
     case NODE_intersection:
         if (!has_k) return np_max(d1, d2);
-        h = np_clip(0.5 - 0.5 * (d2 - d1) / K, 0, 1);
+        h = np_clip(R(0.5) - R(0.5) * (d2 - d1) / K, 0, 1);
         m = d2 + (d1 - d2) * h;
         return m + K * h * (1 - h);
     case NODE_blend:
         return K * d2 + (1 - K) * d1;
     }
-    return NAN;
+    return R_NAN;
 }
 
-static double box_like(double qx, double qy, double qz) {
+static real box_like(real qx, real qy, real qz) {
     /* _length(_max(q, 0)) + _min(np.amax(q, axis=1), 0) */
-    double mx = np_max(np_max(qx, qy), qz);
+    real mx = np_max(np_max(qx, qy), qz);
     return len3(np_max(qx, 0), np_max(qy, 0), np_max(qz, 0)) + np_min(mx, 0);
 }
 
-static double eval_node(const tree_t *t, int id, const double *p);
+static real eval_node(const tree_t *t, int id, const real *p);
 
-static inline double child(const tree_t *t, const int32_t *n, int i, const double *p) {
+static inline real child(const tree_t *t, const int32_t *n, int i, const real *p) {
     return eval_node(t, t->children[n[3] + i], p);
 }
 
-static double eval_node(const tree_t *t, int id, const double *p) {
+static real eval_node(const tree_t *t, int id, const real *p) {
     const int32_t *n = t->nodes + 5 * id;
-    const double *c = t->params + n[1];
-    const double x = p[0], y = p[1], z = p[2];
-    double q[3];
+    const real *c = t->params + n[1];
+    const real x = p[0], y = p[1], z = p[2];
+    real q[3];
     switch (n[0]) {
     /* ---------------- 3-D leaves ---------------- */
     case NODE_sphere:  /* d3.py:92-96 */
@@ -196,91 +237,91 @@ static double eval_node(const tree_t *t, int id, const double *p) {
     case NODE_plane:   /* d3.py:98-103: np.dot(point - p, normal) */
         return dot3(c[3] - x, c[4] - y, c[5] - z, c[0], c[1], c[2]);
     case NODE_box:     /* d3.py:122-134 */
-        return box_like(fabs(x - c[0]) - c[3], fabs(y - c[1]) - c[4], fabs(z - c[2]) - c[5]);
+        return box_like(r_fabs(x - c[0]) - c[3], r_fabs(y - c[1]) - c[4], r_fabs(z - c[2]) - c[5]);
     case NODE_rounded_box: /* d3.py:136-142 */
-        return box_like(fabs(x) - c[0] + c[3], fabs(y) - c[1] + c[3], fabs(z) - c[2] + c[3]) - c[3];
+        return box_like(r_fabs(x) - c[0] + c[3], r_fabs(y) - c[1] + c[3], r_fabs(z) - c[2] + c[3]) - c[3];
     case NODE_wireframe_box: { /* d3.py:144-155 */
-        double t2 = c[3];
-        double px = fabs(x) - c[0] - t2, py = fabs(y) - c[1] - t2, pz = fabs(z) - c[2] - t2;
-        double qx = fabs(px + t2) - t2, qy = fabs(py + t2) - t2, qz = fabs(pz + t2) - t2;
+        real t2 = c[3];
+        real px = r_fabs(x) - c[0] - t2, py = r_fabs(y) - c[1] - t2, pz = r_fabs(z) - c[2] - t2;
+        real qx = r_fabs(px + t2) - t2, qy = r_fabs(py + t2) - t2, qz = r_fabs(pz + t2) - t2;
 #define WG(a, b, cc) (len3(np_max(a, 0), np_max(b, 0), np_max(cc, 0)) + np_min(np_max(a, np_max(b, cc)), 0))
-        double g1 = WG(px, qy, qz), g2 = WG(qx, py, qz), g3 = WG(qx, qy, pz);
+        real g1 = WG(px, qy, qz), g2 = WG(qx, py, qz), g3 = WG(qx, qy, pz);
 #undef WG
         return np_min(np_min(g1, g2), g3); }
     case NODE_torus: { /* d3.py:157-165 */
-        double a = len2(x, y) - c[0];
+        real a = len2(x, y) - c[0];
         return len2(a, z) - c[1]; }
     case NODE_capsule: { /* d3.py:167-176 */
-        double pax = x - c[0], pay = y - c[1], paz = z - c[2];
-        double h = np_clip(dot3(pax, pay, paz, c[3], c[4], c[5]) / c[6], 0, 1);
+        real pax = x - c[0], pay = y - c[1], paz = z - c[2];
+        real h = np_clip(dot3(pax, pay, paz, c[3], c[4], c[5]) / c[6], 0, 1);
         return len3(pax - c[3] * h, pay - c[4] * h, paz - c[5] * h) - c[7]; }
     case NODE_cylinder: /* d3.py:178-182 */
         return len2(x, y) - c[0];
     case NODE_capped_cylinder: { /* d3.py:184-204 */
-        double bax = c[3], bay = c[4], baz = c[5], baba = c[6];
-        double pax = x - c[0], pay = y - c[1], paz = z - c[2];
-        double paba = dot3(pax, pay, paz, bax, bay, baz);
-        double xx = len3(pax * baba - bax * paba, pay * baba - bay * paba, paz * baba - baz * paba) - c[8];
-        double yy = fabs(paba - c[9]) - c[9];
-        double x2 = xx * xx, y2 = yy * yy * baba, d;
+        real bax = c[3], bay = c[4], baz = c[5], baba = c[6];
+        real pax = x - c[0], pay = y - c[1], paz = z - c[2];
+        real paba = dot3(pax, pay, paz, bax, bay, baz);
+        real xx = len3(pax * baba - bax * paba, pay * baba - bay * paba, paz * baba - baz * paba) - c[8];
+        real yy = r_fabs(paba - c[9]) - c[9];
+        real x2 = xx * xx, y2 = yy * yy * baba, d;
         if (np_max(xx, yy) < 0) d = -np_min(x2, y2);
         else d = (xx > 0 ? x2 : 0) + (yy > 0 ? y2 : 0);
-        return np_sign(d) * sqrt(fabs(d)) / baba; }
+        return np_sign(d) * r_sqrt(r_fabs(d)) / baba; }
     case NODE_rounded_cylinder: { /* d3.py:206-215 */
-        double d0 = len2(x, y) - c[0] + c[1];
-        double d1 = fabs(z) - c[2] + c[1];
+        real d0 = len2(x, y) - c[0] + c[1];
+        real d1 = r_fabs(z) - c[2] + c[1];
         return np_min(np_max(d0, d1), 0) + len2(np_max(d0, 0), np_max(d1, 0)) - c[1]; }
     case NODE_capped_cone: { /* d3.py:217-237 */
-        double ra = c[6], rb = c[7], baba = c[8], rba = c[9], k = c[10];
-        double pax = x - c[0], pay = y - c[1], paz = z - c[2];
-        double papa = (pax * pax + pay * pay) + paz * paz;
-        double paba = dot3(pax, pay, paz, c[3], c[4], c[5]) / baba;
-        double xx = sqrt(papa - paba * paba * baba);
-        double cax = np_max(0, xx - (paba < 0.5 ? ra : rb));
-        double cay = fabs(paba - 0.5) - 0.5;
-        double f = np_clip((rba * (xx - ra) + paba * baba) / k, 0, 1);
-        double cbx = xx - ra - f * rba;
-        double cby = paba - f;
-        double s = (cbx < 0 && cay < 0) ? -1 : 1;
-        return s * sqrt(np_min(cax * cax + cay * cay * baba, cbx * cbx + cby * cby * baba)); }
+        real ra = c[6], rb = c[7], baba = c[8], rba = c[9], k = c[10];
+        real pax = x - c[0], pay = y - c[1], paz = z - c[2];
+        real papa = (pax * pax + pay * pay) + paz * paz;
+        real paba = dot3(pax, pay, paz, c[3], c[4], c[5]) / baba;
+        real xx = r_sqrt(papa - paba * paba * baba);
+        real cax = np_max(0, xx - (paba < R(0.5) ? ra : rb));
+        real cay = r_fabs(paba - R(0.5)) - R(0.5);
+        real f = np_clip((rba * (xx - ra) + paba * baba) / k, 0, 1);
+        real cbx = xx - ra - f * rba;
+        real cby = paba - f;
+        real s = (cbx < 0 && cay < 0) ? -1 : 1;
+        return s * r_sqrt(np_min(cax * cax + cay * cay * baba, cbx * cbx + cby * cby * baba)); }
     case NODE_rounded_cone: { /* d3.py:239-250 */
-        double r1 = c[0], r2 = c[1], h = c[2], b = c[3], a = c[4], ah = c[5];
-        double qx = len2(x, y), qy = z;
-        double k = dot2(qx, qy, -b, a);
-        double c1 = len2(qx, qy) - r1;
-        double c2 = len2(qx - 0, qy - h) - r2;
-        double c3 = dot2(qx, qy, a, b) - r1;
+        real r1 = c[0], r2 = c[1], h = c[2], b = c[3], a = c[4], ah = c[5];
+        real qx = len2(x, y), qy = z;
+        real k = dot2(qx, qy, -b, a);
+        real c1 = len2(qx, qy) - r1;
+        real c2 = len2(qx - 0, qy - h) - r2;
+        real c3 = dot2(qx, qy, a, b) - r1;
         return k < 0 ? c1 : (k > ah ? c2 : c3); }
     case NODE_ellipsoid: { /* d3.py:252-259 */
-        double k0 = len3(x / c[0], y / c[1], z / c[2]);
-        double k1 = len3(x / c[3], y / c[4], z / c[5]);
+        real k0 = len3(x / c[0], y / c[1], z / c[2]);
+        real k1 = len3(x / c[3], y / c[4], z / c[5]);
         return k0 * (k0 - 1) / k1; }
     case NODE_pyramid: { /* d3.py:261-282 */
-        double h = c[0], m2 = c[1], m2q = c[2];
-        double a0 = fabs(x) - 0.5, a1 = fabs(y) - 0.5;
-        if (a1 > a0) { double tmp = a0; a0 = a1; a1 = tmp; }
-        double px = a0, py = z, pz = a1;
-        double qx = pz, qy = h * py - 0.5 * px, qz = h * px + 0.5 * py;
-        double s = np_max(-qx, 0);
-        double tt = np_clip((qy - 0.5 * pz) / m2q, 0, 1);
-        double a = m2 * ((qx + s) * (qx + s)) + qy * qy;
-        double b = m2 * ((qx + 0.5 * tt) * (qx + 0.5 * tt)) + (qy - m2 * tt) * (qy - m2 * tt);
-        double d2 = np_min(qy, -qx * m2 - qy * 0.5) > 0 ? 0 : np_min(a, b);
-        return sqrt((d2 + qz * qz) / m2) * np_sign(np_max(qz, -py)); }
+        real h = c[0], m2 = c[1], m2q = c[2];
+        real a0 = r_fabs(x) - R(0.5), a1 = r_fabs(y) - R(0.5);
+        if (a1 > a0) { real tmp = a0; a0 = a1; a1 = tmp; }
+        real px = a0, py = z, pz = a1;
+        real qx = pz, qy = h * py - R(0.5) * px, qz = h * px + R(0.5) * py;
+        real s = np_max(-qx, 0);
+        real tt = np_clip((qy - R(0.5) * pz) / m2q, 0, 1);
+        real a = m2 * ((qx + s) * (qx + s)) + qy * qy;
+        real b = m2 * ((qx + R(0.5) * tt) * (qx + R(0.5) * tt)) + (qy - m2 * tt) * (qy - m2 * tt);
+        real d2 = np_min(qy, -qx * m2 - qy * R(0.5)) > 0 ? 0 : np_min(a, b);
+        return r_sqrt((d2 + qz * qz) / m2) * np_sign(np_max(qz, -py)); }
     case NODE_tetrahedron: /* d3.py:286-293 */
-        return (np_max(fabs(x + y) - z, fabs(x - y) + z) - c[0]) / c[1];
+        return (np_max(r_fabs(x + y) - z, r_fabs(x - y) + z) - c[0]) / c[1];
     case NODE_octahedron:  /* d3.py:295-299: np.sum(np.abs(p), axis=1) */
-        return (((fabs(x) + fabs(y)) + fabs(z)) - c[0]) * c[1];
+        return (((r_fabs(x) + r_fabs(y)) + r_fabs(z)) - c[0]) * c[1];
     case NODE_dodecahedron: { /* d3.py:301-311 */
-        double r = c[0], X = c[1], Y = c[2], Z = c[3];
-        double ax = fabs(x / r), ay = fabs(y / r), az = fabs(z / r);
-        double a = dot3(ax, ay, az, X, Y, Z), b = dot3(ax, ay, az, Z, X, Y), cc = dot3(ax, ay, az, Y, Z, X);
+        real r = c[0], X = c[1], Y = c[2], Z = c[3];
+        real ax = r_fabs(x / r), ay = r_fabs(y / r), az = r_fabs(z / r);
+        real a = dot3(ax, ay, az, X, Y, Z), b = dot3(ax, ay, az, Z, X, Y), cc = dot3(ax, ay, az, Y, Z, X);
         return (np_max(np_max(a, b), cc) - X) * r; }
     case NODE_icosahedron: { /* d3.py:313-325 */
-        double r = c[0], X = c[1], Y = c[2], Z = c[3], w = c[4];
-        double ax = fabs(x / r), ay = fabs(y / r), az = fabs(z / r);
-        double a = dot3(ax, ay, az, X, Y, Z), b = dot3(ax, ay, az, Z, X, Y), cc = dot3(ax, ay, az, Y, Z, X);
-        double d = dot3(ax, ay, az, w, w, w) - X;
+        real r = c[0], X = c[1], Y = c[2], Z = c[3], w = c[4];
+        real ax = r_fabs(x / r), ay = r_fabs(y / r), az = r_fabs(z / r);
+        real a = dot3(ax, ay, az, X, Y, Z), b = dot3(ax, ay, az, Z, X, Y), cc = dot3(ax, ay, az, Y, Z, X);
+        real d = dot3(ax, ay, az, w, w, w) - X;
         return np_max(np_max(np_max(a, b), cc) - X, d) * r; }
     /* ---------------- 3-D transforms ---------------- */
     case NODE_translate: /* d3.py:329-333 */
@@ -295,84 +336,84 @@ static double eval_node(const tree_t *t, int id, const double *p) {
         q[2] = dot3(x, y, z, c[2], c[5], c[8]);
         return child(t, n, 0, q);
     case NODE_circular_array: { /* d3.py:379-392 */
-        double da = c[0];
-        double d = hypot(x, y);
-        double a = np_mod(atan2(y, x), da);
-        q[0] = cos(a - da) * d; q[1] = sin(a - da) * d; q[2] = z;
-        double d1 = child(t, n, 0, q);
-        q[0] = cos(a) * d; q[1] = sin(a) * d; q[2] = z;
-        double d2 = child(t, n, 0, q);
+        real da = c[0];
+        real d = r_hypot(x, y);
+        real a = np_mod(r_atan2(y, x), da);
+        q[0] = r_cos(a - da) * d; q[1] = r_sin(a - da) * d; q[2] = z;
+        real d1 = child(t, n, 0, q);
+        q[0] = r_cos(a) * d; q[1] = r_sin(a) * d; q[2] = z;
+        real d2 = child(t, n, 0, q);
         return np_min(d1, d2); }
     case NODE_elongate: { /* d3.py:396-405 */
-        double qx = fabs(x) - c[0], qy = fabs(y) - c[1], qz = fabs(z) - c[2];
-        double w = np_min(np_max(qx, np_max(qy, qz)), 0);
+        real qx = r_fabs(x) - c[0], qy = r_fabs(y) - c[1], qz = r_fabs(z) - c[2];
+        real w = np_min(np_max(qx, np_max(qy, qz)), 0);
         q[0] = np_max(qx, 0); q[1] = np_max(qy, 0); q[2] = np_max(qz, 0);
         return child(t, n, 0, q) + w; }
     case NODE_twist: {  /* d3.py:407-419 */
-        double cc = cos(c[0] * z), s = sin(c[0] * z);
+        real cc = r_cos(c[0] * z), s = r_sin(c[0] * z);
         q[0] = cc * x - s * y; q[1] = s * x + cc * y; q[2] = z;
         return child(t, n, 0, q); }
     case NODE_bend: {   /* d3.py:421-433 */
-        double cc = cos(c[0] * x), s = sin(c[0] * x);
+        real cc = r_cos(c[0] * x), s = r_sin(c[0] * x);
         q[0] = cc * x - s * y; q[1] = s * x + cc * y; q[2] = z;
         return child(t, n, 0, q); }
     case NODE_bend_linear: { /* d3.py:435-445 */
-        double tt = np_clip(dot3(x - c[0], y - c[1], z - c[2], c[3], c[4], c[5]) / c[6], 0, 1);
+        real tt = np_clip(dot3(x - c[0], y - c[1], z - c[2], c[3], c[4], c[5]) / c[6], 0, 1);
         tt = ease_apply((int)c[10], tt);
         q[0] = x + tt * c[7]; q[1] = y + tt * c[8]; q[2] = z + tt * c[9];
         return child(t, n, 0, q); }
     case NODE_bend_radial: { /* d3.py:447-457 */
-        double r = hypot(x, y);
-        double tt = np_clip((r - c[0]) / c[1], 0, 1);
+        real r = r_hypot(x, y);
+        real tt = np_clip((r - c[0]) / c[1], 0, 1);
         q[0] = x; q[1] = y; q[2] = z - c[2] * ease_apply((int)c[3], tt);
         return child(t, n, 0, q); }
     case NODE_wrap_around: { /* d3.py:483-502 */
-        const double pi = 3.141592653589793;
-        double d = hypot(x, y) - c[9];
-        double a = atan2(y, x);
-        double tt = ease_apply((int)c[10], (a + pi) / (2 * pi));
+        const real pi = R(3.141592653589793);
+        real d = r_hypot(x, y) - c[9];
+        real a = r_atan2(y, x);
+        real tt = ease_apply((int)c[10], (a + pi) / (2 * pi));
         q[0] = c[0] + c[3] * tt + c[6] * d;
         q[1] = c[1] + c[4] * tt + c[7] * d;
         q[2] = z;
         return child(t, n, 0, q); }
     case NODE_transition_linear: { /* d3.py:459-470 */
-        double d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
-        double tt = np_clip(dot3(x - c[0], y - c[1], z - c[2], c[3], c[4], c[5]) / c[6], 0, 1);
+        real d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
+        real tt = np_clip(dot3(x - c[0], y - c[1], z - c[2], c[3], c[4], c[5]) / c[6], 0, 1);
         tt = ease_apply((int)c[7], tt);
         return tt * d2 + (1 - tt) * d1; }
     case NODE_transition_radial: { /* d3.py:472-481 */
-        double d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
-        double r = hypot(x, y);
-        double tt = ease_apply((int)c[2], np_clip((r - c[0]) / c[1], 0, 1));
+        real d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
+        real r = r_hypot(x, y);
+        real tt = ease_apply((int)c[2], np_clip((r - c[0]) / c[1], 0, 1));
         return tt * d2 + (1 - tt) * d1; }
     /* ---------------- dimension-agnostic ---------------- */
     case NODE_union: case NODE_difference: case NODE_intersection: case NODE_blend: {
         /* dn.py:7-58; params are (has_k, K) per right operand, resolved by the front end */
-        double d1 = child(t, n, 0, p);
+        real d1 = child(t, n, 0, p);
         for (int i = 1; i < n[4]; i++) {
-            double d2 = child(t, n, i, p);
+            real d2 = child(t, n, i, p);
             d1 = fold_boolean(n[0], d1, d2, c[2 * (i - 1)] != 0, c[2 * (i - 1) + 1]);
         }
         return d1; }
     case NODE_negate: return -child(t, n, 0, p);            /* dn.py:60-63 */
     case NODE_dilate: return child(t, n, 0, p) - c[0];      /* dn.py:65-68 */
     case NODE_erode:  return child(t, n, 0, p) + c[0];      /* dn.py:70-73 */
-    case NODE_shell:  return fabs(child(t, n, 0, p)) - c[0]; /* dn.py:75-78 */
+    case NODE_shell:  return r_fabs(child(t, n, 0, p)) - c[0]; /* dn.py:75-78 */
     case NODE_repeat: { /* dn.py:80-112; params: dim, s[3], has_count, count[3], nn, n[nn][3] */
         int dim = (int)c[0], nn = (int)c[8];
-        double idx[3] = {0, 0, 0};
+        real idx[3] = {0, 0, 0};
         for (int i = 0; i < dim; i++) {
-            double s = c[1 + i];
-            double qq = s != 0 ? p[i] / s : 0.0;
-            double r = nearbyint(qq);                      /* np.round: half to even */
+            real s = c[1 + i];
+            real qq = s != 0 ? p[i] / s : R(0.0);
+            real r = r_nearbyint(qq);                      /* np.round: half to even */
             if (c[4] != 0) r = np_clip(r, -c[5 + i], c[5 + i]);
             idx[i] = r;
         }
-        double best = 0;
+        real best = 0;
         for (int k = 0; k < nn; k++) {
             q[0] = x; q[1] = y; q[2] = z;
             for (int i = 0; i < dim; i++) q[i] = p[i] - c[1 + i] * (idx[i] + c[9 + 3 * k + i]);
-            double d = child(t, n, 0, q);
+            real d = child(t, n, 0, q);
             best = k == 0 ? d : np_min(best, d);
         }
         return best; }
@@ -382,82 +423,82 @@ static double eval_node(const tree_t *t, int id, const double *p) {
     case NODE_line:    /* d2.py:82-87 */
         return dot2(c[2] - x, c[3] - y, c[0], c[1]);
     case NODE_rectangle: { /* d2.py:102-114 */
-        double qx = fabs(x - c[0]) - c[2], qy = fabs(y - c[1]) - c[3];
+        real qx = r_fabs(x - c[0]) - c[2], qy = r_fabs(y - c[1]) - c[3];
         return len2(np_max(qx, 0), np_max(qy, 0)) + np_min(np_max(qx, qy), 0); }
     case NODE_rounded_rectangle: { /* d2.py:116-134 */
-        double r = 0;
+        real r = 0;
         if (x > 0 && y > 0) r = c[2];
         if (x > 0 && y <= 0) r = c[3];
         if (x <= 0 && y <= 0) r = c[4];
         if (x <= 0 && y > 0) r = c[5];
-        double qx = fabs(x) - c[0] + r, qy = fabs(y) - c[1] + r;
+        real qx = r_fabs(x) - c[0] + r, qy = r_fabs(y) - c[1] + r;
         return np_min(np_max(qx, qy), 0) + len2(np_max(qx, 0), np_max(qy, 0)) - r; }
     case NODE_equilateral_triangle: { /* d2.py:136-152 */
-        double k = c[0];
-        double px = fabs(x) - 1, py = y + c[1];
+        real k = c[0];
+        real px = r_fabs(x) - 1, py = y + c[1];
         if (px + k * py > 0) {
-            double nx = (px - k * py) / 2, ny = (-k * px - py) / 2;
+            real nx = (px - k * py) / 2, ny = (-k * px - py) / 2;
             px = nx; py = ny;
         }
         px = px - np_clip(px, -2, 0);
         return -len2(px, py) * np_sign(py); }
     case NODE_hexagon: { /* d2.py:154-165 */
-        double r = c[0], k0 = c[1], k1 = c[2];
-        double px = fabs(x), py = fabs(y);
-        double m = np_min(k0 * px + k1 * py, 0);
+        real r = c[0], k0 = c[1], k1 = c[2];
+        real px = r_fabs(x), py = r_fabs(y);
+        real m = np_min(k0 * px + k1 * py, 0);
         px -= c[4] * m; py -= c[5] * m;
-        px -= np_clip(px, c[6], c[7]); py -= (0.0 + r);
+        px -= np_clip(px, c[6], c[7]); py -= (R(0.0) + r);
         return len2(px, py) * np_sign(py); }
     case NODE_rounded_x: { /* d2.py:167-173 */
-        double px = fabs(x), py = fabs(y);
-        double qq = np_min(px + py, c[0]) * 0.5;
+        real px = r_fabs(x), py = r_fabs(y);
+        real qq = np_min(px + py, c[0]) * R(0.5);
         return len2(px - qq, py - qq) - c[1]; }
     case NODE_polygon: { /* d2.py:175-196 */
         int np_ = (int)c[0];
-        const double *v = c + 1;
-        double dx = x - v[0], dy = y - v[1];
-        double d = dx * dx + dy * dy;
-        double s = 1.0;
+        const real *v = c + 1;
+        real dx = x - v[0], dy = y - v[1];
+        real d = dx * dx + dy * dy;
+        real s = R(1.0);
         for (int i = 0; i < np_; i++) {
             int j = (i + np_ - 1) % np_;
-            double vix = v[2 * i], viy = v[2 * i + 1], vjx = v[2 * j], vjy = v[2 * j + 1];
-            double ex = vjx - vix, ey = vjy - viy;
-            double wx = x - vix, wy = y - viy;
-            double ee = dot2(ex, ey, ex, ey);  /* np.dot(e, e): 1-D ddot */
-            double cl = np_clip(dot2(wx, wy, ex, ey) / ee, 0, 1);
-            double bx = wx - ex * cl, by = wy - ey * cl;
+            real vix = v[2 * i], viy = v[2 * i + 1], vjx = v[2 * j], vjy = v[2 * j + 1];
+            real ex = vjx - vix, ey = vjy - viy;
+            real wx = x - vix, wy = y - viy;
+            real ee = dot2(ex, ey, ex, ey);  /* np.dot(e, e): 1-D ddot */
+            real cl = np_clip(dot2(wx, wy, ex, ey) / ee, 0, 1);
+            real bx = wx - ex * cl, by = wy - ey * cl;
             d = np_min(d, bx * bx + by * by);
             int c1 = y >= viy, c2 = y < vjy, c3 = ex * wy > ey * wx;
             if ((c1 && c2 && c3) || (!c1 && !c2 && !c3)) s = -s;
         }
-        return s * sqrt(d); }
+        return s * r_sqrt(d); }
     case NODE_vesica: { /* d2.py:198-207 */
-        double r = c[0], d = c[1], b = c[2];
-        double px = fabs(x), py = fabs(y);
+        real r = c[0], d = c[1], b = c[2];
+        real px = r_fabs(x), py = r_fabs(y);
         if ((py - b) * d > px * b) return len2(px - 0, py - b);
         return len2(px - (-d), py - 0) - r; }
     /* ---------------- 2-D transforms ---------------- */
     case NODE_texture2d: { /* text.py:116-153: bilinear lookup into the distance texture, fallback
                             * rectangle outside it.  c: x0 y0 x1 y1 pw ph px py tw th rect(4) tex[th][tw] */
         long tw = (long)c[8], th = (long)c[9];
-        const double *tex = c + 14;
-        double u = (x - c[0]) / (c[2] - c[0]);
-        double v = (y - c[1]) / (c[3] - c[1]);
+        const real *tex = c + 14;
+        real u = (x - c[0]) / (c[2] - c[0]);
+        real v = (y - c[1]) / (c[3] - c[1]);
         v = 1 - v;
-        double fi = u * c[4] + c[6], fj = v * c[5] + c[7];
+        real fi = u * c[4] + c[6], fj = v * c[5] + c[7];
         /* _bilinear_interpolate (:138-153): np.floor(...).astype(int), then np.clip */
-        double gi = floor(fi), gj = floor(fj);
-        long a0 = gi != gi ? 0 : (gi < -2 ? -2 : (gi > (double)tw ? tw : (long)gi));
-        long b0 = gj != gj ? 0 : (gj < -2 ? -2 : (gj > (double)th ? th : (long)gj));
+        real gi = r_floor(fi), gj = r_floor(fj);
+        long a0 = gi != gi ? 0 : (gi < -2 ? -2 : (gi > (real)tw ? tw : (long)gi));
+        long b0 = gj != gj ? 0 : (gj < -2 ? -2 : (gj > (real)th ? th : (long)gj));
         long ix0 = a0 < 0 ? 0 : (a0 > tw - 1 ? tw - 1 : a0), ix1 = a0 + 1 < 0 ? 0 : (a0 + 1 > tw - 1 ? tw - 1 : a0 + 1);
         long iy0 = b0 < 0 ? 0 : (b0 > th - 1 ? th - 1 : b0), iy1 = b0 + 1 < 0 ? 0 : (b0 + 1 > th - 1 ? th - 1 : b0 + 1);
-        double pa = tex[iy0 * tw + ix0], pb = tex[iy1 * tw + ix0], pc = tex[iy0 * tw + ix1], pd = tex[iy1 * tw + ix1];
-        double wa = ((double)ix1 - fi) * ((double)iy1 - fj), wb = ((double)ix1 - fi) * (fj - (double)iy0);
-        double wc = (fi - (double)ix0) * ((double)iy1 - fj), wd = (fi - (double)ix0) * (fj - (double)iy0);
-        double d = wa * pa + wb * pb + wc * pc + wd * pd;
-        double qx = fabs(x - c[10]) - c[12], qy = fabs(y - c[11]) - c[13];
-        double qd = len2(np_max(qx, 0), np_max(qy, 0)) + np_min(np_max(qx, qy), 0);
-        int outside = (fi < 0) || (fi >= (double)(tw - 1)) || (fj < 0) || (fj >= (double)(th - 1));
+        real pa = tex[iy0 * tw + ix0], pb = tex[iy1 * tw + ix0], pc = tex[iy0 * tw + ix1], pd = tex[iy1 * tw + ix1];
+        real wa = ((real)ix1 - fi) * ((real)iy1 - fj), wb = ((real)ix1 - fi) * (fj - (real)iy0);
+        real wc = (fi - (real)ix0) * ((real)iy1 - fj), wd = (fi - (real)ix0) * (fj - (real)iy0);
+        real d = wa * pa + wb * pb + wc * pc + wd * pd;
+        real qx = r_fabs(x - c[10]) - c[12], qy = r_fabs(y - c[11]) - c[13];
+        real qd = len2(np_max(qx, 0), np_max(qy, 0)) + np_min(np_max(qx, qy), 0);
+        int outside = (fi < 0) || (fi >= (real)(tw - 1)) || (fj < 0) || (fj >= (real)(th - 1));
         return outside ? qd : d; }
     case NODE_grid3d: { /* mesh.py:96-105 `f`: np.where(e > background, e, interpolator(p)) with e = box(a=a, b=b)
                          * (d3.py:122-134) and scipy 1.7.1 RegularGridInterpolator(method='linear', bounds_error=False,
@@ -466,19 +507,19 @@ static double eval_node(const tree_t *t, int id, const double *p) {
                          * itertools.product order: weight = ((1. * wx) * wy) * wz; values += float32 voxel * weight).
                          * c: nx ny nz background box-centre(3) box-half-size(3) X[nx] Y[ny] Z[nz] A[nx][ny][nz] */
         long n3[3] = {(long)c[0], (long)c[1], (long)c[2]};
-        double bg = c[3];
-        const double *g[3] = {c + 10, c + 10 + n3[0], c + 10 + n3[0] + n3[1]};
-        const double *vox = c + 10 + n3[0] + n3[1] + n3[2];
-        double qx = fabs(x - c[4]) - c[7], qy = fabs(y - c[5]) - c[8], qz = fabs(z - c[6]) - c[9];
-        double e = len3(np_max(qx, 0), np_max(qy, 0), np_max(qz, 0)) + np_min(np_max(np_max(qx, qy), qz), 0);
-        double pp[3] = {x, y, z}, w[3];
+        real bg = c[3];
+        const real *g[3] = {c + 10, c + 10 + n3[0], c + 10 + n3[0] + n3[1]};
+        const real *vox = c + 10 + n3[0] + n3[1] + n3[2];
+        real qx = r_fabs(x - c[4]) - c[7], qy = r_fabs(y - c[5]) - c[8], qz = r_fabs(z - c[6]) - c[9];
+        real e = len3(np_max(qx, 0), np_max(qy, 0), np_max(qz, 0)) + np_min(np_max(np_max(qx, qy), qz), 0);
+        real pp[3] = {x, y, z}, w[3];
         long idx[3];
         int oob = 0;
         for (int a = 0; a < 3; a++) {
             long lo = 0, hi = n3[a];
             while (lo < hi) { /* np.searchsorted side='left'; NaN sorts last */
                 long mid = (lo + hi) >> 1;
-                double gm = g[a][mid];
+                real gm = g[a][mid];
                 if (gm < pp[a] || (pp[a] != pp[a] && gm == gm)) lo = mid + 1; else hi = mid;
             }
             long i = lo - 1; if (i < 0) i = 0; if (i > n3[a] - 2) i = n3[a] - 2;
@@ -486,16 +527,16 @@ static double eval_node(const tree_t *t, int id, const double *p) {
             w[a] = (pp[a] - g[a][i]) / (g[a][i + 1] - g[a][i]);
             oob = oob || pp[a] < g[a][0] || pp[a] > g[a][n3[a] - 1];
         }
-        double values = 0.0;
+        real values = R(0.0);
         for (int k = 0; k < 8; k++) {
             int o0 = k >> 2, o1 = (k >> 1) & 1, o2 = k & 1;
-            double weight = 1.0;
+            real weight = R(1.0);
             weight *= o0 ? w[0] : 1 - w[0];
             weight *= o1 ? w[1] : 1 - w[1];
             weight *= o2 ? w[2] : 1 - w[2];
             values += vox[((idx[0] + o0) * n3[1] + (idx[1] + o1)) * n3[2] + (idx[2] + o2)] * weight;
         }
-        double d = oob ? bg : values;
+        real d = oob ? bg : values;
         return e > bg ? e : d; }
     case NODE_translate2: q[0] = x - c[0]; q[1] = y - c[1]; q[2] = z; return child(t, n, 0, q);
     case NODE_scale2: q[0] = x / c[0]; q[1] = y / c[1]; q[2] = z; return child(t, n, 0, q) * c[2];
@@ -503,36 +544,64 @@ static double eval_node(const tree_t *t, int id, const double *p) {
         q[0] = dot2(x, y, c[0], c[2]); q[1] = dot2(x, y, c[1], c[3]); q[2] = z;
         return child(t, n, 0, q);
     case NODE_elongate2: { /* d2.py:249-257 */
-        double qx = fabs(x) - c[0], qy = fabs(y) - c[1];
-        double w = np_min(np_max(qx, qy), 0);
+        real qx = r_fabs(x) - c[0], qy = r_fabs(y) - c[1];
+        real w = np_min(np_max(qx, qy), 0);
         q[0] = np_max(qx, 0); q[1] = np_max(qy, 0); q[2] = z;
         return child(t, n, 0, q) + w; }
     /* ---------------- dimension changes ---------------- */
     case NODE_extrude: { /* d2.py:261-267 */
-        double d = child(t, n, 0, p);
-        double w1 = fabs(z) - c[0];
+        real d = child(t, n, 0, p);
+        real w1 = r_fabs(z) - c[0];
         return np_min(np_max(d, w1), 0) + len2(np_max(d, 0), np_max(w1, 0)); }
     case NODE_extrude_to: { /* d2.py:269-278 */
-        double d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
-        double tt = ease_apply((int)c[2], np_clip(z / c[0], -0.5, 0.5) + 0.5);
-        double d = d1 + (d2 - d1) * tt;
-        double w1 = fabs(z) - c[1];
+        real d1 = child(t, n, 0, p), d2 = child(t, n, 1, p);
+        real tt = ease_apply((int)c[2], np_clip(z / c[0], -R(0.5), R(0.5)) + R(0.5));
+        real d = d1 + (d2 - d1) * tt;
+        real w1 = r_fabs(z) - c[1];
         return np_min(np_max(d, w1), 0) + len2(np_max(d, 0), np_max(w1, 0)); }
     case NODE_revolve: /* d2.py:280-286 */
         q[0] = len2(x, y) - c[0]; q[1] = z; q[2] = 0;
         return child(t, n, 0, q);
     case NODE_slice: { /* d3.py:506-520 */
-        q[0] = x; q[1] = y; q[2] = 0.0;
-        double A = child(t, n, 0, q);
-        double B = -child(t, n, 1, q);
+        q[0] = x; q[1] = y; q[2] = R(0.0);
+        real A = child(t, n, 0, q);
+        real B = -child(t, n, 1, q);
         return A <= 0 ? B : A; }
     }
-    return NAN;
+    return R_NAN;
 }
 
 /* ================================================================================== */
 /* public C API (called through ctypes from tests/ and bench.py's cpu_baseline leg)    */
 /* ================================================================================== */
+
+#if ORACLE_F32
+/* one past the last parameter any node under `id` reads: the entry point is not told the array's length */
+static int64_t params_end(const int32_t *nodes, const int32_t *children, int id) {
+    const int32_t *n = nodes + 5 * id;
+    int64_t end = (int64_t)n[1] + n[2];
+    for (int i = 0; i < n[4]; i++) {
+        int64_t e = params_end(nodes, children, children[n[3] + i]);
+        if (e > end) end = e;
+    }
+    return end;
+}
+
+/* f(P) in float32: the parameters are rounded to float once (as the product rounds its constant table), every
+ * point on the way in; the float result is widened on the way out.  The caller's arrays stay float64. */
+void sdf_oracle_eval_tree(const int32_t *nodes, const double *params, const int32_t *children,
+                          int32_t root, const double *pts, int64_t n, int dim, double *out) {
+    int64_t np_ = params_end(nodes, children, root);
+    real *params32 = (real *)malloc(sizeof(real) * (size_t)(np_ > 0 ? np_ : 1));
+    for (int64_t i = 0; i < np_; i++) params32[i] = (real)params[i];
+    tree_t t = {nodes, params32, children, root};
+    for (int64_t i = 0; i < n; i++) {
+        real p[3] = {(real)pts[i * dim], (real)pts[i * dim + 1], dim > 2 ? (real)pts[i * dim + 2] : R(0.0)};
+        out[i] = (double)eval_node(&t, root, p);
+    }
+    free(params32);
+}
+#else
 
 static tree_t mk_tree(const int32_t *nodes, const double *params, const int32_t *children, int32_t root) {
     tree_t t = {nodes, params, children, root};
@@ -770,3 +839,4 @@ int sdf_oracle_estimate_bounds(const int32_t *nodes, const double *params, const
     for (int a = 0; a < 3; a++) { out6[a] = lo[a]; out6[3 + a] = hi[a]; }
     return 0;
 }
+#endif /* !ORACLE_F32 */

@@ -128,7 +128,13 @@ def _estimate_bounds(sdf):
             break
         prev = threshold
         volume = eng.eval_grid(tape, X, Y, Z)
-        where = np.argwhere(np.abs(volume) <= threshold)
+        reach = np.abs(volume)
+        if eng.precision != engine.PRECISION_F64:
+            # float32 values: 16 units of 2^-24 max(|v|, |p|inf, 1) are taken off before the comparison, as k_estimate_bounds_w<float>
+            # does (csrc/sdf_bounds.hip says why: without it no probe of the first round is within the threshold)
+            far = np.maximum(np.maximum(np.abs(X)[:, None, None], np.abs(Y)[None, :, None]), np.abs(Z)[None, None, :])
+            reach = reach - 2.0 ** -20 * np.maximum(np.maximum(reach, far), 1.0)
+        where = np.argwhere(reach <= threshold)
         x1, y1, z1 = (x0, y0, z0) + where.max(axis=0) * d + d / 2
         x0, y0, z0 = (x0, y0, z0) + where.min(axis=0) * d - d / 2
     return ((x0, y0, z0), (x1, y1, z1))

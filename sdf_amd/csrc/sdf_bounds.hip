@@ -58,7 +58,15 @@ __global__ __launch_bounds__(64) void k_estimate_bounds_w(const uint32_t *__rest
         prev = thr;
         const double x = i == 15 ? hi0 : lo0 + (double)i * s0, y = j == 15 ? hi1 : lo1 + (double)j * s1, z = k == 15 ? hi2 : lo2 + (double)k * s2;
         const T v = run_tape<T, FULL, NP, ND, 1>(code, consts, Vec<T, 1>((T)x), Vec<T, 1>((T)y), Vec<T, 1>((T)z)).v[0];
-        const bool hit = fabs((double)v) <= thr;
+        // float32: a probe's value carries the interpreter's rounding, up to 16 units of 2^-24 max(|v|, |p|inf, 1) on a well-conditioned
+        // model, and the FIRST round decides on less than that: its probes at +-6.7e7 lie sqrt(3) * 6.7e7 from the
+        // origin, which IS the threshold, and only the model's own size -- a few units against a float32 spacing of 8 -- puts them within
+        // it.  Without the allowance no round-0 probe of any model hits and the call fails.  (2^-20 = 16 * 2^-24: the product is exact,
+        // core._estimate_bounds states the same difference for its float32 loop and the two agree bit for bit.  Taken off |v|, not
+        // added to the threshold: an infinite value then compares as NaN and stays a miss.)
+        double av = fabs((double)v);
+        if constexpr (sizeof(T) == 4) av = av - 0x1p-20 * fmax(fmax(av, fmax(fmax(fabs(x), fabs(y)), fabs(z))), 1.0);
+        const bool hit = av <= thr;
         const unsigned mine_lo = wave_or_u32(hit ? (1u << i) | (1u << (16 + j)) : 0u), mine_hi = wave_or_u32(hit ? 1u << k : 0u);
         unsigned long long *slot = work + (size_t)it * BOUNDS_WAVES;
         if (lane == 0)
