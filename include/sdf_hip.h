@@ -449,7 +449,8 @@ double sdf_mesh_components_last_kernel_ms(void);
  * area, regularised by reg x trace towards the mean of the cluster's vertices, solved in closed form; a representative that is not
  * finite or leaves its cell is replaced by that mean (`mean_fallback`), a cluster of zero-area triangles only takes the mean too
  * (`flat`).  A triangle survives if its three clusters differ; survivors keep their order and winding (`collapsed` counts the
- * others).  Duplicate triangles and oppositely wound pairs are NOT removed (sdf_mesh_edge_census reports them), and topology is
+ * others).  Duplicate triangles and oppositely wound pairs are NOT removed unless the result goes through sdf_mesh_mend
+ * (sdf_mesh_edge_census reports them), and topology is
  * not preserved.  Every float sum is sequential in the definition's order (one lane per cluster): the result does not depend on
  * launch geometry or the order of atomics.  sdf_mesh_simplify welds the source first if that has not happened; it serves generated
  * meshes, meshes of sdf_generate_records, adopted soups and selections.  The new mesh OWNS its soup, like a selection's, and is what
@@ -467,6 +468,32 @@ int sdf_mesh_simplify(sdf_mesh *mesh, const double *origin3, const double *cell3
 /* the kernels of this thread's last sdf_mesh_simplify, milliseconds by HIP events; parts4 (or NULL): keys and numbering, the item
  * sort and its segments, k_cluster_vertex, live flags and emission (tools/simplify_time.py) */
 double sdf_mesh_simplify_last_kernel_ms(double *parts4);
+/* The mesh mended on the device (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4k, defined
+ * by tests/mend_ref.py and reproduced exactly): duplicate triangles are dropped and oppositely wound pairs cancel -- what
+ * sdf_mesh_simplify leaves behind where two sheets of a surface fall into the same clusters.  A cell of the weld with two equal
+ * indices is dropped (`collapsed`).  Every other cell, rotated so that its smallest index comes first, (a, b, c), has the face
+ * (a, min(b, c), max(b, c)) and the side b > c.  Of the cells of one face, n0 on one side and n1 on the other: n0 == n1 drops all of
+ * them (`cancelled`); otherwise one survives, the first in soup order of the majority side, and the others are `duplicates`.
+ * `faces` counts the distinct faces.  The survivors keep their order and winding, and their nine doubles are the source soup's, bit
+ * for bit.  triangles_in == triangles_out + collapsed + duplicates + cancelled.  Integers only: the result is a function of the
+ * welded cells and does not depend on launch geometry or the order of atomics.  NOT done: a misoriented mesh is not re-oriented,
+ * and where a thin wall collapsed only in part the rim of the collapsed region stays non-manifold (sdf_mesh_edge_census goes on
+ * reporting it).  sdf_mesh_mend welds the source first if that has not happened; it serves generated meshes, meshes of
+ * sdf_generate_records, adopted soups, selections and simplified meshes.  The new mesh OWNS its soup, like a selection's, and is
+ * what an adopted soup is for every reader; the source mesh stays valid and unchanged.  One scratch allocation (40 bytes per
+ * triangle and the library sort's), freed before the call returns whether it fails or not.  A mesh of 0 triangles, or one of which
+ * nothing survives, gives a mesh of 0 triangles (the first without a launch).  kernel_ms: the kernels alone, by HIP events.  Refused
+ * on the host before anything is allocated or launched, with return value 2: a NULL argument, 2^31 or more corners (3 x triangles;
+ * the vertices of a weld are no more than its corners).  Other failures return 1 with nothing left allocated; *out is written on
+ * success only. */
+typedef struct sdf_mend_stats {
+    int64_t triangles_in, triangles_out, collapsed, duplicates, cancelled, faces;
+    double kernel_ms;
+} sdf_mend_stats;
+int sdf_mesh_mend(sdf_mesh *mesh, sdf_mesh **out, sdf_mend_stats *stats);
+/* the kernels of this thread's last sdf_mesh_mend, milliseconds by HIP events; parts3 (or NULL): the keys, the two sorts, runs and
+ * emission (tools/mend_time.py) */
+double sdf_mesh_mend_last_kernel_ms(double *parts3);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -46,6 +46,8 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_components.o sdf_components.hip "$@" & pids="$pids $!"
 # (the mesh simplified by vertex clustering with quadric vertices: plain kernels, float64 rounded like NumPy's, hipCUB's radix sort and the scan of sdf_prims.hip, see sdf_simplify.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_simplify.o sdf_simplify.hip "$@" & pids="$pids $!"
+# (the mesh mended -- duplicate triangles dropped, oppositely wound pairs cancelled: plain kernels, integers only, hipCUB's radix sort, the scan of sdf_prims.hip and the copy of sdf_components.hip, see sdf_mend.hip)
+$HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_mend.o sdf_mend.hip "$@" & pids="$pids $!"
 # (the weld uses hipCUB's radix sort and scan; it has no floating-point arithmetic of its own)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build/sdf_weld.o sdf_weld.hip "$@" & pids="$pids $!"
 # (numbering flagged items for the mesh readers: hipCUB's exclusive int scan, instantiated here once; no floating point, the weld's flags)
@@ -53,4 +55,4 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
     build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o \
-    build/sdf_runtime.o build/sdf_chunked.o build/sdf_mesh_out.o build/sdf_comm.o build/sdf_measure.o build/sdf_components.o build/sdf_simplify.o build/sdf_prims.o
+    build/sdf_runtime.o build/sdf_chunked.o build/sdf_mesh_out.o build/sdf_comm.o build/sdf_measure.o build/sdf_components.o build/sdf_simplify.o build/sdf_mend.o build/sdf_prims.o

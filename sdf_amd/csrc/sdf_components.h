@@ -25,6 +25,9 @@ int components_label(hipStream_t st, const long long *d_cells, const double *d_p
 // alone when nothing is kept); *n_kept: how many
 int components_select(hipStream_t st, const double *d_soup, long long n_tris, const int *d_triangle_shell, const unsigned char *h_keep,
                       long long n_shells, DevBuf *out, long long *n_kept, double *kernel_ms);
+// the copy of every compaction of a soup (a selection's, a mended mesh's): the nine doubles of every triangle of d_soup (n_tris x 9
+// float64) whose flag is set go to d_out + 9 * d_pos[triangle], one lane per double of the source; returns the launch's error
+hipError_t select_copy(hipStream_t st, const double *d_soup, const int *d_flags, const int *d_pos, long long n_tris, void *d_out);
 // box keys -> float64 on the host (h_bounds: n_shells x 2 x 3)
 void shell_bounds(const unsigned long long *h_keys, long long n_shells, double *h_bounds);
 }

@@ -230,6 +230,10 @@ __global__ __launch_bounds__(256) void k_select_copy(const double *__restrict__ 
     if (flags[t]) out[9ll * pos[t] + (i - 9 * t)] = soup[i];
 }
 
+hipError_t select_copy(hipStream_t st, const double *d_soup, const int *d_flags, const int *d_pos, long long n_tris, void *d_out) {
+    return launch_rows(k_select_copy, 9 * n_tris, st, d_soup, d_flags, d_pos, 9 * n_tris, d_out);
+}
+
 size_t shell_block_bytes(long long nv, long long nt, long long k) {
     return align256((size_t)nv * 4) + align256((size_t)nt * 4) + 2 * align256((size_t)k * 8) + align256((size_t)k * 48);
 }
@@ -340,7 +344,7 @@ int components_select(hipStream_t st, const double *d_soup, long long n_tris, co
     if (number_flags(who, "flags", st, flags, pos, n_tris, tmp, tmp_bytes, &kept)) return 1;
     if (kept > 0) {
         if (out->ensure((size_t)kept * 72)) return 1;
-        HIPCHK_MSG(who, launch_rows(k_select_copy, 9 * n_tris, st, d_soup, flags, pos, 9 * n_tris, out->p));
+        HIPCHK_MSG(who, select_copy(st, d_soup, flags, pos, n_tris, out->p));
     }
     HIPCHK_MSG(who, timer.stop(st));
     HIPCHK_MSG(who, stream_wait(st));

@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals at the welded vertices,
-// binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -11,6 +11,7 @@
 #include "sdf_components.h"
 #include "sdf_expand_host.h"   // (+ <chrono>, <cstring>, <mutex>, <thread>)
 #include "sdf_measure.h"
+#include "sdf_mend.h"
 #include "sdf_normals.h"
 #include "sdf_plain.h"
 #include "sdf_simplify.h"
@@ -494,6 +495,39 @@ int sdf_mesh_simplify(sdf_mesh *m, const double *origin3, const double *cell3, d
 double sdf_mesh_simplify_last_kernel_ms(double *parts4) {
     for (int k = 0; parts4 && k < 4; k++) parts4[k] = g_simplify_kernel_ms[k];
     return g_simplify_kernel_ms[0] + g_simplify_kernel_ms[1] + g_simplify_kernel_ms[2] + g_simplify_kernel_ms[3];
+}
+
+// ---- the mesh mended: duplicate triangles dropped, oppositely wound pairs cancelled, the survivors as a mesh of its own ----
+static thread_local double g_mend_kernel_ms[3] = {0.0, 0.0, 0.0};
+
+int sdf_mesh_mend(sdf_mesh *m, sdf_mesh **out, sdf_mend_stats *stats) {
+    if (!m || !out || !stats) { fail("sdf_mesh_mend: NULL argument"); return 2; }
+    MESH_READY(m);
+    const long long nt = (long long)m->st.n_triangles;
+    if (3 * nt >= (1ll << 31)) { fail("sdf_mesh_mend: 2^31 or more corners or vertices"); return 2; }      // (a weld has no more vertices than corners)
+    *stats = sdf_mend_stats();
+    DevBuf soup;                                                       // the survivors' own soup: the new mesh's `out`
+    if (nt > 0) {                                                      // (no triangles: a mesh of 0 triangles, no launch)
+        int64_t nu = 0;
+        if (sdf_mesh_weld(m, &nu)) return 1;                           // (it also makes the float64 soup of a records mesh)
+        HIPCHK(set_device(m->ctx->device));
+        if (mend_device(m->ctx->stream, (const double *)mesh_soup(m), m->weld_inv.as<long long>(), m->weld_n, nt, &soup, stats, g_mend_kernel_ms)) {
+            soup.release();
+            *stats = sdf_mend_stats();
+            return 1;
+        }
+    }
+    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
+    s->ctx = m->ctx;
+    s->out = soup;
+    s->st.n_triangles = stats->triangles_out;
+    *out = s;
+    return 0;
+}
+
+double sdf_mesh_mend_last_kernel_ms(double *parts3) {
+    for (int k = 0; parts3 && k < 3; k++) parts3[k] = g_mend_kernel_ms[k];
+    return g_mend_kernel_ms[0] + g_mend_kernel_ms[1] + g_mend_kernel_ms[2];
 }
 
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {

@@ -1,5 +1,5 @@
 // sdf_prims.h -- numbering flagged items, the step every compaction of the mesh readers shares (sdf_prims.hip; the roots and the kept
-// triangles of sdf_components.hip, the clusters and the live triangles of sdf_simplify.hip).  The library's int scan (hipCUB) is
+// triangles of sdf_components.hip, the clusters and the live triangles of sdf_simplify.hip, the survivors of sdf_mend.hip).  The library's int scan (hipCUB) is
 // instantiated there, once.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,4 +15,6 @@ hipError_t scan_tmp_bytes(hipStream_t st, long long n, size_t *bytes);
 // for a count outside 0 .. n
 int number_flags(const char *who, const char *what, hipStream_t st, int *flags, int *pos, long long n, void *tmp, size_t tmp_bytes,
                  long long *count);
+// the bits that hold 0 .. n - 1: where a library radix sort over such keys may stop
+static inline int bits_for(long long n) { int b = 1; while (b < 63 && (1ll << b) < n) b += 1; return b; }
 }

@@ -258,8 +258,6 @@ __global__ __launch_bounds__(256) void k_cluster_emit(const long long *__restric
     out[9ll * pos[t] + r] = verts[3ll * vertex_cluster[cells[3 * t + corner]] + (r - 3 * corner)];
 }
 
-static int bits_for(long long n) { int b = 1; while (b < 63 && (1ll << b) < n) b += 1; return b; }      // the bits that hold 0 .. n - 1
-
 int simplify_device(hipStream_t st, const double *d_points, const long long *d_cells, long long n_vertices, long long n_tris,
                     const double *origin, const double *cell, double reg, DevBuf *out, sdf_simplify_stats *stats, double kernel_ms[4]) {
     static const char who[] = "sdf_mesh_simplify: ";

@@ -67,6 +67,14 @@ class SdfSimplifyStats(ctypes.Structure):
     _fields_ = [(k, _c_i64) for k in SIMPLIFY_FIELDS] + [('kernel_ms', ctypes.c_double)]
 
 
+MEND_FIELDS = ('triangles_in', 'triangles_out', 'collapsed', 'duplicates', 'cancelled', 'faces')
+
+
+class SdfMendStats(ctypes.Structure):
+    """mirror of `sdf_mend_stats` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in MEND_FIELDS] + [('kernel_ms', ctypes.c_double)]
+
+
 class SdfStats(ctypes.Structure):
     """mirror of `sdf_stats` in include/sdf_hip.h"""
     _fields_ = [
@@ -181,6 +189,8 @@ ABI = {
     'sdf_mesh_components_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_simplify': (ctypes.c_int, [_vp, _f64p, _f64p, ctypes.c_double, ctypes.POINTER(_vp), ctypes.POINTER(SdfSimplifyStats)]),
     'sdf_mesh_simplify_last_kernel_ms': (ctypes.c_double, [_f64p]),
+    'sdf_mesh_mend': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(SdfMendStats)]),
+    'sdf_mesh_mend_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
@@ -564,7 +574,7 @@ class Mesh:
         tests/simplify_ref.py and reproduced bit for bit).  The welded vertices are clustered on the uniform grid (origin (3,), cell
         (3,) > 0), every cluster gets one representative placed by its quadric (regularised by reg towards the mean of its vertices,
         kept inside its cell), and the triangles whose three clusters differ survive, in order and winding.  Duplicates and
-        oppositely wound pairs are not removed (`edge_census` reports them).  The result owns its soup and serves every reader;
+        oppositely wound pairs are not removed unless the result is mended (`mend`; `edge_census` reports them).  The result owns its soup and serves every reader;
         its `simplify_stats` is a dict of clusters, triangles_in, triangles_out, collapsed, mean_fallback, flat and kernel_ms.
         This mesh stays valid.  ValueError, before any device work, for a cell that is not positive and finite, an origin that
         is not finite or a negative reg; SdfHipError for a vertex that is not finite or a cell too small for the key."""
@@ -578,6 +588,24 @@ class Mesh:
         m = Mesh(eng, h)
         m.emitted = False
         m.simplify_stats = dict({k: int(getattr(st, k)) for k in SIMPLIFY_FIELDS}, kernel_ms=float(st.kernel_ms))
+        return m
+
+    def mend(self):
+        """a new Mesh: this one mended on the device (sdf_mesh_mend, csrc/sdf_mend.hip; defined by
+        tests/mend_ref.py and reproduced exactly).  Of the welded cells, those with two equal indices are dropped; of the cells of
+        one face (the same three vertices), as many on either winding cancel, and otherwise the first in soup order of the majority
+        winding survives alone.  Survivors keep their order, their winding and the bits of their nine doubles.  Nothing is
+        re-oriented, and a wall that collapsed only in part keeps a non-manifold rim (`edge_census` reports it).  The result owns
+        its soup and serves every reader; its `mend_stats` is a dict of triangles_in, triangles_out, collapsed, duplicates,
+        cancelled, faces and kernel_ms.  This mesh stays valid.  ValueError for a mesh that has been closed (its handle is gone)."""
+        eng = self.engine
+        if not self._fin.alive:
+            raise ValueError('mend: this mesh has been closed')
+        h, st = _vp(), SdfMendStats()
+        _check(eng.lib, eng.lib.sdf_mesh_mend(self.handle, ctypes.byref(h), ctypes.byref(st)))
+        m = Mesh(eng, h)
+        m.emitted = False
+        m.mend_stats = dict({k: int(getattr(st, k)) for k in MEND_FIELDS}, kernel_ms=float(st.kernel_ms))
         return m
 
     def stl_records(self):

@@ -123,6 +123,19 @@ class Mesh:
             finally:
                 small.close()
 
+    def mend(self):
+        """this mesh mended on the device (sdf_amd/mend.py): a new Mesh of the welded result, without
+        duplicate triangles and without the oppositely wound pairs that `simplify` leaves where a wall is thinner than a cluster"""
+        from . import core
+        pts = np.asarray(self.points, dtype=np.float64)
+        with core.adopted(pts[np.asarray(self.triangles)]) as mesh:
+            mended = mesh.mend()
+            try:
+                points, cells = mended.weld()
+                return Mesh(np.array(points), np.array(cells))
+            finally:
+                mended.close()
+
     @property
     def bounding_box(self):
         lo, hi = self.points.min(axis=0), self.points.max(axis=0)

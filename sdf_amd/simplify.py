@@ -4,7 +4,8 @@ and small features, and almost nobody wants that many triangles in the file.  `s
 (Rossignac-Borrel), every cluster gets one representative placed by its quadric error function (Lindstrom), and the triangles whose
 three clusters differ survive (`engine.Mesh.simplify`, sdf_mesh_simplify, csrc/sdf_simplify.hip).  About k^2 times fewer triangles
 reach the link and the file.  Duplicate triangles and oppositely wound pairs, where two sheets of the surface fall into the same
-clusters, are not removed: `measure` reports them.  tests/simplify_ref.py is the definition."""
+clusters, are not removed unless `mend=True` follows (`sdf_amd/mend.py`): `measure` reports them.  tests/simplify_ref.py is the
+definition."""
 import numbers
 
 import numpy as np
