@@ -4,17 +4,9 @@ import numpy as np
 import pytest
 
 import level_set_ref as ref
+import level_set_truth as truth
+from level_set_truth import CUBE_P, CUBE_T, box_mesh, torus_mesh                # noqa: F401 (other test modules take them from here)
 from sdf_amd import mesh, stl
-
-# the 12 triangles of the unit cube [0, 1]^3, outward
-CUBE_P = np.array([[x, y, z] for x in (0.0, 1.0) for y in (0.0, 1.0) for z in (0.0, 1.0)])
-CUBE_T = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1],
-                   [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]])
-
-
-def box_mesh(lo, hi):
-    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
-    return lo + CUBE_P * (hi - lo), CUBE_T.copy()
 
 
 def box_distance(P, lo, hi):
@@ -22,16 +14,6 @@ def box_distance(P, lo, hi):
     c, h = (np.asarray(lo) + np.asarray(hi)) / 2, (np.asarray(hi) - np.asarray(lo)) / 2
     q = np.abs(P - c) - h
     return np.linalg.norm(np.maximum(q, 0), axis=1) + np.minimum(q.max(axis=1), 0)
-
-
-def torus_mesh(R=0.6, r=0.25, nu=32, nv=16):
-    u, v = np.meshgrid(np.arange(nu) * 2 * np.pi / nu, np.arange(nv) * 2 * np.pi / nv, indexing='ij')
-    P = np.stack([(R + r * np.cos(v)) * np.cos(u), (R + r * np.cos(v)) * np.sin(u), r * np.sin(v)], axis=-1).reshape(-1, 3)
-    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing='ij')
-    a, b = i * nv + j, ((i + 1) % nu) * nv + j
-    c, d = ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
-    T = np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)])
-    return P, T
 
 
 def voxel_points(ijk0, shape, vs):
@@ -125,6 +107,44 @@ def test_voxel_values_agree_with_the_dense_restatement():
     idx = rng.integers(0, A.shape, size=(40, 3))
     got = ref.voxel_values(P, T, vs, 0.2, ijk0 + idx)
     assert np.array_equal(got.view(np.uint32), A[tuple(idx.T)].view(np.uint32))
+
+
+@pytest.mark.parametrize('name', truth.NAMES)
+def test_restatement_holds_to_true_distance_and_winding_number(name):
+    """The restatement against tests/level_set_truth.py, which shares none of its derivation: on every catalogue case the
+    magnitude within one float32 ulp of the background of the true clamped distance, the sign that of the winding number,
+    the distance to 1e-12 on the surface, and the returned box the index box of float32(want) < background (`truth.hold`).
+
+    The open prefixes ('open1' ... 'open5': the first triangles of the octahedron) are held in magnitude and box only.  An
+    open mesh has no inside; the sign it gets is the parity of the crossings below the voxel, which is this library's
+    definition and stays so."""
+    c = truth.get_case(name)
+    ijk0, A, bg, work = ref.level_set(c.points, c.triangles, c.voxel_size, c.half_width)
+    assert bg == truth.case_truth(name).bg
+    f = truth.hold_case(name, ijk0, A, work)
+    print('%s: grid %s, work grid %s, on the surface %d, largest | |v| - want | %.3f ulp of the background'
+          % (name, f['shape'], f['work'], f['on_surface'], f['max_ulp']))
+
+
+def test_truth_distance_and_winding_on_known_points():
+    """the truth itself where the answer is known in closed form: the unit right triangle in the plane z = 0 (face, the three
+    sides, the three corners, a point above), a triangle shrunk to a segment and to a point, and the winding number of the
+    unit cube (1 inside, 0 outside, 2 for the cube listed twice, -1 turned inside out)"""
+    V = np.array([[[0.0, 0, 0], [1, 0, 0], [0, 1, 0]]])
+    Q = np.array([[0.25, 0.25, 0.5], [0.5, -2.0, 0.0], [-3.0, 0.5, 4.0], [1.0, 1.0, 1.0], [-1.0, -2.0, 2.0], [3.0, -1.0, 0.0], [-1.0, 3.0, 0.0],
+                  [0.25, 0.25, 0.0], [0.5, 0.5, 0.0]])
+    want = [0.25, 4.0, 25.0, 1.5, 9.0, 5.0, 5.0, 0.0, 0.0]
+    for turn in range(3):                                 # whichever corner is listed first
+        assert np.allclose(truth.true_d2(Q, np.roll(V, turn, axis=1)).astype(np.float64), want, rtol=0, atol=1e-15)
+    S = np.array([[[0.0, 0, 0], [2, 0, 0], [1, 0, 0]], [[5.0, 5, 5]] * 3])
+    assert np.allclose(truth.true_d2(np.array([[3.0, 4.0, 0.0], [1.5, 0.0, 2.0]]), S[:1]).astype(np.float64), [17.0, 4.0], rtol=0, atol=1e-15)
+    assert np.allclose(truth.true_d2(np.array([[5.0, 5.0, 7.0]]), S[1:]).astype(np.float64), [4.0], rtol=0, atol=1e-15)
+    assert np.all(np.isinf(truth.true_d2(Q, V + 100.0, reach=1.0)))
+    C = CUBE_P[CUBE_T]
+    Q = np.array([[0.5, 0.5, 0.5], [0.1, 0.9, 0.3], [1.5, 0.5, 0.5], [-0.2, -0.2, -0.2], [0.5, 0.5, 7.0]])
+    assert np.allclose(truth.winding(Q, C), [1, 1, 0, 0, 0], rtol=0, atol=1e-12)
+    assert np.allclose(truth.winding(Q, np.concatenate([C, C])), [2, 2, 0, 0, 0], rtol=0, atol=1e-12)
+    assert np.allclose(truth.winding(Q, C[:, ::-1]), [-1, -1, 0, 0, 0], rtol=0, atol=1e-12)
 
 
 def test_from_stl_round_trip_and_truncated_file(tmp_path):
