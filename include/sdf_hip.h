@@ -367,6 +367,28 @@ int sdf_mesh_vertex_normals(sdf_mesh *mesh, sdf_tape *tape, double eps, double *
 /* the kernel of this thread's last sdf_mesh_vertex_normals that computed (not one served from the cache) alone, milliseconds by
  * HIP events (tools/export_time.py) */
 double sdf_mesh_normals_last_kernel_ms(void);
+/* The wall thickness at the welded vertices (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section
+ * 4l, defined by tests/thickness_ref.py and reproduced bit for bit): from every unique vertex p of sdf_mesh_weld a ray is
+ * sphere-traced INWARD through the solid until the field f turns positive again.  params6 = normal_eps, start, min_step, t_far,
+ * step_scale, 0 (reserved).  The direction is d = -(g / len) with g, len of sdf_mesh_vertex_normals at step normal_eps; a vertex
+ * whose len is 0 or NaN is FLAT (3): thickness NaN, 0 steps.  The march starts at t = start with the bracket lo = 0, hi = start
+ * and evaluates v = f(p + t d) at most max_steps times: a NaN ends it as NAN (4, thickness NaN); v >= 0 ends it with hi = t -- on
+ * the first evaluation as THIN (2: nothing solid lies `start` inside the vertex; the thickness reported is `start`, an upper
+ * bound), later as THICK (1); otherwise lo = t and t advances by max((-v) * step_scale, min_step), and a t beyond t_far ends it
+ * as OPEN (0, thickness +inf), as does running out of steps.  The bracket of a THICK vertex is bisected `refine` times (the
+ * midpoint goes to lo where f < 0 there, else to hi) and its thickness is hi.  min_step lets a ray leave the surface it starts on
+ * and pass along a nearby face; the price is that an outside gap narrower than min_step can be stepped over.  Outputs, one per
+ * welded vertex: h_thickness float64, h_status uint8, h_steps int32 (evaluations of the march).  Float64, the interpreter of
+ * sdf_eval_points.  It serves every mesh of the context that has been welded: generated meshes, adopted soups, selections,
+ * simplified and mended meshes.  Synchronous, on the context's stream; one device allocation (13 bytes per vertex), freed before
+ * it returns; nothing is kept with the mesh.  A mesh of 0 vertices returns 0 without a launch.  Refused on the host before
+ * anything is allocated or launched, with return value 2: a NULL argument, a mesh that is not welded, a tape of another context, a
+ * tape with user closures (sdf_tape_extern_count > 0), a non-finite parameter, normal_eps, start or min_step not above 0,
+ * step_scale outside (0, 1], t_far < start, max_steps < 1, refine < 0.  Other failures return 1. */
+int sdf_mesh_vertex_thickness(sdf_mesh *mesh, sdf_tape *tape, const double *params6, int max_steps, int refine,
+                              double *h_thickness, uint8_t *h_status, int32_t *h_steps);
+/* the kernel of this thread's last successful sdf_mesh_vertex_thickness alone, milliseconds by HIP events (tools/thickness_time.py) */
+double sdf_mesh_thickness_last_kernel_ms(void);
 /* The body of a binary little-endian PLY file of the welded mesh: h_vertices receives n_unique records of float32 x, y, z (12
  * bytes) or, with_normals = 1, float32 x, y, z, nx, ny, nz (24 bytes; needs a successful sdf_mesh_vertex_normals first);
  * h_faces receives T records of 13 bytes: uint8 3 and three little-endian int32 vertex indices.  Refused with return value 2: a

@@ -40,4 +40,5 @@ from .stl import (
 
 from .render import render   # (not in the reference: sphere-traced previews)
 from .measure import measure   # (not in the reference: volume, area, inertia and the edge census on the device, section 4g)
+from .thickness import thickness, Thickness   # (not in the reference: the wall thickness at the vertices of a mesh, probed on the device, section 4l)
 from .shells import shells, measure_shells, Shells   # (not in the reference: the connected shells of a mesh, kept or dropped on the device, section 4h)

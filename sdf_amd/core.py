@@ -375,7 +375,7 @@ generate_mesh.last_simplify = None
 generate_mesh.last_mend = None
 
 
-def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, **kwargs):
+def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
@@ -384,23 +384,43 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     is simplified on the device in clusters of k^3 grid cells and the file holds the simplified mesh: about k^2 times fewer triangles
     cross the link and reach the disk (`sdf_amd/simplify.py`).  mend: True -- after keep and simplify, duplicate
     triangles are dropped and oppositely wound pairs cancel, and the file holds the mended mesh (`sdf_amd/mend.py`, DESIGN.md
-    section 4k)."""
+    section 4k).  thickness: True, or a dict of the probe's arguments (start, min_step, t_far, step_scale, max_steps, refine) -- the
+    vertices of a .ply file carry the wall thickness of the final mesh as `property float quality` (`sdf_amd/thickness.py`, DESIGN.md
+    section 4l; the direction's step is normal_eps); the native writer only, any other extension or writer raises ValueError before
+    anything is meshed, and the file's body is packed on the host: it is not the fast path.  May be combined with normals=True."""
     from . import meshfile
     path = os.fspath(path)
-    how = meshfile.choose_writer(path, writer, normals)
+    how = meshfile.choose_writer(path, writer, normals, bool(thickness))
     ply = path.lower().endswith('.ply')
     if simplify is not None:      # (simplify=None is the call without the argument)
         kwargs['simplify'] = simplify
     if mend is not False:         # (mend=False is the call without the argument)
         kwargs['mend'] = mend
+    if thickness:                 # (refused before anything is meshed, like the extension above)
+        from .thickness import check_params, default_params, read_thickness
+        probe = dict(thickness) if isinstance(thickness, dict) else {}
+        unknown = set(probe) - {'start', 'min_step', 't_far', 'step_scale', 'max_steps', 'refine'}
+        if unknown:
+            raise ValueError('thickness: unknown probe arguments %s' % sorted(unknown))
+        check_params(1.0 if normal_eps is None else normal_eps, probe.get('start', 1.0), probe.get('min_step', 1.0),
+                     probe.get('t_far', np.finfo(np.float64).max), probe.get('step_scale', 1.0), probe.get('max_steps', 256), probe.get('refine', 16))
     with meshed(*args, keep=keep, **kwargs) as m:
-        if how == 'native':
+        if thickness:
+            got = read_export(m, bool(normals), normal_eps)
+            steps3 = grid_axes(m.bounds, args[1] if len(args) > 1 else kwargs.get('step'), args[3] if len(args) > 3 else kwargs.get('samples', SAMPLES))[3]
+            params = dict(default_params(m.bounds, steps3, probe.get('start'), probe.get('min_step'), probe.get('t_far'), normal_eps),
+                          step_scale=float(probe.get('step_scale', 1.0)), max_steps=int(probe.get('max_steps', 256)), refine=int(probe.get('refine', 16)))
+            quality = read_thickness(m, params, with_mesh=False)[2]
+        elif how == 'native':
             got = read_export(m, bool(normals), normal_eps, ply)
         elif how == 'stl':
             records = read_stl_records(m)
         else:
             points, cells = read_weld(m)
-    if how == 'native' and ply:
+    if thickness:
+        vb, fb = meshfile.ply_records(got['points'], got['cells'], got['normals'], quality)
+        meshfile.write_ply(path, vb, fb, got['n_vertices'], got['n_faces'], bool(normals), quality=True)
+    elif how == 'native' and ply:
         meshfile.write_ply(path, got['ply'][0], got['ply'][1], got['n_vertices'], got['n_faces'], bool(normals))
     elif how == 'native':
         meshfile.write_obj(path, got['points'], got['cells'], got['normals'])

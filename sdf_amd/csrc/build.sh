@@ -26,12 +26,14 @@ $HIPCC $FLAGS -c -o build/sdf_bounds.o sdf_bounds.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -c -o build/sdf_render.o sdf_render.hip "$@" & pids="$pids $!"
 # (the vertex normals of the indexed export k_vertex_normals: a tape interpreter, six wave-uniform passes, see sdf_normals.hip)
 $HIPCC $FLAGS -c -o build/sdf_normals.o sdf_normals.hip "$@" & pids="$pids $!"
+# (the wall-thickness probe k_vertex_thickness: a tape interpreter whose loops are all wave-uniform, see sdf_thickness.hip)
+$HIPCC $FLAGS -c -o build/sdf_thickness.o sdf_thickness.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=0 -DMESH_NAME=sdf_launch_mesh_f64 -c -o build/mesh_f64.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 $HIPCC $FLAGS -DMESH_T=double -DMESH_FULL=1 -DMESH_NAME=sdf_launch_mesh_f64_full -c -o build/mesh_f64_full.o sdf_mesh_inst.hip "$@" & pids="$pids $!"
 # (every kernel that is not a tape interpreter: built WITHOUT the structurizer option, see sdf_plain.hip)
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/sdf_plain.o sdf_plain.hip "$@" & pids="$pids $!"
 # (host code only -- the runtime every unit shares, the meshing paths through device memory, the readers of a finished mesh, the
-# multi-GPU step: they launch through the launchers of sdf_plain / sdf_normals / sdf_weld and, for the one interpreter kernel
+# multi-GPU step: they launch through the launchers of sdf_plain / sdf_normals / sdf_thickness / sdf_weld and, for the one interpreter kernel
 # among them, k_eval_tiles, through enqueue_eval_tiles of sdf_hip.hip, so they take the plain flags)
 for u in sdf_runtime sdf_chunked sdf_mesh_out sdf_comm; do
     $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-result -c -o build/$u.o $u.hip "$@" & pids="$pids $!"
@@ -54,5 +56,5 @@ $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build
 $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -c -o build/sdf_prims.o sdf_prims.hip "$@" & pids="$pids $!"
 for p in $pids; do wait $p; done
 exec $HIPCC --offload-arch=gfx950 -fPIC -shared -o libsdf_hip.so build/sdf_hip.o build/mesh_f64.o build/mesh_f64_full.o \
-    build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o \
+    build/sdf_bounds.o build/sdf_render.o build/sdf_normals.o build/sdf_thickness.o build/sdf_weld.o build/sdf_plain.o build/sdf_level_set.o build/sdf_edt.o \
     build/sdf_runtime.o build/sdf_chunked.o build/sdf_mesh_out.o build/sdf_comm.o build/sdf_measure.o build/sdf_components.o build/sdf_simplify.o build/sdf_mend.o build/sdf_prims.o

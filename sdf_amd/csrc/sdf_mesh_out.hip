@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
-// (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals at the welded vertices,
-// binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
+// welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -15,6 +15,7 @@
 #include "sdf_normals.h"
 #include "sdf_plain.h"
 #include "sdf_simplify.h"
+#include "sdf_thickness.h"
 
 using namespace sdfk;
 
@@ -346,6 +347,52 @@ int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_norm
 }
 
 double sdf_mesh_normals_last_kernel_ms(void) { return g_normals_kernel_ms; }
+
+// ---- the wall thickness at the welded vertices: inward rays through the solid ----
+static thread_local double g_thickness_kernel_ms = 0.0;
+
+int sdf_mesh_vertex_thickness(sdf_mesh *m, sdf_tape *t, const double *params6, int max_steps, int refine, double *h_thickness,
+                              uint8_t *h_status, int32_t *h_steps) {
+    auto refuse = [](const std::string &why) { fail("sdf_mesh_vertex_thickness: " + why); return 2; };
+    if (!m || !t || !params6 || !h_thickness || !h_status || !h_steps) return refuse("NULL argument");
+    if (m->weld_n < 0) return refuse("call sdf_mesh_weld first");
+    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
+    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip");
+    for (int i = 0; i < 6; i++) if (!std::isfinite(params6[i])) return refuse("the parameters are not finite");
+    ThicknessArgs a;
+    a.normal_eps = params6[0]; a.start = params6[1]; a.min_step = params6[2]; a.t_far = params6[3]; a.step_scale = params6[4];
+    a.max_steps = max_steps; a.refine = refine;
+    if (!(a.normal_eps > 0.0)) return refuse("normal_eps must be positive");
+    if (!(a.start > 0.0)) return refuse("start must be positive");
+    if (!(a.min_step > 0.0)) return refuse("min_step must be positive");
+    if (!(a.step_scale > 0.0 && a.step_scale <= 1.0)) return refuse("step_scale must lie in (0, 1]");
+    if (a.t_far < a.start) return refuse("t_far lies before start");
+    if (max_steps < 1) return refuse("max_steps must be at least 1");
+    if (refine < 0) return refuse("refine must not be negative");
+    const long long nu = m->weld_n;
+    if (nu == 0) return 0;
+    sdf_ctx *c = m->ctx;
+    HIPCHK(set_device(c->device));
+    hipStream_t st = c->stream;
+    double *thick;
+    int32_t *steps;
+    uint8_t *status;
+    Scratch scratch(st);
+    scratch.part(&thick, (size_t)nu); scratch.part(&steps, (size_t)nu); scratch.part(&status, (size_t)nu);
+    EventTimer timer;
+    HIPCHK_MSG("sdf_mesh_vertex_thickness: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
+    HIPCHK_FN(timer.start(st));
+    HIPCHK_FN((hipError_t)launch_vertex_thickness(st, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, a, thick, status, steps));
+    HIPCHK_FN(timer.stop(st));
+    HIPCHK_FN(hipMemcpyAsync(h_thickness, thick, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_status, status, (size_t)nu, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_steps, steps, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(stream_wait(st));
+    HIPCHK_FN(timer.ms(&g_thickness_kernel_ms));
+    return 0;
+}
+
+double sdf_mesh_thickness_last_kernel_ms(void) { return g_thickness_kernel_ms; }
 
 // ---- the mesh measured on the device: moments of the soup, edge census of the welded cells ----
 static thread_local double g_measure_kernel_ms = 0.0;

@@ -1,0 +1,115 @@
+// sdf_thickness.hip -- the wall thickness at the welded vertices of a mesh (sdf_mesh_vertex_thickness): from every
+// vertex a ray is sphere-traced INWARD, along the negated field normal, through the solid until the field turns positive again; the
+// bracket of that crossing is bisected and the ray's length is the wall's ray thickness there.  tests/thickness_ref.py is the
+// definition; this kernel reproduces it bit for bit over the interpreter that sdf_eval_points runs: float64, one rounding per written
+// operation (-ffp-contract=off), divisions where the definition divides, dot = (x*x + y*y) + z*z, a point on a ray is p + t * d.
+//
+// One welded vertex per lane, like k_vertex_normals.  The interpreter is inlined ONCE: the six evaluations of the normal, the march
+// and the bisection are phases of one loop whose phase and counter are wave-uniform -- k_render's structure (sdf_render.hip) in the
+// order NORMAL -> MARCH -> REFINE: the march ends when `__any(status == MARCH)` says so or after max_steps passes, REFINE is skipped
+// when no lane of the wave is THICK.  Lanes never branch around the interpreter -- this unit is built with the structurizer option
+// that is only safe for wave-uniform control flow (build.sh) -- they take their state changes by selects: a lane that is done keeps
+// evaluating at its frozen parameter and discards the value, a FLAT lane (direction 0) evaluates at its vertex.  A lane beyond the
+// last vertex evaluates at the last vertex and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
+#include <cmath>
+
+#include "sdf_interp.h"
+#include "sdf_thickness.h"
+
+using namespace sdfk;
+
+enum { W_OPEN = 0, W_THICK = 1, W_THIN = 2, W_FLAT = 3, W_NAN = 4, W_MARCH = 5 };      // (0 .. 4: the status codes of the ABI)
+enum { PH_NORMAL = 0, PH_MARCH = 1, PH_REFINE = 2 };
+
+template <typename T, bool FULL>
+__global__ __launch_bounds__(256) void k_vertex_thickness(const uint32_t *__restrict__ code, const T *__restrict__ consts,
+                                                          const double *__restrict__ pts, long long n, const ThicknessArgs a,
+                                                          double *__restrict__ thickness, uint8_t *__restrict__ status_out,
+                                                          int32_t *__restrict__ steps_out) {
+    const long long wave0 = (long long)blockIdx.x * 256 + (long long)(threadIdx.x & ~63u);
+    if (wave0 >= n) return;                                            // (wave-uniform)
+    const long long i = wave0 + (long long)(threadIdx.x & 63u);
+    const bool live = i < n;
+    const long long j = live ? i : n - 1;
+    const double px = pts[3 * j], py = pts[3 * j + 1], pz = pts[3 * j + 2];
+    double gp = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    double dx = 0.0, dy = 0.0, dz = 0.0;
+    double t = a.start, lo = 0.0, hi = a.start;
+    int status = W_MARCH, steps = 0;
+    int phase = PH_NORMAL, k = 0;                                      // (wave-uniform, like every condition on them below)
+    for (;;) {
+        // where this pass evaluates: the vertex moved by +-eps along an axis, the march's t, the bisection's midpoint
+        const double mid = 0.5 * (lo + hi);
+        const bool fix = status == W_THICK;
+        const double s = (phase == PH_REFINE && fix) ? mid : t;
+        double x = px + s * dx, y = py + s * dy, z = pz + s * dz;
+        if (phase == PH_NORMAL) {                                      // pass k: axis k / 2, + eps then - eps
+            const double h = (k & 1) ? -a.normal_eps : a.normal_eps;
+            x = px; y = py; z = pz;
+            if ((k >> 1) == 0) x = x + h;
+            else if ((k >> 1) == 1) y = y + h;
+            else z = z + h;
+        }
+        const double v = (double)run_tape1<T, FULL>(code, consts, (T)x, (T)y, (T)z);
+        if (phase == PH_NORMAL) {
+            const double g = gp - v;
+            if (k == 1) g0 = g;
+            else if (k == 3) g1 = g;
+            else if (k == 5) g2 = g;
+            gp = v;
+            k++;
+            if (k == 6) {
+                const double len = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
+                const bool flat = len == 0.0 || len != len;
+                dx = flat ? 0.0 : -(g0 / len);                         // inward for this library's winding
+                dy = flat ? 0.0 : -(g1 / len);
+                dz = flat ? 0.0 : -(g2 / len);
+                status = flat ? W_FLAT : W_MARCH;
+                if (!__any(status == W_MARCH)) break;                  // a wave of flat vertices: no ray to march
+                phase = PH_MARCH; k = 0;
+            }
+        } else if (phase == PH_MARCH) {
+            const bool m = status == W_MARCH;
+            const bool nan = v != v, out = !nan && v >= 0.0, in = !nan && !out;
+            const double adv = (-v) * a.step_scale;
+            const double t1 = t + (adv > a.min_step ? adv : a.min_step);
+            const bool far = t1 > a.t_far;
+            steps += m ? 1 : 0;
+            hi = (m && out) ? t : hi;
+            lo = (m && in) ? t : lo;
+            status = !m ? status : (nan ? W_NAN : (out ? (k == 0 ? W_THIN : W_THICK) : (far ? W_OPEN : W_MARCH)));
+            t = (m && in && !far) ? t1 : t;
+            k++;
+            if (!(__any(status == W_MARCH) && k < a.max_steps)) {
+                status = status == W_MARCH ? W_OPEN : status;          // ran out of steps
+                if (!(a.refine > 0 && __any(status == W_THICK))) break;
+                phase = PH_REFINE; k = 0;
+            }
+        } else {
+            const bool in = v < 0.0;
+            lo = (fix && in) ? mid : lo;
+            hi = (fix && !in) ? mid : hi;                              // (NaN included)
+            k++;
+            if (k == a.refine) break;
+        }
+    }
+    if (!live) return;
+    thickness[i] = (status == W_THICK || status == W_THIN) ? hi : (status == W_OPEN ? (double)INFINITY : (double)NAN);
+    status_out[i] = (uint8_t)status;
+    steps_out[i] = steps;
+}
+
+namespace sdfk {
+
+// enqueue only: the thickness of n >= 1 vertices (n x 3 float64 at d_pts) into d_thickness / d_status / d_steps.  Returns a
+// hipError_t value (0 = ok).
+int launch_vertex_thickness(hipStream_t st, const uint32_t *d_code, const double *d_consts, bool full, const double *d_pts, long long n,
+                            const ThicknessArgs &a, double *d_thickness, uint8_t *d_status, int32_t *d_steps) {
+    if (n < 1) return 0;
+    const unsigned grid = (unsigned)((n + 255) / 256);                 // (n < 2^31 vertices: the weld's limit)
+    if (full) hipLaunchKernelGGL((k_vertex_thickness<double, true>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, a, d_thickness, d_status, d_steps);
+    else hipLaunchKernelGGL((k_vertex_thickness<double, false>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, a, d_thickness, d_status, d_steps);
+    return (int)hipGetLastError();
+}
+
+}  // namespace sdfk

@@ -76,6 +76,10 @@ class SDF3(SDFBase):
         from .measure import measure
         return measure(self, *args, **kwargs)
 
+    def thickness(self, *args, **kwargs):
+        from .thickness import thickness
+        return thickness(self, *args, **kwargs)
+
     def shells(self, **kwargs):
         from .shells import shells
         return shells(self, **kwargs)

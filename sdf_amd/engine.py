@@ -178,6 +178,8 @@ ABI = {
     'sdf_mesh_weld_fetch': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(ctypes.c_int64)]),
     'sdf_mesh_vertex_normals': (ctypes.c_int, [_vp, _vp, ctypes.c_double, _f64p, ctypes.POINTER(ctypes.c_int64)]),
     'sdf_mesh_normals_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_vertex_thickness': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _u8p, ctypes.POINTER(ctypes.c_int32)]),
+    'sdf_mesh_thickness_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_emit_ply_host': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'sdf_mesh_moments': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(SdfMoments)]),
     'sdf_mesh_edge_census': (ctypes.c_int, [_vp, ctypes.POINTER(SdfEdgeCensus)]),
@@ -473,6 +475,30 @@ class Mesh:
         flat = ctypes.c_int64(0)
         _check(eng.lib, eng.lib.sdf_mesh_vertex_normals(self.handle, dt.handle, eps, _dp(out, _f64p), ctypes.byref(flat)))
         return out, int(flat.value)
+
+    def vertex_thickness(self, sdf_or_tape, normal_eps, start, min_step, t_far, step_scale=1.0, max_steps=256, refine=16):
+        """(thickness (U,) float64, status (U,) uint8, steps (U,) int32): the wall's ray thickness at the U welded vertices
+        (sdf_mesh_vertex_thickness, csrc/sdf_thickness.hip; defined by tests/thickness_ref.py and reproduced
+        bit for bit).  From every vertex a ray is sphere-traced inward, along the negated field normal (step normal_eps), from
+        t = start through the solid until the field is positive again, advancing by max(-value * step_scale, min_step), and the
+        crossing is bisected `refine` times.  status: 0 OPEN (beyond t_far or out of max_steps: +inf), 1 THICK, 2 THIN (outside
+        already at `start`: the thickness is `start`, an upper bound), 3 FLAT (no gradient: NaN), 4 NAN (the field was NaN on the
+        ray: NaN).  A model with user closures takes the same definition over `Engine.eval_points` on the host.  Raises ValueError,
+        before any device work, for the parameters the C entry refuses and for an engine in float32 precision."""
+        from .thickness import check_params, vertex_thickness      # (the package's attribute `thickness` is the function)
+        eng = self.engine
+        params = check_params(normal_eps, start, min_step, t_far, step_scale, max_steps, refine)
+        if eng.precision != PRECISION_F64:
+            raise ValueError('vertex_thickness marches in float64 only; this engine is set to float32 precision')
+        dt = eng.tape_for(sdf_or_tape)
+        if dt.tape.externs:
+            return vertex_thickness(lambda P: eng.eval_points(dt, P), self.weld()[0], *params)
+        nu = self._welded()
+        th, status, steps = np.empty(nu, np.float64), np.empty(nu, np.uint8), np.empty(nu, np.int32)
+        p6 = np.array(params[:5] + [0.0], np.float64)
+        _check(eng.lib, eng.lib.sdf_mesh_vertex_thickness(self.handle, dt.handle, _dp(p6, _f64p), params[5], params[6], _dp(th, _f64p),
+                                                          _dp(status, _u8p), _dp(steps, ctypes.POINTER(ctypes.c_int32))))
+        return th, status, steps
 
     def ply_records(self, normals=False):
         """(vertex_bytes, face_bytes) uint8: the body of a binary little-endian PLY file of the welded mesh, packed on the device

@@ -101,6 +101,19 @@ class Mesh:
         from .measure import measure_soup
         return measure_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], origin)
 
+    def thickness(self, f, step=None, start=None, min_step=None, t_far=None, max_steps=256, refine=16, normal_eps=None, step_scale=1.0):
+        """the walls of this mesh measured in the field `f` (sdf_amd/thickness.py): a `Thickness` over the
+        vertices of the soup welded on the device.  A file has no sampling grid, so `step` must be given (start = min_step = a
+        quarter of it), or start and min_step themselves; t_far defaults to the diagonal of this mesh's bounding box and normal_eps
+        to 1e-4 x half of it."""
+        from .thickness import default_params, thickness_of_soup
+        pts = np.asarray(self.points, dtype=np.float64)
+        if len(pts) == 0:
+            raise ValueError('thickness: the mesh has no vertices')
+        steps3 = None if step is None else tuple(np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)).tolist())
+        params = default_params((pts.min(axis=0), pts.max(axis=0)), steps3, start, min_step, t_far, normal_eps)
+        return thickness_of_soup(pts[np.asarray(self.triangles)], f, step_scale=step_scale, max_steps=max_steps, refine=refine, **params)
+
     def shells(self):
         """the connected shells of this mesh (sdf_amd/shells.py `Shells`), labelled on the device.  The soup is welded there again:
         `vertex_shell` is over THAT weld's vertices (lexicographic order), `triangle_shell` over this mesh's triangles"""

@@ -13,18 +13,22 @@ import numpy as np
 NATIVE_EXTENSIONS = ('.ply', '.obj')
 
 
-def ply_header(n_vertices, n_faces, with_normals):
-    """the header of a binary little-endian PLY file of n_vertices float32 vertices (with float32 normals) and n_faces triangles"""
+def ply_header(n_vertices, n_faces, with_normals, quality=None):
+    """the header of a binary little-endian PLY file of n_vertices float32 vertices (with float32 normals; with quality, a float32
+    scalar per vertex after them under MeshLab's name, `property float quality`) and n_faces triangles"""
     lines = ['ply', 'format binary_little_endian 1.0', 'comment sdf_amd', 'element vertex %d' % n_vertices,
              'property float x', 'property float y', 'property float z']
     if with_normals:
         lines += ['property float nx', 'property float ny', 'property float nz']
+    if quality is not None and quality is not False:
+        lines += ['property float quality']
     lines += ['element face %d' % n_faces, 'property list uchar int vertex_indices', 'end_header']
     return ('\n'.join(lines) + '\n').encode('ascii')
 
 
-def ply_records(points, cells, normals=None):
-    """(vertex_bytes, face_bytes) of a host mesh: what `engine.Mesh.ply_records` packs on the device"""
+def ply_records(points, cells, normals=None, quality=None):
+    """(vertex_bytes, face_bytes) of a host mesh: what `engine.Mesh.ply_records` packs on the device; quality: a scalar per vertex,
+    appended to each vertex record as a float32 (inf and nan as they are)"""
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     cells = np.asarray(cells).reshape(-1, 3)
     if len(points) >= 1 << 31:
@@ -32,6 +36,12 @@ def ply_records(points, cells, normals=None):
     cols = [points.astype('<f4')]
     if normals is not None:
         cols.append(np.asarray(normals, dtype=np.float64).reshape(-1, 3).astype('<f4'))
+    if quality is not None:
+        q = np.asarray(quality, dtype=np.float64).reshape(-1, 1)
+        if len(q) != len(points):
+            raise ValueError('%d quality values for %d vertices' % (len(q), len(points)))
+        with np.errstate(over='ignore'):
+            cols.append(q.astype('<f4'))
     vertex = np.ascontiguousarray(np.hstack(cols)).view(np.uint8).reshape(-1)
     face = np.empty(len(cells), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
     face['n'] = 3
@@ -39,15 +49,17 @@ def ply_records(points, cells, normals=None):
     return vertex, face.view(np.uint8).reshape(-1)
 
 
-def write_ply(path, vertex_bytes, face_bytes, n_vertices, n_faces, with_normals):
-    """header + the two record blocks, as they come from the device"""
+def write_ply(path, vertex_bytes, face_bytes, n_vertices, n_faces, with_normals, quality=None):
+    """header + the two record blocks, as they come from the device (quality: the vertex records end in a float32 scalar)"""
+    quality = quality is not None and quality is not False
     vertex_bytes = np.ascontiguousarray(vertex_bytes, dtype=np.uint8).reshape(-1)
     face_bytes = np.ascontiguousarray(face_bytes, dtype=np.uint8).reshape(-1)
-    if len(vertex_bytes) != n_vertices * (24 if with_normals else 12) or len(face_bytes) != n_faces * 13:
-        raise ValueError('%d vertex bytes and %d face bytes do not hold %d vertices%s and %d faces'
-                         % (len(vertex_bytes), len(face_bytes), n_vertices, ' with normals' if with_normals else '', n_faces))
+    if len(vertex_bytes) != n_vertices * ((24 if with_normals else 12) + (4 if quality else 0)) or len(face_bytes) != n_faces * 13:
+        raise ValueError('%d vertex bytes and %d face bytes do not hold %d vertices%s%s and %d faces'
+                         % (len(vertex_bytes), len(face_bytes), n_vertices, ' with normals' if with_normals else '',
+                            ' with quality' if quality else '', n_faces))
     with open(path, 'wb') as fp:
-        fp.write(ply_header(n_vertices, n_faces, with_normals))
+        fp.write(ply_header(n_vertices, n_faces, with_normals, quality or None))
         fp.write(memoryview(vertex_bytes))
         fp.write(memoryview(face_bytes))
 
@@ -103,14 +115,21 @@ def _has_meshio():
         return False
 
 
-def choose_writer(path, writer=None, normals=False):
+def choose_writer(path, writer=None, normals=False, thickness=False):
     """which writer `save` uses for `path`: 'stl', 'meshio' or 'native'.  writer=None: native when normals are asked for,
     else meshio where it imports (as before there was a native writer), else native for .ply / .obj.  Raises ValueError for
     what no writer serves (vertex normals in an STL file or through meshio, a native extension other than .ply / .obj, an
-    unknown writer) and ImportError where only meshio could serve and it is not installed."""
+    unknown writer) and ImportError where only meshio could serve and it is not installed.  thickness: the file is to carry the
+    wall thickness per vertex -- .ply and the native writer only, anything else raises ValueError."""
     ext = os.path.splitext(os.fspath(path))[1].lower()
     if writer not in (None, 'native', 'meshio'):
         raise ValueError("writer must be None, 'native' or 'meshio', got %r" % (writer,))
+    if thickness:
+        if ext != '.ply':
+            raise ValueError("the wall thickness is written as a .ply file's `quality` property, not into %r" % (ext,))
+        if writer == 'meshio':
+            raise ValueError("the meshio writer does not write the wall thickness: use writer='native'")
+        return 'native'
     if ext == '.stl':
         if normals:
             raise ValueError('STL has no vertex normals: save a .ply or an .obj with normals=True')
