@@ -18,7 +18,7 @@
 // dispatch, a few dependent float64 operations), and a wave that shares its SIMD with three others -- 1024 lanes on one compute unit
 // -- waits for them at every link of it: ~ 500 cycles per instruction whatever it computes.  Alone on its SIMD the same wave takes a
 // third of that, and a workgroup of one wave has nothing to synchronise with but the other sixty-three once per round.
-// A translation unit of its own: built in parallel with the others (build.sh), with the interpreters' structurizer option.
+// A translation unit of its own: built in parallel with the others (build.units), with the interpreters' structurizer option.
 #include "sdf_interp.h"
 #include "sdf_bounds.h"
 

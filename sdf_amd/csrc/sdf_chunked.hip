@@ -1,8 +1,8 @@
 // sdf_chunked.hip -- meshing a grid through device memory, a chunk of batches per submission: `generate` for batch_size > 32
 // (generate_big: the tape samples the tiles, k_eval_tiles) and for models with user closures at any batch size (sdf_generate_field:
 // a host callback samples them).  One driver, march_chunks, with a sampler per path; the arithmetic the GPU never sees is
-// sdf_chunk_plan.h.  Host code only: it launches through the launchers of sdf_plain.h and through enqueue_skip / enqueue_eval_tiles
-// of sdf_hip.hip, so it is built WITHOUT the interpreters' structurizer option (build.sh).
+// sdf_chunk_plan.h.  Host code only: it launches through the launchers of sdf_plain.h and through enqueue_skip (sdf_prepass.hip) /
+// enqueue_eval_tiles (sdf_eval.hip), so it is built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 

@@ -1,5 +1,5 @@
-// sdf_comm.hip -- the multi-GPU exchange step inside the library: it drives generate_impl and enqueue_skip (sdf_hip.hip, declared in
-// sdf_internal.h) and k_expand's launcher directly.  No kernels of its own.
+// sdf_comm.hip -- the multi-GPU exchange step inside the library: it drives generate_impl (sdf_generate.hip) and enqueue_skip (sdf_prepass.hip; both
+// declared in sdf_internal.h) and k_expand's launcher directly.  No kernels of its own.
 //
 // One process per GPU.  A rank meshes its contiguous share of the surviving-batch work list into a SLAB (header with
 // the counts | per-batch triangle prefix and transform | triangles as 16-byte records in batch-local coordinates, sdf_slab.h

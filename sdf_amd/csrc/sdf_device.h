@@ -508,7 +508,7 @@ struct TileTasks {
 // Writes the record of the batch -- u16 number of listed units (0xFFFF: not culled), the units (u16 each: u0 << 10 | u1 << 5 |
 // u2, ascending, padded with 0xFFFF to whole tasks), the sub-group states -- and returns the number of TASKS, or -1 when the tile is not culled
 // (degenerate tile, the interval state of the tape does not fit in LDS, or so many units that listing them saves nothing).
-// Listing more units than necessary is harmless, missing one is not.  This is the body of k_cull (sdf_hip.hip), a kernel
+// Listing more units than necessary is harmless, missing one is not.  This is the body of k_cull (sdf_prepass.hip), a kernel
 // of its own in front of k_mesh: inside k_mesh the interval pass would run on half the waves of a workgroup that holds a
 // whole CU, and its registers would compete with the interpreter's.
 // record / scratch: [0] u16 unit count | CULL_ULIST: units | CULL_SSTATE: 16^3 sub-group states (0 unknown, 1 positive,

@@ -1,6 +1,6 @@
 // sdf_internal.h -- what the handles of the C ABI (include/sdf_hip.h) point to: the context, a tape, a mesh, and the descriptor of a
-// generate call; plus the few functions of the generate pipeline (sdf_hip.hip), of its paths through device memory (sdf_chunked.hip)
-// and of the mesh readers (sdf_mesh_out.hip) that another translation unit calls.  With sdf_runtime.h, all a unit needs to define an extern "C" entry point that takes a handle.
+// generate call; plus the few functions of the generate pipeline (sdf_generate.hip), of the kernels it launches (sdf_prepass.hip,
+// sdf_eval.hip), of its paths through device memory (sdf_chunked.hip) and of the mesh readers (sdf_mesh_out.hip) that another translation unit calls.  With sdf_runtime.h, all a unit needs to define an extern "C" entry point that takes a handle.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -174,13 +174,17 @@ inline GenCall gen_call(sdf_tape *t, const double *X, int nx, const double *Y, i
     return call;
 }
 
-// ---- sdf_hip.hip (the generate pipeline) ----
-int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb);
+// ---- sdf_prepass.hip (k_skip, k_prune_list, k_cull and their launches) ----
 int enqueue_skip(sdf_tape *t, const double *d_axes, int nx, int ny, int nz, int bs, int b0, int b1, int precision,
                  unsigned char *d_kinds, hipStream_t st);
+int enqueue_prepass(const GenCall &call, sdf_mesh *m, int nb, int tape_stride, hipStream_t st);
+int enqueue_cull(sdf_tape *t, sdf_mesh *m, int nb, int tape_stride, bool tail_order, int tail_max, hipStream_t st);
+// ---- sdf_eval.hip (k_eval_*) ----
 struct FieldTile;   // (sdf_plain.h)
 void enqueue_eval_tiles(sdf_tape *t, int precision, const double *dX, const double *dY, const double *dZ, const FieldTile *d_tiles,
                         const int *d_org, float *d_vol, size_t largest_tile, int nt, hipStream_t st);
+// ---- sdf_generate.hip (the generate pipeline) ----
+int grid_batches(int nx, int ny, int nz, int bs, const char *who, GridDesc &g, int &nb);
 int generate_impl(sdf_mesh *m, const GenCall &call);
 int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, sdfk::MeshCounters &h);
 // ---- sdf_chunked.hip (batch_size > 32: through device memory, a chunk of batches per submission) ----

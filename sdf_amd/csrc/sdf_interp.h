@@ -947,3 +947,22 @@ __device__ __forceinline__ T run_tape1_ext(const uint32_t *__restrict__ code, co
 }
 
 }  // namespace sdfk
+
+// ---- launching a kernel template <T, FULL> whose first two arguments are the tape's code and constants -----------------------
+// the float64 kernel, with or without the trigonometric ops (`full`: sdf_tape::full); the arguments behind the stream are the kernel's
+#define LAUNCH_F64_ON(STREAM, KERNEL, grid, block, shmem, full, ...)                                            \
+    do {                                                                                                        \
+        if (full) hipLaunchKernelGGL((KERNEL<double, true>), grid, block, shmem, STREAM, __VA_ARGS__);          \
+        else hipLaunchKernelGGL((KERNEL<double, false>), grid, block, shmem, STREAM, __VA_ARGS__);              \
+    } while (0)
+
+// dispatch over (precision, FULL) for a tape handle `t` (sdf_internal.h), which supplies the code and the constants of that precision
+#define LAUNCH_TAPE_ON(STREAM, KERNEL, grid, block, shmem, t, precision, ...)                                   \
+    do {                                                                                                        \
+        if ((precision) == SDF_PRECISION_F64) {                                                                 \
+            LAUNCH_F64_ON(STREAM, KERNEL, grid, block, shmem, (t)->full, (t)->d_code, (t)->d_c64, __VA_ARGS__); \
+        } else {                                                                                                \
+            if ((t)->full) hipLaunchKernelGGL((KERNEL<float, true>), grid, block, shmem, STREAM, (t)->d_code, (t)->d_c32, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL<float, false>), grid, block, shmem, STREAM, (t)->d_code, (t)->d_c32, __VA_ARGS__); \
+        }                                                                                                       \
+    } while (0)

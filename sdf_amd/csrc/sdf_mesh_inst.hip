@@ -1,5 +1,5 @@
 // sdf_mesh_inst.hip -- instantiations of the fused sample+march kernel for ONE family.
-// Built twice (see build.sh): -DMESH_T=double -DMESH_FULL=0|1 -DMESH_NAME=... (FULL: the tape uses the trigonometric ops),
+// Built twice (see build.units): -DMESH_T=double -DMESH_FULL=0|1 -DMESH_NAME=... (FULL: the tape uses the trigonometric ops),
 // so the families compile in parallel.  (float32 sampling of the meshing path was removed in round 5.)
 #include "sdf_device.h"
 

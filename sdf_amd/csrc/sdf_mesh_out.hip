@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
 // welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.sh).
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

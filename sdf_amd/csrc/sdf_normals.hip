@@ -6,7 +6,7 @@
 //
 // One welded vertex per lane.  The interpreter is inlined ONCE: the six evaluations are passes of one loop whose counter is
 // wave-uniform -- the order of k_render's normal phase (sdf_render.hip): plus first, then minus.  Lanes never branch around the
-// interpreter -- this unit is built with the structurizer option that is only safe for wave-uniform control flow (build.sh): a lane
+// interpreter -- this unit is built with the structurizer option that is only safe for wave-uniform control flow (build.units): a lane
 // beyond the last vertex evaluates at the last vertex and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
 // The flat vertices are counted by one integer atomic add per wave that has any.
 #include "sdf_interp.h"
@@ -58,8 +58,7 @@ int launch_vertex_normals(hipStream_t st, const uint32_t *d_code, const double *
                           double eps, double *d_out, unsigned long long *d_flat) {
     if (n < 1) return 0;
     const unsigned grid = (unsigned)((n + 255) / 256);                 // (n < 2^31 vertices: the weld's limit)
-    if (full) hipLaunchKernelGGL((k_vertex_normals<double, true>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, eps, d_out, d_flat);
-    else hipLaunchKernelGGL((k_vertex_normals<double, false>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, eps, d_out, d_flat);
+    LAUNCH_F64_ON(st, k_vertex_normals, dim3(grid), dim3(256), 0, full, d_code, d_consts, d_pts, n, eps, d_out, d_flat);
     return (int)hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // sdf_plain.h -- launchers of the kernels that are NOT tape interpreters (sdf_plain.hip, built without the interpreters'
-// structurizer option; build.sh).  Each launches on `stream` with the given grid and block; the caller checks
+// structurizer option; build.units).  Each launches on `stream` with the given grid and block; the caller checks
 // hipGetLastError() as it did when the kernels shared its translation unit.
 #pragma once
 #include "sdf_device.h"

@@ -2,8 +2,8 @@
 // marching cubes of caller-supplied volumes and tiles, the two-pass meshing's scan and emission, the multi-GPU exchange
 // unit's kernels (k_pack_slab / k_expand / k_collect_headers), the STL records.
 //
-// A translation unit of its own because it is built WITHOUT -structurizecfg-skip-uniform-regions (build.sh).  The tape
-// interpreters (sdf_hip.hip, sdf_mesh_inst.hip) need that option -- their dispatch is a scalar jump through a table
+// A translation unit of its own because it is built WITHOUT -structurizecfg-skip-uniform-regions (build.units).  The tape
+// interpreters (sdf_eval.hip, sdf_prepass.hip, sdf_mesh_inst.hip, ...) need that option -- their dispatch is a scalar jump through a table
 // (asm goto + s_setpc, sdf_interp.h) that the structurizer must leave alone -- but it is not safe for kernels whose
 // lanes diverge: r03's k_expand, written here first in the interpreters' unit, came out wrong for every workgroup that
 // straddled into the last slab (a divergent search loop next to a uniform one), and right without the option.

@@ -21,7 +21,7 @@ struct PruneArgs {
     const MeshCounters *ctr;         //               (NULL: every batch, by index)
 };
 
-// The interval pass of one workgroup of the prepass kernel (k_skip, sdf_hip.hip): 8 lanes per batch
+// The interval pass of one workgroup of the prepass kernel (k_skip, sdf_prepass.hip): 8 lanes per batch
 // (lane = octant of the batch's box of sample coordinates), PRUNE_BLOCK / 8 batches per workgroup.
 // It runs for EVERY batch, next to the skip test rather than after it: the work list is not known
 // yet, and a launch of its own behind k_compact would sit on the critical path.

@@ -9,7 +9,7 @@
 // The interpreter is inlined ONCE: march, refinement and the six evaluations of the normal are phases of one loop whose phase and
 // counter are wave-uniform (the march ends when `__any(status == MARCH)` says so or after max_steps passes, the others after `refine`
 // and 6 passes).  Lanes never branch around the interpreter -- this unit is built with the structurizer option that is only safe for
-// wave-uniform control flow (build.sh) -- they take their state changes by selects: a lane that is done keeps evaluating at its frozen
+// wave-uniform control flow (build.units) -- they take their state changes by selects: a lane that is done keeps evaluating at its frozen
 // parameter and discards the value; a lane outside the image is a MISS from the start and stores nothing.
 #include <cmath>
 #include <string>
@@ -153,8 +153,7 @@ extern "C" int sdf_render_host(sdf_tape *t, const double *frame18, int width, in
     const unsigned grid = (unsigned)((a.n_tiles + 3) / 4);
     HIPCHK_FN(scratch.alloc());
     HIPCHK_FN(timer.start(st));
-    if (t->full) hipLaunchKernelGGL((k_render<double, true>), dim3(grid), dim3(256), 0, st, (const uint32_t *)t->d_code, (const double *)t->d_c64, a, depth, normal, steps, status);
-    else hipLaunchKernelGGL((k_render<double, false>), dim3(grid), dim3(256), 0, st, (const uint32_t *)t->d_code, (const double *)t->d_c64, a, depth, normal, steps, status);
+    LAUNCH_F64_ON(st, k_render, dim3(grid), dim3(256), 0, t->full, (const uint32_t *)t->d_code, (const double *)t->d_c64, a, depth, normal, steps, status);
     HIPCHK_FN(hipGetLastError());
     HIPCHK_FN(timer.stop(st));
     HIPCHK_FN(hipMemcpyAsync(h_depth, depth, n * 8, hipMemcpyDeviceToHost, st));

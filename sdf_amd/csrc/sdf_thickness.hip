@@ -8,7 +8,7 @@
 // and the bisection are phases of one loop whose phase and counter are wave-uniform -- k_render's structure (sdf_render.hip) in the
 // order NORMAL -> MARCH -> REFINE: the march ends when `__any(status == MARCH)` says so or after max_steps passes, REFINE is skipped
 // when no lane of the wave is THICK.  Lanes never branch around the interpreter -- this unit is built with the structurizer option
-// that is only safe for wave-uniform control flow (build.sh) -- they take their state changes by selects: a lane that is done keeps
+// that is only safe for wave-uniform control flow (build.units) -- they take their state changes by selects: a lane that is done keeps
 // evaluating at its frozen parameter and discards the value, a FLAT lane (direction 0) evaluates at its vertex.  A lane beyond the
 // last vertex evaluates at the last vertex and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
 #include <cmath>
@@ -107,8 +107,7 @@ int launch_vertex_thickness(hipStream_t st, const uint32_t *d_code, const double
                             const ThicknessArgs &a, double *d_thickness, uint8_t *d_status, int32_t *d_steps) {
     if (n < 1) return 0;
     const unsigned grid = (unsigned)((n + 255) / 256);                 // (n < 2^31 vertices: the weld's limit)
-    if (full) hipLaunchKernelGGL((k_vertex_thickness<double, true>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, a, d_thickness, d_status, d_steps);
-    else hipLaunchKernelGGL((k_vertex_thickness<double, false>), dim3(grid), dim3(256), 0, st, d_code, d_consts, d_pts, n, a, d_thickness, d_status, d_steps);
+    LAUNCH_F64_ON(st, k_vertex_thickness, dim3(grid), dim3(256), 0, full, d_code, d_consts, d_pts, n, a, d_thickness, d_status, d_steps);
     return (int)hipGetLastError();
 }
 

@@ -67,7 +67,7 @@ def rank():
 
 def shard_bounds(n_work, r, world):
     """contiguous chunk [lo, hi) of the work list for rank r (same formula as
-    csrc/sdf_hip.hip `k_compact`)"""
+    csrc/sdf_plain.hip `k_compact`)"""
     return (n_work * r) // world, (n_work * (r + 1)) // world
 
 

@@ -230,7 +230,7 @@ def _strip_c_comments(text):
 
 
 def source_id():
-    """sha256 (16 hex digits) over the library's sources -- sdf_amd/csrc/*.{h,hip,inc,sh} and the public header
+    """sha256 (16 hex digits) over the library's sources -- sdf_amd/csrc/*.{h,hip,inc,sh,units} and the public header
     include/sdf_hip.h -- WITHOUT their comments and blank lines: what a committed rocprofv3 summary was taken on
     (tools/summarize_prof.py writes it, bench.py only quotes a summary whose id is this build's).  Editing a comment does
     not make a profile stale; editing code, a string literal or the exchange's host code does."""
@@ -243,9 +243,9 @@ def source_id():
     files = sorted(glob.glob(os.path.join(d, '*'))) + [os.path.join(os.path.dirname(here), 'include', 'sdf_hip.h')]
     for f in files:
         ext = f.rsplit('.', 1)[-1]
-        if os.path.isfile(f) and ext in ('h', 'hip', 'inc', 'sh'):
+        if os.path.isfile(f) and ext in ('h', 'hip', 'inc', 'sh', 'units'):
             text = open(f, encoding='utf-8', errors='replace').read()
-            if ext == 'sh':
+            if ext in ('sh', 'units'):
                 text = re.sub(r'(?m)^\s*#(?!!).*$', '', text)
             else:
                 text = _strip_c_comments(text)

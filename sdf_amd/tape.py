@@ -77,7 +77,7 @@ SV_FLAG, SV_SHIFT = 1 << 15, 16
 PD_FLAG, PD_SHIFT = 1 << 19, 20
 PREFIX_MASK = 0x00FFF800
 
-PRUNE_MAX_INSTR = 256     # csrc/sdf_hip.hip generate_impl: `pruning` needs n_instr <= 256
+PRUNE_MAX_INSTR = 256     # csrc/sdf_generate.hip generate_impl: `pruning` needs n_instr <= 256
 
 # hard limits of the default kernel build (csrc/sdf_interp.h NP_SLOTS / ND_SLOTS)
 MAX_P_SLOTS = 8

@@ -247,7 +247,7 @@ for _k in CUSTOM_FIXTURES:
 
 # ---- models that need many register slots (sdf_amd/tape.py palloc / dalloc): each one is lowered to the register-file variant
 # of k_mesh named in its key -- (saved-point slots, saved-distance slots) of the smallest file that holds the tape, plain or trig
-# family (csrc/sdf_hip.hip launch_mesh, tape_needs_full).  Nested transforms over booleans take saved-point slots, right-nested
+# family (csrc/sdf_generate.hip launch_mesh, csrc/sdf_ctx.hip tape_needs_full).  Nested transforms over booleans take saved-point slots, right-nested
 # booleans saved-distance slots.  Kept apart from FIXTURES: values.npz / bounds.npz stay as they are (values_slots.npz,
 # bounds_slots.npz and gen_slots_*.npz are theirs, tools/make_golden.py slots). ----
 SLOT_FIXTURES = {

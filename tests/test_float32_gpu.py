@@ -83,7 +83,7 @@ def _grid_model(name):
 
 
 def test_the_float_trig_interpreter_is_reached(ns):
-    """run_tape<float, FULL = true> is what LAUNCH_TAPE picks for a tape that `tape_needs_full` (csrc/sdf_hip.hip; restated by
+    """run_tape<float, FULL = true> is what LAUNCH_TAPE picks for a tape that `tape_needs_full` (csrc/sdf_ctx.hip; restated by
     test_register_slots.is_trig): several models of test a have one, and several the plain build"""
     full = [name for name in ALL if is_trig(tape.lower(fixtures.build(name, ns)))]
     assert len(full) >= 10 and len(ALL) - len(full) >= 10, full

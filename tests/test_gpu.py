@@ -2018,7 +2018,7 @@ def test_forced_register_file_gives_the_same_soup(name, ns, eng, monkeypatch):
 
 
 def test_device_tape_refuses_a_ninth_slot(ns, oracle_lib, eng):
-    """validate_tape (csrc/sdf_hip.hip) refuses a tape that declares more slots than the (8,8) register file holds; one that
+    """validate_tape (csrc/sdf_ctx.hip) refuses a tape that declares more slots than the (8,8) register file holds; one that
     declares exactly 8 + 8 is accepted and meshed by that file"""
     from sdf_amd import engine
     f = ns['sphere'](1) & ns['box'](1.5)

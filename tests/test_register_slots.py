@@ -12,7 +12,7 @@ import fixtures
 from conftest import GOLDEN, value_tolerance
 from sdf_amd import ease, tape
 
-# csrc/sdf_hip.hip launch_mesh `kFile`: index = the register file's number (SDF_MESH_SLOTS)
+# csrc/sdf_generate.hip launch_mesh `kFile`: index = the register file's number (SDF_MESH_SLOTS)
 REGISTER_FILES = ((1, 1), (2, 2), (4, 2), (2, 4), (4, 4), (8, 8))
 
 _TRIG_EASES = {ease.EASING_IDS[n] for n in ('in_sine', 'out_sine', 'in_out_sine', 'in_expo', 'out_expo', 'in_out_expo',
@@ -20,7 +20,7 @@ _TRIG_EASES = {ease.EASING_IDS[n] for n in ('in_sine', 'out_sine', 'in_out_sine'
 
 
 def is_trig(t):
-    """csrc/sdf_hip.hip tape_needs_full: the tape is meshed by the trig family (sdf_launch_mesh_f64_full)"""
+    """csrc/sdf_ctx.hip tape_needs_full: the tape is meshed by the trig family (sdf_launch_mesh_f64_full)"""
     for i in range(t.n_instr):
         op = tape.OP_NAMES[int(t.code[2 * i]) & 255]
         c = t.consts[(int(t.code[2 * i + 1]) & tape.COFF_MASK) + 1:]

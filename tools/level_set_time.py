@@ -7,7 +7,7 @@ The mesh is the canonical CSG example (bench.py's model) welded on the device at
 is its extent / --voxels.  Prints one JSON line: triangle count, work grid and active dims, the median wall time of the
 C call (host clock around the synchronous call: upload, all kernels, the copy of the cropped grid) and whether the grid
 stays under the tape-constant limit below which `generate` still prunes a model holding it (0xFFFFF0 constants,
-csrc/sdf_hip.hip: `t->n_consts < 0xFFFFF0u`).  Needs an MI355X."""
+csrc/sdf_generate.hip: `t->n_consts < 0xFFFFF0u`).  Needs an MI355X."""
 import argparse
 import json
 import os
