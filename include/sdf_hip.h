@@ -516,6 +516,45 @@ int sdf_mesh_mend(sdf_mesh *mesh, sdf_mesh **out, sdf_mend_stats *stats);
 /* the kernels of this thread's last sdf_mesh_mend, milliseconds by HIP events; parts3 (or NULL): the keys, the two sorts, runs and
  * emission (tools/mend_time.py) */
 double sdf_mesh_mend_last_kernel_ms(double *parts3);
+/* The contours of a sampled 2-D field: closed, oriented, ordered polylines (added under ABI 17: the version is unchanged, nothing
+ * above changes; DESIGN.md section 4m, defined by tests/contour_ref.py and reproduced bit for bit).  Samples V[nw][nx][ny] (nw
+ * layers, the last axis fastest) over the axes X[nx], Y[ny]; a sample is inside iff v < level.  Marching squares with the saddles
+ * decided by the cell's centre value ((v00 + v10) + (v01 + v11)) * 0.25; a cell emits 0 .. 2 segments with the inside on their
+ * left, so outer boundaries run counter-clockwise (positive area) and holes clockwise (negative area); a cell with a non-finite
+ * corner emits nothing and is counted.  The vertex of a grid edge is computed from the lower-index sample a to the higher-index
+ * one b, t = (a - level) / (a - b), c = ca + t * (cb - ca).  Segments are numbered by layer, cell ix * (ny - 1) + iy and slot, linked
+ * through the case table, and every chain is one contour: a closed loop starts at its smallest segment index and has one point per
+ * segment, an open chain (it ends at the border of the grid or beside a non-finite cell) starts at its segment without a
+ * predecessor and has one point more.  Contours are ordered by that first segment, which groups them by layer.  area is the
+ * shoelace sum, left to right from the first point; 0 for an open chain.  Segments of length zero (a sample equal to the level)
+ * are kept.
+ *   sdf_contour_grid_host   contours of a host sample grid: the twin of sdf_marching_cubes_host, and what serves models with user
+ *                           closures and float32 evaluation (the caller evaluates, then calls this).
+ *   sdf_contour_host        samples on the device -- float64, the interpreter of sdf_eval_points over points made from the axes, in
+ *                           slabs of at most 2^24 -- and contours.  dim 3: layer w lies at z = W[w]; dim 2: W is ignored and nw must
+ *                           be 1.  h_values (or NULL) receives the nw * nx * ny samples.
+ * Both return a handle and the counts; sdf_contours_fetch copies the arrays out -- h_points n_points x 2 float64, h_offsets
+ * (n_contours + 1) int64, h_closed n_contours uint8, h_layer n_contours int32, h_area n_contours float64; any pointer may be NULL --
+ * and sdf_contours_destroy frees the handle's one device block.  Synchronous, on the context's stream.  Device memory: two scratch
+ * allocations (17 bytes per sample and the library scan's, the slab of points; 60 bytes per segment), freed before the call
+ * returns whether it fails or not, and the handle's block.  `rounds` = ceil(log2(n_segments)): the launches of each of the two
+ * pointer-jumping phases of the linking.  Refused on the host before anything is allocated or launched, with return value 2: a NULL
+ * pointer, nx < 2 or ny < 2, nw < 1, nw * nx * ny > 2^28, a level or an axis value that is not finite, axes that are not strictly
+ * increasing, a dim other than 2 and 3, dim 2 with nw != 1, a tape with user closures (sdf_tape_extern_count > 0).  Other failures
+ * return 1 and *out is NULL. */
+typedef struct sdf_contours sdf_contours;
+typedef struct sdf_contour_counts {
+    int64_t n_points, n_contours, n_segments, nonfinite_cells, rounds;
+} sdf_contour_counts;
+int sdf_contour_grid_host(sdf_ctx *ctx, const double *h_values, int nw, int nx, int ny, const double *X, const double *Y, double level,
+                          sdf_contours **out, sdf_contour_counts *counts);
+int sdf_contour_host(sdf_tape *tape, int dim, const double *X, int nx, const double *Y, int ny, const double *W, int nw, double level,
+                     double *h_values, sdf_contours **out, sdf_contour_counts *counts);
+int sdf_contours_fetch(sdf_contours *contours, double *h_points, int64_t *h_offsets, uint8_t *h_closed, int32_t *h_layer, double *h_area);
+int sdf_contours_destroy(sdf_contours *contours);
+/* the kernels of this thread's last sdf_contour_grid_host or sdf_contour_host, milliseconds by HIP events; parts4 (or NULL): the
+ * sampling (0 for the grid entry), count + scan + emit, the linking with its scans and the scatter, the areas (tools/contour_time.py) */
+double sdf_contour_last_kernel_ms(double *parts4);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

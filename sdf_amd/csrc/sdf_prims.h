@@ -15,6 +15,11 @@ hipError_t scan_tmp_bytes(hipStream_t st, long long n, size_t *bytes);
 // for a count outside 0 .. n
 int number_flags(const char *who, const char *what, hipStream_t st, int *flags, int *pos, long long n, void *tmp, size_t tmp_bytes,
                  long long *count);
+// the same for items that each count 0 or more (the segments of a cell, the points of a contour: sdf_contour.hip): pos[i] = the sum of
+// the counts before i, *total = the sum of all of them, which the caller bounds by max_total < 2^31 -- "<who>the scan of the <what> is
+// inconsistent" for a total outside 0 .. max_total.  number_flags is this with max_total = n
+int number_counts(const char *who, const char *what, hipStream_t st, int *counts, int *pos, long long n, long long max_total, void *tmp,
+                  size_t tmp_bytes, long long *total);
 // the bits that hold 0 .. n - 1: where a library radix sort over such keys may stop
 static inline int bits_for(long long n) { int b = 1; while (b < 63 && (1ll << b) < n) b += 1; return b; }
 }

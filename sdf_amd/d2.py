@@ -49,6 +49,20 @@ class SDF2(SDFBase):
         self._k = k
         return self
 
+    def contours(self, *args, **kwargs):
+        """closed, oriented polylines of the outline (not in the reference: sdf_amd/contour.py)"""
+        from .contour import contours
+        return contours(self, *args, **kwargs)
+
+    def save(self, path, *args, **kwargs):
+        """the outline as 'x.svg' or 'x.dxf'; the arguments of `contours`"""
+        from .contour import contours
+        if str(path).rsplit('.', 1)[-1].lower() not in ('svg', 'dxf'):
+            raise ValueError('a 2-D model is saved as .svg or .dxf, got %r' % (path,))
+        c = contours(self, *args, **kwargs)
+        c.save(path)
+        return c
+
 
 def sdf2(f):
     def wrapper(*args, **kwargs):

@@ -92,6 +92,12 @@ class SDF3(SDFBase):
         from .render import render
         return render(self, path, **kwargs)
 
+    def slices(self, z, *args, **kwargs):
+        """the model cut at the height z, or at every height of a sequence: closed, oriented polylines per layer (not in the
+        reference: sdf_amd/contour.py; `slice` is the op that makes a 2-D model of the cut at z = 0)"""
+        from .contour import contours
+        return contours(self, *args, z=z, **kwargs)
+
     def show_slice(self, *args, **kwargs):
         from . import core
         return core.show_slice(self, *args, **kwargs)

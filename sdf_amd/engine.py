@@ -75,6 +75,14 @@ class SdfMendStats(ctypes.Structure):
     _fields_ = [(k, _c_i64) for k in MEND_FIELDS] + [('kernel_ms', ctypes.c_double)]
 
 
+CONTOUR_COUNTS = ('n_points', 'n_contours', 'n_segments', 'nonfinite_cells', 'rounds')
+
+
+class SdfContourCounts(ctypes.Structure):
+    """mirror of `sdf_contour_counts` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in CONTOUR_COUNTS]
+
+
 class SdfStats(ctypes.Structure):
     """mirror of `sdf_stats` in include/sdf_hip.h"""
     _fields_ = [
@@ -193,6 +201,13 @@ ABI = {
     'sdf_mesh_simplify_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_mesh_mend': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(SdfMendStats)]),
     'sdf_mesh_mend_last_kernel_ms': (ctypes.c_double, [_f64p]),
+    'sdf_contour_grid_host': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, ctypes.c_double,
+                                             ctypes.POINTER(_vp), ctypes.POINTER(SdfContourCounts)]),
+    'sdf_contour_host': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_double,
+                                        _f64p, ctypes.POINTER(_vp), ctypes.POINTER(SdfContourCounts)]),
+    'sdf_contours_fetch': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(_c_i64), _u8p, ctypes.POINTER(ctypes.c_int32), _f64p]),
+    'sdf_contours_destroy': (ctypes.c_int, [_vp]),
+    'sdf_contour_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
