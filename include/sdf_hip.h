@@ -555,6 +555,33 @@ int sdf_contours_destroy(sdf_contours *contours);
 /* the kernels of this thread's last sdf_contour_grid_host or sdf_contour_host, milliseconds by HIP events; parts4 (or NULL): the
  * sampling (0 for the grid entry), count + scan + emit, the linking with its scans and the scatter, the areas (tools/contour_time.py) */
 double sdf_contour_last_kernel_ms(double *parts4);
+/* Build directions rated on the device (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4n,
+ * defined by tests/overhang_ref.py and reproduced bit for bit).  For the float64 soup of a mesh and n_dirs UNIT directions d ("up": the
+ * bed lies below the part), per direction: h(p) = (px dx + py dy) + pz dz and its extremes lo, hi over the vertices of the finite
+ * triangles (none: +inf, -inf); per triangle (a, b, c) with the raw normal n = (b - a) x (c - a), dbl = |n|, dn = (nx dx + ny dy) +
+ * nz dz and ha, hb, hc = h - lo:  on_bed = max(ha, hb, hc) <= bed_tol;  overhang = finite, not on_bed, dn < -(sin_limit * dbl);
+ * contact = finite, on_bed, dn < 0.  s0 = sum of dbl over the overhangs (twice their area), s1 = sum of (-dn) ((ha + hb) + hc) over
+ * them (six times the volume of the prisms from the overhanging faces straight down to the bed plane -- a PROXY for the support: the
+ * part's own material under an overhang is not subtracted, and the faces hidden inside a soup of overlapping solids count), s2 = sum
+ * of dbl over the contacts (twice the area on the bed).  Every multiply and add is rounded separately and the sums run through a
+ * fixed tree: chunks of 1024 consecutive triangles summed one after the other from +0.0, the chunk partials in groups of 256 through
+ * the halving tree of sdf_mesh_moments.  The result does not depend on launch geometry, the order of atomics, or the slabs:
+ * the directions are taken in slabs whose chunk partials stay under max_scratch_bytes (0: 64 MiB; never fewer than one direction).
+ *   sdf_mesh_overhangs         h_values: n_dirs x 5 float64 (lo, hi, s0, s1, s2); h_counts: n_dirs x 2 int64 (overhanging triangles,
+ *                              bed-contact triangles).
+ *   sdf_mesh_overhang_classes  one direction h_dir3; h_classes: one byte per triangle -- 0 neither, 1 overhang, 2 bed contact,
+ *                              3 non-finite -- by the same predicates.
+ * Both serve generated meshes, meshes of sdf_generate_records and adopted soups, like sdf_mesh_moments.  Synchronous, on the
+ * context's stream; one scratch allocation, freed before the call returns whether it fails or not.  A mesh of 0 triangles gives the
+ * empty result (+inf, -inf, zeros) without a launch.  Refused on the host before anything is allocated or launched, with return
+ * value 2: a NULL argument, n_dirs < 1 or > 2^20, a direction that is zero, not finite or not of unit length to 1e-12, sin_limit
+ * outside [0, 1), bed_tol negative or NaN, 2^31 or more triangles.  Other failures return 1. */
+int sdf_mesh_overhangs(sdf_mesh *mesh, const double *h_dirs, int64_t n_dirs, double sin_limit, double bed_tol, size_t max_scratch_bytes,
+                       double *h_values, int64_t *h_counts);
+int sdf_mesh_overhang_classes(sdf_mesh *mesh, const double *h_dir3, double sin_limit, double bed_tol, uint8_t *h_classes);
+/* the kernels of this thread's last sdf_mesh_overhangs or sdf_mesh_overhang_classes alone, milliseconds by HIP events; *n_slabs (or
+ * NULL): the slabs of directions that call took (tools/overhang_time.py) */
+double sdf_overhang_last_kernel_ms(int64_t *n_slabs);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -42,3 +42,4 @@ from .render import render   # (not in the reference: sphere-traced previews, DE
 from .measure import measure   # (not in the reference: volume, area, inertia and the edge census on the device, section 4g)
 from .thickness import thickness, Thickness   # (not in the reference: the wall thickness at the vertices of a mesh, probed on the device, section 4l)
 from .shells import shells, measure_shells, Shells   # (not in the reference: the connected shells of a mesh, kept or dropped on the device, section 4h)
+from .overhang import overhangs, overhangs_of_mesh, overhangs_soup, sphere_directions, Overhangs   # (not in the reference: build directions rated on the device, section 4n)

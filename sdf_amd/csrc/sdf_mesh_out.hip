@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
-// welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
+// welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build directions, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -13,6 +13,7 @@
 #include "sdf_measure.h"
 #include "sdf_mend.h"
 #include "sdf_normals.h"
+#include "sdf_overhang.h"
 #include "sdf_plain.h"
 #include "sdf_simplify.h"
 #include "sdf_thickness.h"
@@ -575,6 +576,65 @@ int sdf_mesh_mend(sdf_mesh *m, sdf_mesh **out, sdf_mend_stats *stats) {
 double sdf_mesh_mend_last_kernel_ms(double *parts3) {
     for (int k = 0; parts3 && k < 3; k++) parts3[k] = g_mend_kernel_ms[k];
     return g_mend_kernel_ms[0] + g_mend_kernel_ms[1] + g_mend_kernel_ms[2];
+}
+
+// ---- build directions rated: extents, overhang and bed-contact totals per direction, classes per triangle ----
+static thread_local double g_overhang_kernel_ms = 0.0;
+static thread_local long long g_overhang_slabs = 0;
+
+// the refusals both entries share; 0 when the arguments are in order
+static int overhang_refused(const char *who, const double *h_dirs, long long n_dirs, double sin_limit, double bed_tol) {
+    const std::string w(who);
+    if (n_dirs < 1) return fail(w + ": n_dirs must be at least 1");
+    if (n_dirs > OVERHANG_MAX_DIRS) return fail(w + ": more than 2^20 directions");
+    if (!(sin_limit >= 0.0 && sin_limit < 1.0)) return fail(w + ": sin_limit must lie in [0, 1)");
+    if (!(bed_tol >= 0.0)) return fail(w + ": bed_tol must not be negative or NaN");
+    for (long long k = 0; k < n_dirs; k++) {
+        const double x = h_dirs[3 * k], y = h_dirs[3 * k + 1], z = h_dirs[3 * k + 2];
+        const double len = std::sqrt((x * x + y * y) + z * z);
+        if (!(std::fabs(len - 1.0) <= 1e-12))                          // (a NaN or an infinite component fails this too)
+            return fail(w + ": direction " + std::to_string(k) + " is zero, not finite or not of unit length to 1e-12");
+    }
+    return 0;
+}
+
+int sdf_mesh_overhangs(sdf_mesh *m, const double *h_dirs, int64_t n_dirs, double sin_limit, double bed_tol, size_t max_scratch_bytes,
+                       double *h_values, int64_t *h_counts) {
+    if (!m || !h_dirs || !h_values || !h_counts) { fail("sdf_mesh_overhangs: NULL argument"); return 2; }
+    if (overhang_refused("sdf_mesh_overhangs", h_dirs, (long long)n_dirs, sin_limit, bed_tol)) return 2;
+    MESH_READY(m);
+    if ((long long)m->st.n_triangles >= (1ll << 31)) { fail("sdf_mesh_overhangs: 2^31 or more triangles"); return 2; }
+    g_overhang_kernel_ms = 0.0;
+    g_overhang_slabs = 0;
+    for (int64_t k = 0; k < n_dirs; k++) {                             // the empty result: no launch for a mesh of 0 triangles
+        h_values[5 * k] = INFINITY; h_values[5 * k + 1] = -INFINITY;
+        h_values[5 * k + 2] = h_values[5 * k + 3] = h_values[5 * k + 4] = 0.0;
+        h_counts[2 * k] = h_counts[2 * k + 1] = 0;
+    }
+    if (m->st.n_triangles == 0) return 0;
+    MESH_SOUP_READY(m);
+    HIPCHK(set_device(m->ctx->device));
+    return overhang_rate(m->ctx->stream, (const double *)mesh_soup(m), (long long)m->st.n_triangles, h_dirs, (long long)n_dirs, sin_limit,
+                         bed_tol, max_scratch_bytes, h_values, h_counts, &g_overhang_slabs, &g_overhang_kernel_ms);
+}
+
+int sdf_mesh_overhang_classes(sdf_mesh *m, const double *h_dir3, double sin_limit, double bed_tol, uint8_t *h_classes) {
+    if (!m || !h_dir3 || !h_classes) { fail("sdf_mesh_overhang_classes: NULL argument"); return 2; }
+    if (overhang_refused("sdf_mesh_overhang_classes", h_dir3, 1, sin_limit, bed_tol)) return 2;
+    MESH_READY(m);
+    if ((long long)m->st.n_triangles >= (1ll << 31)) { fail("sdf_mesh_overhang_classes: 2^31 or more triangles"); return 2; }
+    g_overhang_kernel_ms = 0.0;
+    g_overhang_slabs = 0;
+    if (m->st.n_triangles == 0) return 0;
+    MESH_SOUP_READY(m);
+    HIPCHK(set_device(m->ctx->device));
+    return overhang_classes(m->ctx->stream, (const double *)mesh_soup(m), (long long)m->st.n_triangles, h_dir3, sin_limit, bed_tol, h_classes,
+                            &g_overhang_kernel_ms);
+}
+
+double sdf_overhang_last_kernel_ms(int64_t *n_slabs) {
+    if (n_slabs) *n_slabs = (int64_t)g_overhang_slabs;
+    return g_overhang_kernel_ms;
 }
 
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {

@@ -208,6 +208,10 @@ ABI = {
     'sdf_contours_fetch': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(_c_i64), _u8p, ctypes.POINTER(ctypes.c_int32), _f64p]),
     'sdf_contours_destroy': (ctypes.c_int, [_vp]),
     'sdf_contour_last_kernel_ms': (ctypes.c_double, [_f64p]),
+    'sdf_mesh_overhangs': (ctypes.c_int, [_vp, _f64p, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_size_t, _f64p,
+                                          ctypes.POINTER(_c_i64)]),
+    'sdf_mesh_overhang_classes': (ctypes.c_int, [_vp, _f64p, ctypes.c_double, ctypes.c_double, _u8p]),
+    'sdf_overhang_last_kernel_ms': (ctypes.c_double, [ctypes.POINTER(_c_i64)]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
@@ -648,6 +652,36 @@ class Mesh:
         m.emitted = False
         m.mend_stats = dict({k: int(getattr(st, k)) for k in MEND_FIELDS}, kernel_ms=float(st.kernel_ms))
         return m
+
+    def overhangs(self, directions, sin_limit, bed_tol, max_scratch_bytes=0):
+        """build directions rated on the device (sdf_mesh_overhangs, csrc/sdf_overhang.hip; defined by
+        tests/overhang_ref.py::rate and reproduced bit for bit): for UNIT directions (K, 3), a dict of `lo`, `hi` (K,) -- the
+        extremes of the soup along each direction --, `sums` (K, 3) -- twice the overhanging area, six times the support prisms'
+        volume, twice the area on the bed -- and the counts `overhang_triangles`, `contact_triangles` (K,) int64.
+        `overhang.derive` turns the totals into areas, volume and height.  max_scratch_bytes: the cap of the chunk partials of a
+        slab of directions (0: 64 MiB); no bit depends on it.  Needs no weld.  ValueError, before any device work, for what the C
+        entry refuses: no direction, a direction not of unit length to 1e-12, sin_limit outside [0, 1), a negative bed_tol."""
+        eng = self.engine
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError('directions must have the shape (K, 3), got %r' % (d.shape,))
+        k = len(d)
+        values, counts = np.empty((max(k, 1), 5), np.float64), np.empty((max(k, 1), 2), np.int64)
+        _check(eng.lib, eng.lib.sdf_mesh_overhangs(self.handle, _dp(d, _f64p), k, float(sin_limit), float(bed_tol), int(max_scratch_bytes),
+                                                   _dp(values, _f64p), _dp(counts, ctypes.POINTER(_c_i64))))
+        return {'lo': values[:, 0].copy(), 'hi': values[:, 1].copy(), 'sums': values[:, 2:5].copy(),
+                'overhang_triangles': counts[:, 0].copy(), 'contact_triangles': counts[:, 1].copy()}
+
+    def overhang_classes(self, direction, sin_limit, bed_tol):
+        """(T,) uint8, the class of every triangle for ONE unit direction, by the predicates of `overhangs`
+        (sdf_mesh_overhang_classes): 0 neither, 1 overhang, 2 bed contact, 3 non-finite"""
+        eng = self.engine
+        d = np.ascontiguousarray(direction, dtype=np.float64).reshape(-1)
+        if d.shape != (3,):
+            raise ValueError('direction must have 3 components, got %r' % (direction,))
+        out = np.zeros(max(self.n_triangles, 1), np.uint8)
+        _check(eng.lib, eng.lib.sdf_mesh_overhang_classes(self.handle, _dp(d, _f64p), float(sin_limit), float(bed_tol), _dp(out, _u8p)))
+        return out[:self.n_triangles]
 
     def stl_records(self):
         """T x 50-byte binary STL records (normals computed on the device)"""

@@ -114,6 +114,13 @@ class Mesh:
         params = default_params((pts.min(axis=0), pts.max(axis=0)), steps3, start, min_step, t_far, normal_eps)
         return thickness_of_soup(pts[np.asarray(self.triangles)], f, step_scale=step_scale, max_steps=max_steps, refine=refine, **params)
 
+    def overhangs(self, directions=(0.0, 0.0, 1.0), angle=45.0, bed_tolerance=None, classes=False):
+        """build directions rated for this mesh on the device (sdf_amd/overhang.py): an `Overhangs`.
+        directions: one vector, an array (K, 3) or an int n for the six axes and n spiral points; a file has no sampling grid, so
+        bed_tolerance=None is 0.0"""
+        from .overhang import overhangs_soup
+        return overhangs_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], directions, angle, bed_tolerance, classes)
+
     def shells(self):
         """the connected shells of this mesh (sdf_amd/shells.py `Shells`), labelled on the device.  The soup is welded there again:
         `vertex_shell` is over THAT weld's vertices (lexicographic order), `triangle_shell` over this mesh's triangles"""
