@@ -582,6 +582,45 @@ int sdf_mesh_overhang_classes(sdf_mesh *mesh, const double *h_dir3, double sin_l
 /* the kernels of this thread's last sdf_mesh_overhangs or sdf_mesh_overhang_classes alone, milliseconds by HIP events; *n_slabs (or
  * NULL): the slabs of directions that call took (tools/overhang_time.py) */
 double sdf_overhang_last_kernel_ms(int64_t *n_slabs);
+/* Support rays traced through the field: the true support volume of a build direction (added under ABI 17: the version is unchanged,
+ * nothing above changes; DESIGN.md section 4o, defined by tests/supports_ref.py and reproduced bit for bit).  For the float64 soup of a
+ * mesh in the field f of `tape` and n_dirs UNIT directions d, one after another: the faces are the triangles that
+ * sdf_mesh_overhang_classes gives class 1 (overhang) for sin_limit and bed_tol, in triangle order, M of them; lo, hi are that rating's.
+ * Per face: n and dn as there, proj = -dn (twice the area projected on the bed); the centroid c = ((a + b) + c) / 3.0 per coordinate;
+ * tb = max(((cx dx + cy dy) + cz dz) - lo, 0), the distance to the bed plane.  A ray is sphere-traced from c along -d starting at
+ * t = start: start >= tb ends it as BED (0) with height tb and no evaluation; otherwise at most max_steps times v = f(c + t (-d)): NaN
+ * ends it as NAN (4, height NaN); v < 0 ends it with hi = t -- on the first evaluation as BURIED (2, height +0: the face has material
+ * `start` below it), later as PART (1); otherwise lo = t and t advances by max(v * step_scale, min_step), and t >= tb ends it as BED
+ * with height tb.  A ray that runs out of steps is UNRESOLVED (3) with height tb, an upper bound.  The bracket of a PART ray is bisected
+ * `refine` times (the midpoint goes to hi where f < 0 there, else to lo) and its height is hi.  The five terms of a ray: proj * height
+ * if BED or UNRESOLVED; proj * height if PART; proj if PART; proj; proj if BURIED -- else +0 -- summed over the M RAYS IN THEIR ORDER
+ * through the tree of sdf_mesh_overhangs (chunks of 1024 consecutive rays, then groups of 256 halved).  s0 / 2 is the support volume
+ * that stands on the bed, s1 / 2 the volume that stands on the part, s2 / 2 the projected area where supports touch the part, s3 / 2
+ * the projected area of all overhangs, s4 / 2 that of the buried ones.  One ray per face is first-order quadrature; a gap narrower
+ * than min_step can be stepped over; the columns are vertical.
+ *   params8 = sin_limit, bed_tol, start, min_step, step_scale, 0, 0, 0 (reserved).
+ *   h_values: n_dirs x 7 float64 (lo, hi, s0 .. s4); h_counts: n_dirs x 6 int64 (rays that ended BED, PART, BURIED, UNRESOLVED, NAN; M).
+ *   sdf_support_rays_fetch copies the rays of direction k out -- h_triangle M int32, h_height M float64, h_status M uint8, h_steps M
+ *   int32 (evaluations of the march), h_origin M x 3 float64; any pointer may be NULL -- and sdf_support_rays_destroy frees the handle
+ *   and its device blocks (one per direction with rays, 41 bytes a ray).
+ * Float64, the interpreter of sdf_eval_points.  It serves generated meshes, meshes of sdf_generate_records, adopted soups, selections,
+ * simplified and mended meshes.  Synchronous, on the context's stream, one wait per direction (for M); one scratch allocation (49
+ * bytes per triangle and the library scan's), sized once and freed before the call returns whether it fails or not.  A mesh of 0
+ * triangles gives the empty result (+inf, -inf, zeros, M = 0) without a launch.  Refused on the host before anything is allocated or
+ * launched, with return value 2: a NULL argument, a mesh without a soup on the device, a tape of another context, a tape with user
+ * closures (sdf_tape_extern_count > 0), a non-finite parameter, start or min_step not above 0, step_scale outside (0, 1], sin_limit
+ * outside [0, 1), bed_tol negative, max_steps < 1, refine < 0, n_dirs < 1 or > 1024, a direction that is zero, not finite or not of
+ * unit length to 1e-12, 2^31 or more triangles; for the fetch a direction index out of range.  Other failures return 1, nothing stays
+ * allocated and *out is NULL. */
+typedef struct sdf_support_rays sdf_support_rays;
+int sdf_mesh_support_rays(sdf_mesh *mesh, sdf_tape *tape, const double *h_dirs, int64_t n_dirs, const double *params8, int max_steps,
+                          int refine, sdf_support_rays **out, double *h_values, int64_t *h_counts);
+int sdf_support_rays_fetch(sdf_support_rays *rays, int64_t k, int32_t *h_triangle, double *h_height, uint8_t *h_status, int32_t *h_steps,
+                           double *h_origin);
+int sdf_support_rays_destroy(sdf_support_rays *rays);
+/* the kernels of this thread's last sdf_mesh_support_rays, milliseconds by HIP events, summed over the directions; parts4 (or NULL):
+ * classes and extents, numbering, rays, sums (tools/supports_time.py) */
+double sdf_mesh_supports_last_kernel_ms(double *parts4);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
 // welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build directions, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_supports.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +16,7 @@
 #include "sdf_overhang.h"
 #include "sdf_plain.h"
 #include "sdf_simplify.h"
+#include "sdf_supports.h"
 #include "sdf_thickness.h"
 
 using namespace sdfk;
@@ -48,6 +49,12 @@ int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes) {
     HIPCHK(stream_wait(c->stream));
     return 0;
 }
+
+// what sdf_mesh_support_rays leaves behind: one device block per direction that has rays
+struct sdf_support_rays {
+    sdf_ctx *ctx = nullptr;
+    std::vector<SupportRaysDir> dirs;
+};
 
 extern "C" {
 
@@ -635,6 +642,82 @@ int sdf_mesh_overhang_classes(sdf_mesh *m, const double *h_dir3, double sin_limi
 double sdf_overhang_last_kernel_ms(int64_t *n_slabs) {
     if (n_slabs) *n_slabs = (int64_t)g_overhang_slabs;
     return g_overhang_kernel_ms;
+}
+
+// ---- support rays through the field: the true support volume per build direction ----
+static thread_local double g_supports_ms[4] = {0.0, 0.0, 0.0, 0.0};
+
+int sdf_mesh_support_rays(sdf_mesh *m, sdf_tape *t, const double *h_dirs, int64_t n_dirs, const double *params8, int max_steps, int refine,
+                          sdf_support_rays **out, double *h_values, int64_t *h_counts) {
+    auto refuse = [](const std::string &why) { fail("sdf_mesh_support_rays: " + why); return 2; };
+    if (out) *out = nullptr;
+    if (!m || !t || !h_dirs || !params8 || !out || !h_values || !h_counts) return refuse("NULL argument");
+    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
+    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip");
+    for (int i = 0; i < 8; i++) if (!std::isfinite(params8[i])) return refuse("the parameters are not finite");
+    SupportParams p;
+    p.sin_limit = params8[0]; p.bed_tol = params8[1]; p.start = params8[2]; p.min_step = params8[3]; p.step_scale = params8[4];
+    p.max_steps = max_steps; p.refine = refine;
+    if (!(p.start > 0.0)) return refuse("start must be positive");
+    if (!(p.min_step > 0.0)) return refuse("min_step must be positive");
+    if (!(p.step_scale > 0.0 && p.step_scale <= 1.0)) return refuse("step_scale must lie in (0, 1]");
+    if (max_steps < 1) return refuse("max_steps must be at least 1");
+    if (refine < 0) return refuse("refine must not be negative");
+    if (n_dirs > SUPPORT_MAX_DIRS) return refuse("more than 1024 directions");
+    if (overhang_refused("sdf_mesh_support_rays", h_dirs, (long long)n_dirs, p.sin_limit, p.bed_tol)) return 2;
+    MESH_READY(m);
+    if ((long long)m->st.n_triangles >= (1ll << 31)) return refuse("2^31 or more triangles");
+    if (m->st.n_triangles > 0 && !mesh_soup(m) && !m->records) return refuse("the mesh has no soup on the device");
+    for (int k = 0; k < 4; k++) g_supports_ms[k] = 0.0;
+    for (int64_t k = 0; k < n_dirs; k++) {                             // the empty result: no launch for a mesh of 0 triangles
+        h_values[7 * k] = INFINITY; h_values[7 * k + 1] = -INFINITY;
+        for (int c = 2; c < 7; c++) h_values[7 * k + c] = 0.0;
+        for (int c = 0; c < 6; c++) h_counts[6 * k + c] = 0;
+    }
+    sdf_support_rays *res = new sdf_support_rays();
+    struct Guard { sdf_support_rays *r; ~Guard() { delete r; } } guard{res};      // (its blocks go back with it)
+    res->ctx = m->ctx;
+    res->dirs.resize((size_t)n_dirs);
+    if (m->st.n_triangles > 0) {
+        MESH_SOUP_READY(m);
+        HIPCHK(set_device(m->ctx->device));
+        if (support_rays_run(m->ctx->stream, t->d_code, t->d_c64, t->full, (const double *)mesh_soup(m), (long long)m->st.n_triangles, h_dirs,
+                             (long long)n_dirs, p, &res->dirs, h_values, h_counts, g_supports_ms)) return 1;
+    }
+    guard.r = nullptr;
+    *out = res;
+    return 0;
+}
+
+int sdf_support_rays_fetch(sdf_support_rays *r, int64_t k, int32_t *h_triangle, double *h_height, uint8_t *h_status, int32_t *h_steps,
+                           double *h_origin) {
+    if (!r) { fail("sdf_support_rays_fetch: NULL argument"); return 2; }
+    if (k < 0 || k >= (int64_t)r->dirs.size()) { fail("sdf_support_rays_fetch: no such direction"); return 2; }
+    const SupportRaysDir &d = r->dirs[(size_t)k];
+    if (d.m < 1) return 0;                                             // nothing on the device
+    sdf_ctx *c = r->ctx;
+    HIPCHK_FN(set_device(c->device));
+    const char *base = d.block.as<char>();
+    const size_t nm = (size_t)d.m;
+    if (h_origin) HIPCHK_FN(hipMemcpyAsync(h_origin, base, nm * 24, hipMemcpyDeviceToHost, c->stream));
+    if (h_height) HIPCHK_FN(hipMemcpyAsync(h_height, base + d.o_height, nm * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h_triangle) HIPCHK_FN(hipMemcpyAsync(h_triangle, base + d.o_triangle, nm * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_steps) HIPCHK_FN(hipMemcpyAsync(h_steps, base + d.o_steps, nm * 4, hipMemcpyDeviceToHost, c->stream));
+    if (h_status) HIPCHK_FN(hipMemcpyAsync(h_status, base + d.o_status, nm, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK_FN(stream_wait(c->stream));
+    return 0;
+}
+
+int sdf_support_rays_destroy(sdf_support_rays *r) {
+    if (!r) return 0;
+    (void)hipSetDevice(r->ctx->device);
+    delete r;
+    return 0;
+}
+
+double sdf_mesh_supports_last_kernel_ms(double *parts4) {
+    for (int k = 0; parts4 && k < 4; k++) parts4[k] = g_supports_ms[k];
+    return g_supports_ms[0] + g_supports_ms[1] + g_supports_ms[2] + g_supports_ms[3];
 }
 
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {

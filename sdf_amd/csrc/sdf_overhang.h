@@ -1,6 +1,7 @@
 // sdf_overhang.h -- what rates build directions on the device (sdf_overhang.hip): for a float64 soup and unit
 // directions, the extremes along each direction and the three totals and two counts of tests/overhang_ref.py, and the class of every
-// triangle for one direction.  Both follow the conventions of sdf_measure.h: synchronous on `st`, the scratch is one hooked
+// triangle for one direction.  (The unit also holds the driver and the plain kernels of the support rays, section 4o: they use these
+// kernels as they are; see sdf_supports.h.)  Both follow the conventions of sdf_measure.h: synchronous on `st`, the scratch is one hooked
 // allocation that is back when they return, and they return 0, or 1 with the message set.  *kernel_ms: their kernels alone, by HIP
 // events.  The argument checks of the C ABI (unit directions, sin_limit in [0, 1), bed_tol >= 0) are the caller's.
 #pragma once

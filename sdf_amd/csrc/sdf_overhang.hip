@@ -22,6 +22,9 @@
 // launch serves a direction and nothing a direction computes.
 //
 // k_overhang_classes: one direction, one triangle per lane, the same predicates, one byte per triangle.
+//
+// The support rays of section 4o (support_rays_run at the end of this file) take their faces from k_overhang_classes and their sums
+// through k_overhang_partials; what they add here are plain kernels -- flags, numbering, the chunk walk, the status counts.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,7 +35,9 @@
 
 #include "sdf_measure.h"
 #include "sdf_overhang.h"
+#include "sdf_prims.h"
 #include "sdf_runtime.h"
+#include "sdf_supports.h"
 
 namespace sdfk {
 
@@ -183,39 +188,41 @@ __global__ __launch_bounds__(256) void k_overhang_terms(const double *__restrict
     }
 }
 
-// grid: directions x groups of 256 partials (the group varies fastest); in[direction][n][3] -> out[direction][n_groups][3].
+// grid: directions x groups of 256 partials (the group varies fastest); in[direction][n][SUMS] -> out[direction][n_groups][SUMS]
+// (SUMS: the 3 totals of the rating, the 5 columns of the support rays below).
 // packed != NULL (the first level): the chunks' packed counts of the group are added to counts[direction][2]
+template <int SUMS>
 __global__ __launch_bounds__(256) void k_overhang_partials(const double *__restrict__ in, long long n, unsigned n_groups, double *__restrict__ out,
                                                            const unsigned *__restrict__ packed, unsigned long long *__restrict__ counts) {
-    __shared__ double tile[128 * OVERHANG_SUMS];
+    __shared__ double tile[128 * SUMS];
     __shared__ unsigned wave_cnt[2][4];
     const int tid = (int)threadIdx.x;
     const long long dir = (long long)(blockIdx.x / n_groups), g = (long long)(blockIdx.x % n_groups);
     const long long i = g * 256 + tid;
-    double acc[OVERHANG_SUMS];
+    double acc[SUMS];
 #pragma unroll
-    for (int c = 0; c < OVERHANG_SUMS; c++) acc[c] = i < n ? in[(dir * n + i) * OVERHANG_SUMS + c] : 0.0;
+    for (int c = 0; c < SUMS; c++) acc[c] = i < n ? in[(dir * n + i) * SUMS + c] : 0.0;
     for (int h = 128; h >= 64; h >>= 1) {                              // x[:h] + x[h:]: through LDS across the waves
         if (tid >= h && tid < 2 * h) {
 #pragma unroll
-            for (int c = 0; c < OVERHANG_SUMS; c++) tile[c * 128 + (tid - h)] = acc[c];
+            for (int c = 0; c < SUMS; c++) tile[c * 128 + (tid - h)] = acc[c];
         }
         __syncthreads();
         if (tid < h) {
 #pragma unroll
-            for (int c = 0; c < OVERHANG_SUMS; c++) acc[c] = acc[c] + tile[c * 128 + tid];
+            for (int c = 0; c < SUMS; c++) acc[c] = acc[c] + tile[c * 128 + tid];
         }
         __syncthreads();
     }
     if (tid < 64) {                                                    // (wave 0, whole)
         for (int h = 32; h >= 1; h >>= 1) {
 #pragma unroll
-            for (int c = 0; c < OVERHANG_SUMS; c++) acc[c] = acc[c] + __shfl_down(acc[c], h);
+            for (int c = 0; c < SUMS; c++) acc[c] = acc[c] + __shfl_down(acc[c], h);
         }
     }
     if (tid == 0) {
 #pragma unroll
-        for (int c = 0; c < OVERHANG_SUMS; c++) out[(dir * n_groups + g) * OVERHANG_SUMS + c] = acc[c];
+        for (int c = 0; c < SUMS; c++) out[(dir * n_groups + g) * SUMS + c] = acc[c];
     }
     if (packed) {                                                      // (uniform; a group's counts stay below 2^18)
         const unsigned w = i < n ? packed[dir * n + i] : 0u;
@@ -313,7 +320,7 @@ int overhang_rate(hipStream_t st, const double *d_soup, long long n_tris, const 
         bool first = true;
         for (long long n = n_chunks; first || n > 1; n = (n + 255) / 256, first = false) {             // 256 partials to one, until one is left
             const unsigned n_groups = (unsigned)((n + 255) / 256);
-            HIPCHK_MSG(who, launch_grid(k_overhang_partials, (unsigned)(nk * n_groups), st, src, n, n_groups, dst, first ? d_packed : nullptr, d_cnt));
+            HIPCHK_MSG(who, launch_grid(k_overhang_partials<OVERHANG_SUMS>, (unsigned)(nk * n_groups), st, src, n, n_groups, dst, first ? d_packed : nullptr, d_cnt));
             double *t = src; src = dst; dst = t;
         }
         HIPCHK_MSG(who, timer.stop(st));
@@ -363,6 +370,178 @@ int overhang_classes(hipStream_t st, const double *d_soup, long long n_tris, con
     HIPCHK_MSG(who, hipMemcpyAsync(h_classes, d_classes, (size_t)n_tris, hipMemcpyDeviceToHost, st));
     HIPCHK_MSG(who, stream_wait(st));
     HIPCHK_MSG(who, timer.ms(kernel_ms));
+    return 0;
+}
+
+// ---- support rays: everything of a call but the rays themselves, which are a tape interpreter and live in
+// sdf_supports.hip.  The faces are the class-1 triangles of k_overhang_classes above, numbered in triangle order by the scan of
+// sdf_prims.hip; the sums run over the RAYS in that order through the same tree as the rating's. ----
+
+// one triangle per lane: the flag the scan numbers
+__global__ __launch_bounds__(256) void k_support_flags(const unsigned char *__restrict__ classes, long long n_tris, int *__restrict__ flags) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n_tris) flags[t] = classes[t] == 1 ? 1 : 0;
+}
+
+// one triangle per lane: an overhanging one writes its index at its number
+__global__ __launch_bounds__(256) void k_support_number(const int *__restrict__ flags, const int *__restrict__ pos, long long n_tris, long long m,
+                                                        int32_t *__restrict__ triangle) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_tris || !flags[t]) return;
+    const long long r = pos[t];
+    if (r >= 0 && r < m) triangle[r] = (int32_t)t;
+}
+
+// one lane per (chunk of 1024 rays, column): ONE accumulator walks its run of the column in index order from +0.0 -- eight loads in
+// flight, then their terms IN ORDER (k_contour_area's pattern).  terms: column c at terms + c * m; partials[chunk][SUPPORT_SUMS]
+__global__ __launch_bounds__(256) void k_support_chunks(const double *__restrict__ terms, long long m, long long n_chunks, double *__restrict__ partials) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_chunks * SUPPORT_SUMS) return;
+    const long long chunk = g / SUPPORT_SUMS, col = g - chunk * SUPPORT_SUMS;
+    const double *p = terms + col * m;
+    const long long i0 = chunk * OVERHANG_CHUNK, i1 = i0 + OVERHANG_CHUNK < m ? i0 + OVERHANG_CHUNK : m;
+    double acc = 0.0;
+    long long i = i0;
+    for (; i + 8 <= i1; i += 8) {
+        double q[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) q[k] = p[i + k];
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc = acc + q[k];
+    }
+    for (; i < i1; i++) acc = acc + p[i];
+    partials[g] = acc;
+}
+
+// one ray per lane: the rays of each status, one integer atomic per workgroup and counter
+__global__ __launch_bounds__(256) void k_support_counts(const unsigned char *__restrict__ status, long long m, unsigned long long *__restrict__ counts) {
+    __shared__ unsigned wave_cnt[SUPPORT_STATUSES][4];
+    const int tid = (int)threadIdx.x;
+    const long long i = (long long)blockIdx.x * 256 + tid;
+    const int s = i < m ? (int)status[i] : -1;
+#pragma unroll
+    for (int c = 0; c < SUPPORT_STATUSES; c++) {
+        const unsigned n = (unsigned)__popcll(__ballot(s == c));
+        if ((tid & 63) == 0) wave_cnt[c][tid >> 6] = n;
+    }
+    __syncthreads();
+    if (tid < SUPPORT_STATUSES) {
+        const unsigned long long total = (unsigned long long)wave_cnt[tid][0] + wave_cnt[tid][1] + wave_cnt[tid][2] + wave_cnt[tid][3];
+        if (total) atomicAdd(counts + tid, total);
+    }
+}
+
+int support_rays_run(hipStream_t st, const uint32_t *d_code, const double *d_consts, bool full, const double *d_soup, long long n_tris,
+                     const double *h_dirs, long long n_dirs, const SupportParams &p, std::vector<SupportRaysDir> *out, double *h_values,
+                     int64_t *h_counts, double *parts_ms4) {
+    static const char who[] = "sdf_mesh_support_rays: ";
+    if (n_tris < 1 || n_tris >= (1ll << 31)) return fail(std::string(who) + "the triangle count is out of range");
+    if (n_dirs < 1 || n_dirs > SUPPORT_MAX_DIRS) return fail(std::string(who) + "the direction count is out of range");
+    const size_t nt = (size_t)n_tris;
+    const long long max_chunks = (n_tris + OVERHANG_CHUNK - 1) / OVERHANG_CHUNK, max_second = (max_chunks + 255) / 256;
+    size_t tmp_bytes = 0;
+    HIPCHK_MSG(who, scan_tmp_bytes(st, n_tris, &tmp_bytes));
+    std::vector<unsigned long long> h_ext(2 * (size_t)n_dirs), h_cnt(SUPPORT_STATUSES * (size_t)n_dirs, 0ull);
+    std::vector<double> h_sums(SUPPORT_SUMS * (size_t)n_dirs, 0.0);
+    std::deque<EventTimer> timers;
+    double *d_dir, *terms, *part_a, *part_b;
+    unsigned long long *d_ext, *d_cnt2, *d_counts;
+    unsigned char *d_classes, *tmp;
+    int *flags, *pos;
+    Scratch scratch(st);                                               // (declared after the host copies: it waits for the stream before they go)
+    scratch.part(&d_dir, 3);
+    scratch.part(&d_ext, 2);
+    scratch.part(&d_cnt2, 2);
+    scratch.part(&d_counts, SUPPORT_STATUSES);
+    scratch.part(&d_classes, nt);
+    scratch.part(&flags, nt);
+    scratch.part(&pos, nt);
+    scratch.part(&tmp, tmp_bytes);
+    scratch.part(&terms, nt * SUPPORT_SUMS);
+    scratch.part(&part_a, (size_t)max_chunks * SUPPORT_SUMS);
+    scratch.part(&part_b, (size_t)max_second * SUPPORT_SUMS);
+    HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
+    out->clear();
+    out->resize((size_t)n_dirs);
+    for (long long k = 0; k < n_dirs; k++) {
+        SupportRaysDir &res = (*out)[(size_t)k];
+        timers.emplace_back(); EventTimer &t_classes = timers.back();
+        timers.emplace_back(); EventTimer &t_number = timers.back();
+        HIPCHK_MSG(who, hipMemcpyAsync(d_dir, h_dirs + 3 * k, 24, hipMemcpyHostToDevice, st));
+        HIPCHK_MSG(who, t_classes.start(st));
+        HIPCHK_MSG(who, launch_rows(k_overhang_init, 1, st, 1, d_ext, d_cnt2));
+        HIPCHK_MSG(who, launch_grid(k_overhang_extents, extent_blocks(n_tris), st, d_soup, n_tris, d_dir, 1, 1, d_ext));
+        HIPCHK_MSG(who, launch_rows(k_overhang_classes, n_tris, st, d_soup, n_tris, d_dir, d_ext, p.sin_limit, p.bed_tol, d_classes));
+        HIPCHK_MSG(who, t_classes.stop(st));
+        HIPCHK_MSG(who, hipMemcpyAsync(h_ext.data() + 2 * k, d_ext, 16, hipMemcpyDeviceToHost, st));      // (lands behind the scan's wait)
+        HIPCHK_MSG(who, t_number.start(st));
+        HIPCHK_MSG(who, launch_rows(k_support_flags, n_tris, st, d_classes, n_tris, flags));
+        long long m = 0;
+        if (number_flags(who, "overhang flags", st, flags, pos, n_tris, tmp, tmp_bytes, &m)) return 1;
+        res.m = m;
+        if (m < 1) {
+            HIPCHK_MSG(who, t_number.stop(st));
+            continue;
+        }
+        // the direction's block: origin, height, triangle, steps, status
+        const size_t nm = (size_t)m;
+        res.o_height = align256(nm * 24);
+        res.o_triangle = res.o_height + align256(nm * 8);
+        res.o_steps = res.o_triangle + align256(nm * 4);
+        res.o_status = res.o_steps + align256(nm * 4);
+        const size_t bytes = res.o_status + align256(nm);
+        HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string(bytes) + "): ", res.block.alloc(bytes, st));
+        char *base = res.block.as<char>();
+        double *origin = (double *)base, *height = (double *)(base + res.o_height);
+        int32_t *triangle = (int32_t *)(base + res.o_triangle), *steps = (int32_t *)(base + res.o_steps);
+        uint8_t *status = (uint8_t *)(base + res.o_status);
+        HIPCHK_MSG(who, launch_rows(k_support_number, n_tris, st, flags, pos, n_tris, m, triangle));
+        HIPCHK_MSG(who, t_number.stop(st));
+        timers.emplace_back(); EventTimer &t_rays = timers.back();
+        timers.emplace_back(); EventTimer &t_sums = timers.back();
+        SupportArgs a;
+        a.dx = h_dirs[3 * k]; a.dy = h_dirs[3 * k + 1]; a.dz = h_dirs[3 * k + 2];
+        a.lo = key_value(h_ext[2 * (size_t)k]);
+        a.start = p.start; a.min_step = p.min_step; a.step_scale = p.step_scale; a.max_steps = p.max_steps; a.refine = p.refine;
+        HIPCHK_MSG(who, t_rays.start(st));
+        HIPCHK_MSG(who, (hipError_t)launch_support_rays(st, d_code, d_consts, full, d_soup, triangle, m, a, height, status, steps, origin, terms));
+        HIPCHK_MSG(who, t_rays.stop(st));
+        HIPCHK_MSG(who, t_sums.start(st));
+        const long long n_chunks = (m + OVERHANG_CHUNK - 1) / OVERHANG_CHUNK;
+        HIPCHK_MSG(who, launch_rows(k_support_chunks, n_chunks * SUPPORT_SUMS, st, terms, m, n_chunks, part_a));
+        double *src = part_a, *dst = part_b;
+        bool first = true;
+        for (long long n = n_chunks; first || n > 1; n = (n + 255) / 256, first = false) {             // 256 partials to one, until one is left
+            const unsigned n_groups = (unsigned)((n + 255) / 256);
+            HIPCHK_MSG(who, launch_grid(k_overhang_partials<SUPPORT_SUMS>, n_groups, st, src, n, n_groups, dst, nullptr, nullptr));
+            double *t = src; src = dst; dst = t;
+        }
+        HIPCHK_MSG(who, hipMemsetAsync(d_counts, 0, SUPPORT_STATUSES * 8, st));
+        HIPCHK_MSG(who, launch_rows(k_support_counts, m, st, status, m, d_counts));
+        HIPCHK_MSG(who, t_sums.stop(st));
+        HIPCHK_MSG(who, hipMemcpyAsync(h_sums.data() + SUPPORT_SUMS * k, src, SUPPORT_SUMS * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK_MSG(who, hipMemcpyAsync(h_cnt.data() + SUPPORT_STATUSES * k, d_counts, SUPPORT_STATUSES * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK_MSG(who, stream_wait(st));
+    for (int c = 0; c < 4; c++) parts_ms4[c] = 0.0;
+    {
+        size_t ti = 0;
+        for (long long k = 0; k < n_dirs; k++) {
+            const int n = (*out)[(size_t)k].m > 0 ? 4 : 2;
+            for (int c = 0; c < n; c++, ti++) {
+                double ms = 0.0;
+                HIPCHK_MSG(who, timers[ti].ms(&ms));
+                parts_ms4[c] += ms;
+            }
+        }
+    }
+    for (long long k = 0; k < n_dirs; k++) {
+        h_values[7 * k] = key_value(h_ext[2 * k]);
+        h_values[7 * k + 1] = key_value(h_ext[2 * k + 1]);
+        for (int c = 0; c < SUPPORT_SUMS; c++) h_values[7 * k + 2 + c] = h_sums[SUPPORT_SUMS * k + c];
+        for (int c = 0; c < SUPPORT_STATUSES; c++) h_counts[6 * k + c] = (int64_t)h_cnt[SUPPORT_STATUSES * k + c];
+        h_counts[6 * k + 5] = (int64_t)(*out)[(size_t)k].m;
+    }
     return 0;
 }
 

@@ -84,6 +84,10 @@ class SDF3(SDFBase):
         from .overhang import overhangs
         return overhangs(self, *args, **kwargs)
 
+    def supports(self, *args, **kwargs):
+        from .supports import supports
+        return supports(self, *args, **kwargs)
+
     def shells(self, **kwargs):
         from .shells import shells
         return shells(self, **kwargs)

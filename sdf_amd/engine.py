@@ -212,6 +212,11 @@ ABI = {
                                           ctypes.POINTER(_c_i64)]),
     'sdf_mesh_overhang_classes': (ctypes.c_int, [_vp, _f64p, ctypes.c_double, ctypes.c_double, _u8p]),
     'sdf_overhang_last_kernel_ms': (ctypes.c_double, [ctypes.POINTER(_c_i64)]),
+    'sdf_mesh_support_rays': (ctypes.c_int, [_vp, _vp, _f64p, _c_i64, _f64p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), _f64p,
+                                             ctypes.POINTER(_c_i64)]),
+    'sdf_support_rays_fetch': (ctypes.c_int, [_vp, _c_i64, ctypes.POINTER(ctypes.c_int32), _f64p, _u8p, ctypes.POINTER(ctypes.c_int32), _f64p]),
+    'sdf_support_rays_destroy': (ctypes.c_int, [_vp]),
+    'sdf_mesh_supports_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
@@ -682,6 +687,47 @@ class Mesh:
         out = np.zeros(max(self.n_triangles, 1), np.uint8)
         _check(eng.lib, eng.lib.sdf_mesh_overhang_classes(self.handle, _dp(d, _f64p), float(sin_limit), float(bed_tol), _dp(out, _u8p)))
         return out[:self.n_triangles]
+
+    def support_rays(self, sdf_or_tape, directions, sin_limit, bed_tol, start, min_step, step_scale=1.0, max_steps=256, refine=16):
+        """support rays traced through the field of a model on the device (sdf_mesh_support_rays, csrc/sdf_supports.hip and
+        csrc/sdf_overhang.hip; DESIGN.md section 4o; defined by tests/supports_ref.py::supports and reproduced bit for bit): for UNIT
+        directions (K, 3), a dict of `lo`, `hi` (K,), `sums` (K, 5), `counts` (K, 5) int64 -- rays that ended BED, PART, BURIED,
+        UNRESOLVED, NAN -- and `rays`, a list of K tuples (triangle (M,) int32, height (M,) float64, status (M,) uint8, steps (M,)
+        int32, origin (M, 3) float64).  `supports.derive` turns the sums into volumes and areas.  Needs no weld.  A model with user
+        closures takes the same definition over `Engine.eval_points` on the host.  ValueError, before any device work, for what the C
+        entry refuses and for an engine in float32 precision."""
+        from .supports import check_params, support_rays_host
+        eng = self.engine
+        d, params = check_params(directions, sin_limit, bed_tol, start, min_step, step_scale, max_steps, refine)
+        if eng.precision != PRECISION_F64:
+            raise ValueError('support_rays marches in float64 only; this engine is set to float32 precision')
+        dt = eng.tape_for(sdf_or_tape)
+        k = len(d)
+        if dt.tape.externs:
+            soup = self.points().reshape(-1, 3, 3)
+            got = [support_rays_host(lambda P: eng.eval_points(dt, P), soup, d[i], *params) for i in range(k)]
+            return {'lo': np.array([g['lo'] for g in got]), 'hi': np.array([g['hi'] for g in got]),
+                    'sums': np.array([g['sums'] for g in got]).reshape(k, 5), 'counts': np.array([g['counts'] for g in got], np.int64).reshape(k, 5),
+                    'rays': [(g['triangle'], g['height'], g['status'], g['steps'], g['origin']) for g in got]}
+        values, counts = np.empty((k, 7), np.float64), np.empty((k, 6), np.int64)
+        p8 = np.array(params[:5] + [0.0, 0.0, 0.0], np.float64)
+        h = _vp()
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        _check(eng.lib, eng.lib.sdf_mesh_support_rays(self.handle, dt.handle, _dp(d, _f64p), k, _dp(p8, _f64p), params[5], params[6],
+                                                      ctypes.byref(h), _dp(values, _f64p), _dp(counts, ctypes.POINTER(_c_i64))))
+        try:
+            rays = []
+            for i in range(k):
+                m = int(counts[i, 5])
+                tri, height, status = np.empty(m, np.int32), np.empty(m, np.float64), np.empty(m, np.uint8)
+                steps, origin = np.empty(m, np.int32), np.empty((m, 3), np.float64)
+                if m:
+                    _check(eng.lib, eng.lib.sdf_support_rays_fetch(h, i, _dp(tri, i32p), _dp(height, _f64p), _dp(status, _u8p), _dp(steps, i32p),
+                                                                   _dp(origin, _f64p)))
+                rays.append((tri, height, status, steps, origin))
+        finally:
+            eng.lib.sdf_support_rays_destroy(h)
+        return {'lo': values[:, 0].copy(), 'hi': values[:, 1].copy(), 'sums': values[:, 2:7].copy(), 'counts': counts[:, :5].copy(), 'rays': rays}
 
     def stl_records(self):
         """T x 50-byte binary STL records (normals computed on the device)"""

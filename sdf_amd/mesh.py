@@ -121,6 +121,19 @@ class Mesh:
         from .overhang import overhangs_soup
         return overhangs_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], directions, angle, bed_tolerance, classes)
 
+    def supports(self, f, directions=(0.0, 0.0, 1.0), step=None, angle=45.0, bed_tolerance=None, start=None, min_step=None, step_scale=1.0,
+                 max_steps=256, refine=16, top=8):
+        """the support rays of this mesh traced in the field `f` on the device (sdf_amd/supports.py): a
+        `Supports`.  A file has no sampling grid, so `step` must be given (start = min_step = a quarter of it), or start and min_step
+        themselves, and bed_tolerance=None is 0.0"""
+        from .supports import supports_soup
+        if step is not None:
+            quarter = float(np.min(np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)))) / 4
+            start = quarter if start is None else start
+            min_step = quarter if min_step is None else min_step
+        return supports_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], f, directions, angle,
+                             0.0 if bed_tolerance is None else bed_tolerance, start, min_step, step_scale, max_steps, refine, top)
+
     def shells(self):
         """the connected shells of this mesh (sdf_amd/shells.py `Shells`), labelled on the device.  The soup is welded there again:
         `vertex_shell` is over THAT weld's vertices (lexicographic order), `triangle_shell` over this mesh's triangles"""

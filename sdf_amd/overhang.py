@@ -6,7 +6,8 @@ area that lies on the bed, and the height.  Nothing crosses the link but a few n
 definition; `normalise`, `sin_limit_of` and `derive` restate its few lines of host arithmetic.
 
 support_volume is a PROXY: the prism from every overhanging face straight down to the bed plane.  It does not subtract the part's
-own material under an overhang, and in a soup of overlapping solids it counts the faces hidden inside the union.
+own material under an overhang, and in a soup of overlapping solids it counts the faces hidden inside the union.  `supports`
+(sdf_amd/supports.py, section 4o) traces rays from the overhanging faces down to the part for the directions this rating puts first.
 
 To use a result: `f.rotate_to(o.directions[o.best()], Z)` -- or `o.rotation(o.best())` for a mesh."""
 import collections
