@@ -120,6 +120,10 @@ int sdf_tape_create(sdf_ctx *ctx, const uint32_t *code, uint32_t n_words, const 
  * With it, sdf_generate runs an interval prepass per surviving batch and skips the instructions
  * that provably cannot influence any sample of that batch (results are unchanged bit for bit). */
 int sdf_tape_set_prune_info(sdf_tape *tape, const uint16_t *rstart, const uint16_t *lstart, uint32_t n_instr);
+/* 0: sdf_generate runs no interval pass for this tape (neither the instruction pruning nor the cell-group culling).
+ * sdf_amd/tape.py asks for that when a constant of the tape is NaN or infinite or makes a divisor of an op zero: such a
+ * model is NaN at every sample, which an interval cannot say once a clip or a min / max with a finite operand follows. */
+int sdf_tape_set_intervals(sdf_tape *tape, int enabled);
 int sdf_tape_destroy(sdf_tape *tape);
 
 /* f(P) for N points of dimension dim (2 or 3): replaces SDF3.__call__ / SDF2.__call__

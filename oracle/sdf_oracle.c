@@ -765,12 +765,15 @@ oracle_result *sdf_oracle_generate(const int32_t *nodes, const double *params, c
             vol[((int64_t)i * ly + j) * lz + k] = (float)eval_node(&t, root, p);
         }
         R->n_eval += (int64_t)lx * ly * lz;
-        /* skimage: "Surface level must be within volume data range" -> ValueError -> empty */
+        /* skimage: "Surface level must be within volume data range" -> ValueError -> empty.  volume.min() / .max() of a
+         * volume that holds a NaN are NaN and both comparisons false: such a volume is marched (a NaN sample counts as
+         * inside, the vertices next to it get a NaN coordinate) */
         int64_t namb = 0, k = 0;
         {
             float mn = INFINITY, mx = -INFINITY;
-            for (int64_t i = 0; i < (int64_t)lx * ly * lz; i++) { if (vol[i] < mn) mn = vol[i]; if (vol[i] > mx) mx = vol[i]; }
-            if (lx >= 2 && ly >= 2 && lz >= 2 && !(0.0f < mn) && !(0.0f > mx))
+            int has_nan = 0;
+            for (int64_t i = 0; i < (int64_t)lx * ly * lz; i++) { if (vol[i] < mn) mn = vol[i]; if (vol[i] > mx) mx = vol[i]; if (vol[i] != vol[i]) has_nan = 1; }
+            if (lx >= 2 && ly >= 2 && lz >= 2 && (has_nan || (!(0.0f < mn) && !(0.0f > mx))))
                 k = sdf_oracle_marching_cubes(vol, lx, ly, lz, loc, (int64_t)12 * batch * batch * batch, &namb);
         }
         R->n_ambiguous += namb;

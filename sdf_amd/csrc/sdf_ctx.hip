@@ -290,6 +290,12 @@ int sdf_tape_set_prune_info(sdf_tape *t, const uint16_t *rstart, const uint16_t 
     return 0;
 }
 
+int sdf_tape_set_intervals(sdf_tape *t, int enabled) {
+    if (!t) return fail("sdf_tape_set_intervals: tape is NULL");
+    t->ia_off = !enabled;
+    return 0;
+}
+
 int sdf_tape_destroy(sdf_tape *t) {
     if (!t) return 0;
     (void)hipSetDevice(t->ctx->device);

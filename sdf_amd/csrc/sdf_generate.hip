@@ -410,7 +410,8 @@ int generate_impl(sdf_mesh *m, const GenCall &call) {
         return up || down;
     };
     s.n_instr = t->n_words / 2;
-    const bool intervals_ok = call.precision == SDF_PRECISION_F64 && monotone(call.X, nx) && monotone(call.Y, ny) && monotone(call.Z, nz);
+    // (t->ia_off: a tape whose constants make the model NaN -- the interval forms keep no NaN through a later clip or min / max)
+    const bool intervals_ok = call.precision == SDF_PRECISION_F64 && !t->ia_off && monotone(call.X, nx) && monotone(call.Y, ny) && monotone(call.Z, nz);
     s.pruning = c->prune && t->d_rstart && s.n_instr <= 256 && intervals_ok && t->n_consts < 0xFFFFF0u;
     // 64-bit words per batch tape: the instructions, one more END, the length; whole 64-byte lines
     const int tape_stride = s.pruning ? (int)((s.n_instr + 2 + 7) & ~7u) : 0;

@@ -84,6 +84,7 @@ struct sdf_tape {
     uint16_t *d_rstart = nullptr, *d_lstart = nullptr;   // operand ranges of the prunable combines (or NULL)
     bool ia_complete = false;                            // every op has an interval form (sdf_interval.h ia_has_form)
     bool ia_rare = false;                                // ... one of them a leaf of ia_leaf_rare (the k_cull variant that knows them)
+    bool ia_off = false;                                 // the lowering found that the model can be NaN everywhere: no interval pass (sdf_tape_set_intervals)
     uint32_t n_extern = 0;                               // user closures the tape reads through L_EXTERN leaves (sdf_eval_points_extern_*)
     unsigned long long hint_key = 0, hint_total_tris = 0;   // arena sizing: last call of this tape
     unsigned long long content_hash = 0;                    // FNV-1a of the code words and the constants' bits: what identifies the MODEL,

@@ -27,7 +27,13 @@
 // STRICTLY on the losing side of the other's, in which case min / max returns the other operand bit for
 // bit; an operand of a smooth one only in its exact direction (ia_decide).  Anything that could be NaN, and
 // the few ops without an interval form (non-monotone easings), yields the whole real
-// line, which never licenses a skip.  The parity tests (bit-identical soups against the CPU checker and the
+// line, which never licenses a skip.  That holds for a NaN that ARISES in a run (inf - inf, 0 * inf at some box); it does not
+// survive what follows it: a bound that came out as NaN is "no bound", and a later clip, max(., 0) or hard min / max against
+// a finite sibling makes the interval finite again, while the interpreter's np.minimum / np.maximum / np.clip hand the NaN on.
+// A model that is NaN because of its CONSTANTS (a NaN, infinite or extreme parameter, end points that coincide, a zero scale
+// factor: capsule(Z, Z, .5) | sphere(.5) is NaN everywhere, its interval was the sphere's) is therefore kept away from this file
+// altogether: sdf_amd/tape.py lower() marks its tape, sdf_tape_set_intervals(tape, 0), and sdf_generate runs neither interval
+// pass for it (tests/test_params_host.py, tests/test_params_gpu.py: param_cases.NAN_MODELS).  The parity tests (bit-identical soups against the CPU checker and the
 // reference goldens, random CSG / array / leaf sweeps with the passes on and off) run with the prepass
 // active; tests/test_interval_host.py checks the enclosure property of the primitives on the CPU.
 #pragma once

@@ -120,6 +120,7 @@ ABI = {
                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
     'sdf_tape_set_prune_info': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint16),
                                                ctypes.c_uint32]),
+    'sdf_tape_set_intervals': (ctypes.c_int, [_vp, ctypes.c_int]),
     'sdf_tape_destroy': (ctypes.c_int, [_vp]),
     'sdf_eval_points': (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.c_int, _vp, ctypes.c_int]),
     'sdf_eval_points_host': (ctypes.c_int, [_vp, _f64p, _c_i64, ctypes.c_int, _f64p, ctypes.c_int]),
@@ -352,6 +353,8 @@ class DeviceTape:
             u16p = ctypes.POINTER(ctypes.c_uint16)
             _check(lib, lib.sdf_tape_set_prune_info(self.handle, _dp(tape.rstart, u16p), _dp(tape.lstart, u16p),
                                                     tape.n_instr))
+        if not getattr(tape, 'intervals', True):      # (a model that is NaN everywhere, sdf_amd/tape.py: no interval pass at all)
+            _check(lib, lib.sdf_tape_set_intervals(self.handle, 0))
 
 
 class _PinnedBlock:

@@ -98,6 +98,33 @@ _BOOL_POST = {
     'intersection': ('INTER', 'SINTER'), 'blend': (None, 'BLEND'),
 }
 
+# Parameters an op of the interpreter DIVIDES by (csrc/sdf_interp.h), as indices into the node's params: dot(b - a, b - a) of
+# the segment ops, r1 - r0 of the radial ones, the scale factors, the ellipsoid's sizes and their squares, the height of
+# extrude_to.  With one of them zero the op computes 0 / 0 or inf * 0: the model is NaN, at every sample or on a surface.
+_DIVISORS = {
+    'capsule': (6,), 'capped_cylinder': (6,), 'capped_cone': (8, 10), 'ellipsoid': (0, 1, 2, 3, 4, 5),
+    'bend_linear': (6,), 'transition_linear': (6,), 'bend_radial': (1,), 'transition_radial': (1,),
+    'scale': (0, 1, 2), 'scale2': (0, 1), 'extrude_to': (0,),
+}
+
+
+def _tame(c):
+    """a constant that is finite and whose square neither overflows nor, unless it is zero, underflows to zero: one
+    multiplication or division by anything else can turn a finite coordinate into inf or 0, and the next op into NaN
+    (twist(1e300) at z = 1e9: sin(inf))"""
+    return math.isfinite(c) and (c == 0 or 0 < c * c < math.inf)
+
+
+def _zero_divisor(n):
+    """True when a parameter of node n makes a divisor of its op zero (see _DIVISORS; a polygon divides by the squared
+    length of every edge, the closing one included)"""
+    if n.op == 'polygon':
+        k = int(n.params[0])
+        xy = [(n.params[1 + 2 * i], n.params[2 + 2 * i]) for i in range(k)]
+        return any(xy[i] == xy[i - 1] for i in range(k))
+    return any(n.params[i] == 0 for i in _DIVISORS.get(n.op, ()))
+
+
 # rough per-sample arithmetic weights (adds/muls/compares = 1, fma = 2; sqrt/div/trig listed
 # separately) used only for the VALU-side figure bench.py prints (SURVEY.md 8d)
 _FLOPS = {
@@ -120,6 +147,8 @@ class Tape:
         self.n_dslots = n_dslots
         self.dim = dim
         self.rstart = self.lstart = None
+        # False: the model can be NaN wherever it is evaluated (see lower()); the library then runs no interval pass for it
+        self.intervals = True
         # user closures the tape reads through its L_EXTERN leaves: [(callable, dimension of its points)],
         # leaf k of the tape = entry k
         self.externs = []
@@ -179,12 +208,15 @@ class _Lowering:
         self.meta = []
         self.chain = []               # stack: index of the first instruction of the enclosing chain
         self.externs = []             # user closures, in leaf order
+        self.intervals = True         # no NaN / infinite constant and no zero divisor seen (lower())
 
     # -- emission helpers --
     def emit(self, op, post='SET', a=0, b=0, consts=(), K=0.0, blob=None):
         off = len(self.consts)
         self.consts.append(float(K))
         self.consts.extend(float(c) for c in consts)
+        if not all(_tame(c) for c in self.consts[off:]) or (K == 0 and POST[post] >= POST['SUNION']):
+            self.intervals = False    # (a smooth combine divides by K)
         if blob is not None:          # bulk constants (a sampled field) behind the parameters
             self.consts.frombytes(np.ascontiguousarray(blob, dtype=np.float64).tobytes())
         assert 0 <= a < 256 and 0 <= b < 256
@@ -272,6 +304,8 @@ class _Lowering:
             self.dfree()
             return dirty
         op = n.op
+        if _zero_divisor(n):
+            self.intervals = False
         if n.dim and n.dim != dim:
             raise TypeError('%s is a %d-D node used on %d-D points' % (op, n.dim, dim))
         leaf = 'L_' + op.upper()
@@ -597,7 +631,14 @@ def lower(obj, dim=None):
     # prunable combine) -- input of the interval prepass
     # (the prepass handles tapes of up to PRUNE_MAX_INSTR instructions; longer ones carry no ranges and run unpruned)
     t.externs = list(lw.externs)
-    if t.n_instr <= PRUNE_MAX_INSTR and not t.externs:
+    # A NaN must reach the end of an interval run as the whole line, and the interval forms cannot promise that: a bound
+    # that came out as NaN becomes "no bound", and a later clip, max(., 0) or hard min / max against a finite sibling makes
+    # the interval finite again although every value is NaN (np.minimum / np.maximum / np.clip propagate it).  Where that
+    # can happen is known here: a NaN, infinite or extreme constant (_tame), or a constant that makes a divisor of its op
+    # zero.  Such a tape carries no operand ranges and is marked so that the library runs neither interval pass (pruning,
+    # culling) for it -- what it does for an op without an interval form; a well-formed model is lowered exactly as before.
+    t.intervals = lw.intervals
+    if t.n_instr <= PRUNE_MAX_INSTR and not t.externs and t.intervals:
         t.rstart = np.array([0xFFFF if m is None else m[0] for m in meta], dtype=np.uint16)
         t.lstart = np.array([0xFFFF if m is None else m[1] for m in meta], dtype=np.uint16)
     return t
