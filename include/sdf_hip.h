@@ -494,6 +494,33 @@ int sdf_mesh_simplify(sdf_mesh *mesh, const double *origin3, const double *cell3
 /* the kernels of this thread's last sdf_mesh_simplify, milliseconds by HIP events; parts4 (or NULL): keys and numbering, the item
  * sort and its segments, k_cluster_vertex, live flags and emission (tools/simplify_time.py) */
 double sdf_mesh_simplify_last_kernel_ms(double *parts4);
+/* The mesh simplified to a tolerance (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4p,
+ * defined by tests/adaptive_ref.py and reproduced bit for bit): octree vertex clustering with the quadric above as the error
+ * measure.  Level L = 0 .. levels is sdf_mesh_simplify's clustering on the grid (origin3, cell3 x 2^L).  The error of a cluster is
+ * the sum, over the (triangle, corner) items that touch it, of the squared residual of its representative in the triangle's plane
+ * (normal of twice-the-area length); the cluster is accepted if err <= tolerance^2 x w, w the trace of its quadric -- the
+ * squared-area-weighted mean squared distance of the representative from those planes against tolerance^2; it is not a Hausdorff
+ * bound.  Level 0 is always accepted, and every cluster is when tolerance^2 is +inf.  Every welded vertex takes the coarsest level
+ * whose cluster is accepted, that cluster's representative as its position and (level, cluster) as its id; a triangle survives if
+ * its three ids differ, in order and winding.  levels = 0 is sdf_mesh_simplify bit for bit, and so is tolerance = +inf on the
+ * cell x 2^levels.  clusters_used[L], vertices[L]: the clusters of level L that a vertex chose, and those vertices; mean_fallback
+ * and flat count the used clusters.  Every float sum is sequential in the definition's order.  One scratch allocation, reused across
+ * the levels and freed before the call returns; the new mesh OWNS its soup, like sdf_mesh_simplify's.  A mesh of 0 triangles gives a
+ * mesh of 0 triangles without a launch.  Refused on the host with return value 2: what sdf_mesh_simplify refuses, a tolerance that
+ * is negative or NaN, levels outside 0 .. SDF_ADAPTIVE_MAX_LEVELS, a cell3 x 2^levels that is not finite.  Found on the device with
+ * return value 1 and nothing left allocated: a vertex that is not finite, clusters of a level that span 2^21 or more cells on an
+ * axis.  *out is written on success only. */
+#define SDF_ADAPTIVE_MAX_LEVELS 10
+typedef struct sdf_adaptive_stats {
+    int64_t triangles_in, triangles_out, collapsed, levels, mean_fallback, flat;
+    int64_t clusters_used[SDF_ADAPTIVE_MAX_LEVELS + 1], vertices[SDF_ADAPTIVE_MAX_LEVELS + 1];
+    double kernel_ms;
+} sdf_adaptive_stats;
+int sdf_mesh_simplify_adaptive(sdf_mesh *mesh, const double *origin3, const double *cell3, double reg, double tolerance, int levels,
+                               sdf_mesh **out, sdf_adaptive_stats *stats);
+/* the kernels of this thread's last sdf_mesh_simplify_adaptive, milliseconds by HIP events: their sum (the levels and the emission);
+ * ms (or NULL): levels + 1 values, one per level (tools/adaptive_time.py) */
+double sdf_mesh_simplify_adaptive_last_kernel_ms(double *ms);
 /* The mesh mended on the device (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4k, defined
  * by tests/mend_ref.py and reproduced exactly): duplicate triangles are dropped and oppositely wound pairs cancel -- what
  * sdf_mesh_simplify leaves behind where two sheets of a surface fall into the same clusters.  A cell of the weld with two equal

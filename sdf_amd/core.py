@@ -159,7 +159,8 @@ def grid_axes(bounds, step=None, samples=SAMPLES):
 Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', 'bounds', 'stats', 'simplify_stats'), defaults=(None,))
 Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=, the simplified mesh under
 simplify=, the mended mesh under mend=True -- its statistics ride on it: `mesh.mend_stats`), or None when a multi-process run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape,
-engine, bounds, stats: the call's; simplify_stats: the dict of `engine.Mesh.simplify`, or None without simplify=."""
+engine, bounds, stats: the call's; simplify_stats: the dict of `engine.Mesh.simplify` -- of `engine.Mesh.simplify_adaptive` under
+simplify_tolerance= --, or None without either."""
 
 
 @contextlib.contextmanager
@@ -167,12 +168,15 @@ def meshed(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False):
+        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False, simplify_tolerance=None, simplify_levels=5):
     """the one path from a model to its mesh on the device: the arguments of `generate`, `keep` (only these
     connected shells, `shells.resolve_keep`: the device mesh is labelled, the kept shells are compacted into a mesh of their own
     and THAT is yielded; section 4h), `simplify` (a real number k > 0, `simplify.check_simplify`: after keep, the mesh is simplified on
     the device in clusters of k^3 grid cells, `engine.Mesh.simplify`, and the simplified mesh is what is yielded and what the closing
-    line counts; section 4j), `mend` (False or True, `mend.check_mend`: after keep and after simplify -- simplifying is what makes the
+    line counts; section 4j), `simplify_tolerance` and `simplify_levels` (a real number >= 0 in model units and an integer 0 .. 10,
+    `simplify.check_adaptive`: in the place of the uniform clustering the mesh is simplified to that tolerance on the levels of
+    simplify x 2^L grid cells, L = 0 .. simplify_levels, `engine.Mesh.simplify_adaptive`; simplify is then the finest cluster and
+    defaults to 1; section 4p), `mend` (False or True, `mend.check_mend`: after keep and after simplify -- simplifying is what makes the
     pairs -- duplicate triangles are dropped and oppositely wound pairs cancel on the device, `engine.Mesh.mend`, and the mended mesh
     is what is yielded and what the closing line counts; section 4k) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
     16-byte records).  Yields a `Meshed`, which the readers below take; closes what it opened on the way out, and after a body
@@ -181,9 +185,8 @@ def meshed(
     if keep is not None:
         from .shells import check_keep, resolve_keep, shells_of_mesh
         check_keep(keep)      # (before anything is meshed)
-    if simplify is not None:
-        from .simplify import check_simplify, resolve_cell
-        check_simplify(simplify)
+    from .simplify import check_adaptive, resolve_cell
+    simplify, simplify_tolerance, simplify_levels = check_adaptive(simplify, simplify_tolerance, simplify_levels)      # (before anything is meshed)
     from .mend import check_mend
     mend = check_mend(mend)      # (before the engine is asked for)
     start = time.time()
@@ -235,7 +238,8 @@ def meshed(
             if mesh is None:
                 raise NotImplementedError('simplify: the soup of this multi-process run was gathered on the host; a mesh is simplified on '
                                           'the device only (run it in one process, or with a device-resident exchange)')
-            small = mesh.simplify(*resolve_cell(simplify, X, Y, Z, (dx, dy, dz)))
+            origin, cell = resolve_cell(simplify, X, Y, Z, (dx, dy, dz))
+            small = mesh.simplify(origin, cell) if simplify_tolerance is None else mesh.simplify_adaptive(origin, cell, simplify_tolerance, simplify_levels)
             mesh.close()
             mesh = small
             simplify_stats = small.simplify_stats
@@ -257,6 +261,13 @@ def meshed(
         seconds = time.time() - start
         print('%d triangles in %g seconds' % (triangles, seconds))
     generate.last_stats = stats
+
+
+def _tolerance_kwargs(simplify_tolerance, simplify_levels):
+    """what a reader passes on to `meshed` for its two keywords: nothing when they are the defaults (the call without them)"""
+    if simplify_tolerance is None and isinstance(simplify_levels, int) and not isinstance(simplify_levels, bool) and simplify_levels == 5:
+        return {}
+    return {'simplify_tolerance': simplify_tolerance, 'simplify_levels': simplify_levels}
 
 
 @contextlib.contextmanager
@@ -346,7 +357,8 @@ def generate(
 generate.last_stats = None
 
 
-def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None, mend=False, **generate_kwargs):
+def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5,
+                  **generate_kwargs):
     """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
     welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
     difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
@@ -359,6 +371,7 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
     statistics of the last call that mended).  Not in the reference."""
     if simplify is not None:      # (simplify=None is the call without the argument)
         generate_kwargs['simplify'] = simplify
+    generate_kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:         # (mend=False is the call without the argument)
         generate_kwargs['mend'] = mend
     with meshed(sdf, keep=keep, **generate_kwargs) as m:
@@ -375,7 +388,8 @@ generate_mesh.last_simplify = None
 generate_mesh.last_mend = None
 
 
-def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False, **kwargs):
+def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False,
+         simplify_tolerance=None, simplify_levels=5, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
@@ -394,6 +408,7 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     ply = path.lower().endswith('.ply')
     if simplify is not None:      # (simplify=None is the call without the argument)
         kwargs['simplify'] = simplify
+    kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:         # (mend=False is the call without the argument)
         kwargs['mend'] = mend
     if thickness:                 # (refused before anything is meshed, like the extension above)

@@ -44,7 +44,7 @@
 //   k_edt_*                       the exact Euclidean distance transform of `text` / `image` (sdf_edt.hip)
 //   k_soup_* / k_moment_partials / k_edge_*   volume, area, inertia and the edge census of a mesh (sdf_measure.hip)
 //   k_shell_* / k_keep_flags / k_select_copy   the connected shells of a mesh and their selection (sdf_components.hip)
-//   k_cluster_* / k_item_starts   a mesh simplified by vertex clustering with quadric vertices (sdf_simplify.hip)
+//   k_cluster_* / k_item_starts / k_adaptive_*   a mesh simplified by vertex clustering with quadric vertices, on one grid or to a tolerance (sdf_simplify.hip)
 //   k_mend_*                      a mesh mended: duplicate triangles dropped, opposite pairs cancelled (sdf_mend.hip)
 #include <hip/hip_runtime.h>
 

@@ -552,6 +552,57 @@ double sdf_mesh_simplify_last_kernel_ms(double *parts4) {
     return g_simplify_kernel_ms[0] + g_simplify_kernel_ms[1] + g_simplify_kernel_ms[2] + g_simplify_kernel_ms[3];
 }
 
+// ---- the mesh simplified to a tolerance: the same clustering on the levels cell x 2^L, the coarsest accepted cluster per vertex ----
+static thread_local double g_adaptive_kernel_ms[SDF_ADAPTIVE_MAX_LEVELS + 2] = {};     // the levels, then the emission
+static thread_local int g_adaptive_levels = -1;
+
+int sdf_mesh_simplify_adaptive(sdf_mesh *m, const double *origin3, const double *cell3, double reg, double tolerance, int levels,
+                               sdf_mesh **out, sdf_adaptive_stats *stats) {
+    if (!m || !origin3 || !cell3 || !out || !stats) { fail("sdf_mesh_simplify_adaptive: NULL argument"); return 2; }
+    if (levels < 0 || levels > SDF_ADAPTIVE_MAX_LEVELS) { fail("sdf_mesh_simplify_adaptive: levels must lie in 0 .. 10"); return 2; }
+    if (!(tolerance >= 0.0)) { fail("sdf_mesh_simplify_adaptive: tolerance must not be negative or NaN"); return 2; }
+    for (int k = 0; k < 3; k++) {
+        if (!(std::isfinite(cell3[k]) && cell3[k] > 0.0)) { fail("sdf_mesh_simplify_adaptive: cell must be positive and finite"); return 2; }
+        if (!std::isfinite(cell3[k] * (double)(1 << levels))) { fail("sdf_mesh_simplify_adaptive: cell x 2^levels must be finite"); return 2; }
+        if (!std::isfinite(origin3[k])) { fail("sdf_mesh_simplify_adaptive: origin must be finite"); return 2; }
+    }
+    if (!(std::isfinite(reg) && reg >= 0.0)) { fail("sdf_mesh_simplify_adaptive: reg must be finite and not negative"); return 2; }
+    MESH_READY(m);
+    const long long nt = (long long)m->st.n_triangles;
+    if (3 * nt >= (1ll << 31)) { fail("sdf_mesh_simplify_adaptive: 2^31 or more corners or vertices"); return 2; }
+    *stats = sdf_adaptive_stats();
+    stats->levels = levels;
+    DevBuf soup;                                                       // the survivors' own soup: the new mesh's `out`
+    if (nt > 0) {                                                      // (no triangles: a mesh of 0 triangles, no launch)
+        int64_t nu = 0;
+        if (sdf_mesh_weld(m, &nu)) return 1;
+        HIPCHK(set_device(m->ctx->device));
+        for (double &ms : g_adaptive_kernel_ms) ms = 0.0;
+        g_adaptive_levels = levels;
+        if (simplify_adaptive_device(m->ctx->stream, m->weld_pts.as<double>(), m->weld_inv.as<long long>(), m->weld_n, nt, origin3, cell3, reg,
+                                     tolerance, levels, &soup, stats, g_adaptive_kernel_ms, &g_adaptive_kernel_ms[levels + 1])) {
+            soup.release();
+            *stats = sdf_adaptive_stats();
+            return 1;
+        }
+    }
+    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
+    s->ctx = m->ctx;
+    s->out = soup;
+    s->st.n_triangles = stats->triangles_out;
+    *out = s;
+    return 0;
+}
+
+double sdf_mesh_simplify_adaptive_last_kernel_ms(double *ms) {
+    double total = 0.0;
+    for (int k = 0; k <= g_adaptive_levels + 1; k++) {
+        if (ms && k <= g_adaptive_levels) ms[k] = g_adaptive_kernel_ms[k];
+        total += g_adaptive_kernel_ms[k];
+    }
+    return total;
+}
+
 // ---- the mesh mended: duplicate triangles dropped, oppositely wound pairs cancelled, the survivors as a mesh of its own ----
 static thread_local double g_mend_kernel_ms[3] = {0.0, 0.0, 0.0};
 

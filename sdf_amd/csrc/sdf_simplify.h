@@ -14,4 +14,11 @@ namespace sdfk {
 // k_cluster_vertex, live flags and emission, by HIP events; stats->kernel_ms is their sum.
 int simplify_device(hipStream_t st, const double *d_points, const long long *d_cells, long long n_vertices, long long n_tris,
                     const double *origin, const double *cell, double reg, DevBuf *out, sdf_simplify_stats *stats, double kernel_ms[4]);
+// The same mesh simplified to a tolerance: the levels 0 .. levels (<= SDF_ADAPTIVE_MAX_LEVELS) of cell x 2^L,
+// every one finite, from the coarsest down in one scratch; tolerance >= 0, +inf allowed.  level_ms[0 .. levels]: the kernels of
+// every level, *emit_ms: live flags and emission, by HIP events; stats->kernel_ms is their sum.  Fails like simplify_device, before
+// anything is written to `out`.
+int simplify_adaptive_device(hipStream_t st, const double *d_points, const long long *d_cells, long long n_vertices, long long n_tris,
+                             const double *origin, const double *cell, double reg, double tolerance, int levels, DevBuf *out,
+                             sdf_adaptive_stats *stats, double *level_ms, double *emit_ms);
 }

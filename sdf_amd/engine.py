@@ -67,6 +67,16 @@ class SdfSimplifyStats(ctypes.Structure):
     _fields_ = [(k, _c_i64) for k in SIMPLIFY_FIELDS] + [('kernel_ms', ctypes.c_double)]
 
 
+ADAPTIVE_FIELDS = ('triangles_in', 'triangles_out', 'collapsed', 'levels', 'mean_fallback', 'flat')
+ADAPTIVE_MAX_LEVELS = 10
+
+
+class SdfAdaptiveStats(ctypes.Structure):
+    """mirror of `sdf_adaptive_stats` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in ADAPTIVE_FIELDS] + [('clusters_used', _c_i64 * (ADAPTIVE_MAX_LEVELS + 1)),
+                                                         ('vertices', _c_i64 * (ADAPTIVE_MAX_LEVELS + 1)), ('kernel_ms', ctypes.c_double)]
+
+
 MEND_FIELDS = ('triangles_in', 'triangles_out', 'collapsed', 'duplicates', 'cancelled', 'faces')
 
 
@@ -200,6 +210,9 @@ ABI = {
     'sdf_mesh_components_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_simplify': (ctypes.c_int, [_vp, _f64p, _f64p, ctypes.c_double, ctypes.POINTER(_vp), ctypes.POINTER(SdfSimplifyStats)]),
     'sdf_mesh_simplify_last_kernel_ms': (ctypes.c_double, [_f64p]),
+    'sdf_mesh_simplify_adaptive': (ctypes.c_int, [_vp, _f64p, _f64p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(_vp),
+                                                  ctypes.POINTER(SdfAdaptiveStats)]),
+    'sdf_mesh_simplify_adaptive_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_mesh_mend': (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(SdfMendStats)]),
     'sdf_mesh_mend_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_contour_grid_host': (ctypes.c_int, [_vp, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, ctypes.c_double,
@@ -641,6 +654,38 @@ class Mesh:
         m = Mesh(eng, h)
         m.emitted = False
         m.simplify_stats = dict({k: int(getattr(st, k)) for k in SIMPLIFY_FIELDS}, kernel_ms=float(st.kernel_ms))
+        return m
+
+    def simplify_adaptive(self, origin, cell, tolerance, levels=5, reg=1e-3):
+        """a new Mesh: this one simplified to a tolerance on the device (sdf_mesh_simplify_adaptive, csrc/sdf_simplify.hip; DESIGN.md
+        section 4p; defined by tests/adaptive_ref.py and reproduced bit for bit).  Level L = 0 .. levels is the clustering of
+        `simplify` on the grid (origin, cell x 2^L); a cluster is accepted when the squared-area-weighted mean squared distance of
+        its representative from the planes of the triangles that touch it is at most tolerance^2 (model units; not a Hausdorff
+        bound), level 0 always; every welded vertex takes the coarsest accepted cluster it falls into, and the triangles whose
+        three clusters differ survive, in order and winding.  Flat faces collapse to a few triangles, creases and fillets stay
+        fine.  levels=0 is `simplify(origin, cell)`, tolerance=inf is `simplify(origin, cell * 2 ** levels)`.  The result owns its
+        soup and serves every reader; its `simplify_stats` is a dict of triangles_in, triangles_out, collapsed, levels, the lists
+        clusters_used and vertices (one entry per level), mean_fallback, flat, kernel_ms and tolerance.  This mesh stays valid.
+        ValueError, before any device work, for what `simplify` refuses, a tolerance that is negative, NaN or no real number, levels
+        that is no integer from 0 to 10 or a cell x 2^levels that is not finite; SdfHipError for a vertex that is not finite or a
+        cell too small for the key."""
+        from .simplify import check_levels, check_tolerance
+        eng = self.engine
+        tol = check_tolerance(tolerance, 'tolerance')
+        lv = check_levels(levels, 'levels')
+        if tol is None:
+            raise ValueError('simplify_adaptive: tolerance must be a real number >= 0 (inf is allowed), got None')
+        o = np.ascontiguousarray(origin, dtype=np.float64).reshape(-1)
+        c = np.ascontiguousarray(cell, dtype=np.float64).reshape(-1)
+        if o.shape != (3,) or c.shape != (3,):
+            raise ValueError('simplify_adaptive: origin and cell have 3 components each, got %r and %r' % (origin, cell))
+        h, st = _vp(), SdfAdaptiveStats()
+        _check(eng.lib, eng.lib.sdf_mesh_simplify_adaptive(self.handle, _dp(o, _f64p), _dp(c, _f64p), float(reg), tol, lv, ctypes.byref(h),
+                                                           ctypes.byref(st)))
+        m = Mesh(eng, h)
+        m.emitted = False
+        m.simplify_stats = dict({k: int(getattr(st, k)) for k in ADAPTIVE_FIELDS}, clusters_used=[int(n) for n in st.clusters_used[:lv + 1]],
+                                vertices=[int(n) for n in st.vertices[:lv + 1]], kernel_ms=float(st.kernel_ms), tolerance=tol)
         return m
 
     def mend(self):

@@ -156,6 +156,24 @@ class Mesh:
             finally:
                 small.close()
 
+    def simplify_adaptive(self, cell, tolerance, levels=5, origin=None, reg=1e-3):
+        """this mesh simplified to a tolerance on the device (sdf_amd/simplify.py): a new Mesh of the welded
+        result.  cell: the edge of the FINEST cluster, a scalar or one per axis; tolerance: how far, in this mesh's units, a
+        cluster's vertex may lie from the planes of the triangles it replaces (a squared-area-weighted root mean square, not a
+        Hausdorff bound); levels: the clusters double in edge that many times, 0 .. 10; origin: the corner of the clustering grids
+        (default: the minimum of the bounding box); reg: as for `simplify`"""
+        from . import core
+        pts = np.asarray(self.points, dtype=np.float64)
+        c = np.broadcast_to(np.asarray(cell, dtype=np.float64), (3,)).copy()
+        o = pts.min(axis=0) if origin is None and len(pts) else np.zeros(3) if origin is None else np.asarray(origin, dtype=np.float64)
+        with core.adopted(pts[np.asarray(self.triangles)]) as mesh:
+            small = mesh.simplify_adaptive(o, c, tolerance, levels, reg)
+            try:
+                points, cells = small.weld()
+                return Mesh(np.array(points), np.array(cells))
+            finally:
+                small.close()
+
     def mend(self):
         """this mesh mended on the device (sdf_amd/mend.py): a new Mesh of the welded result, without
         duplicate triangles and without the oppositely wound pairs that `simplify` leaves where a wall is thinner than a cluster"""

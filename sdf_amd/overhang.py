@@ -158,19 +158,21 @@ def overhangs_soup(soup, directions=UP, angle=45.0, bed_tolerance=None, classes=
         return _rated(mesh, d, sin_limit, angle, 0.0 if tol is None else tol, classes)
 
 
-def overhangs(sdf, directions=UP, angle=45.0, bed_tolerance=None, classes=False, keep=None, simplify=None, mend=False, **generate_kwargs):
+def overhangs(sdf, directions=UP, angle=45.0, bed_tolerance=None, classes=False, keep=None, simplify=None, mend=False,
+              simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`: step, bounds, samples, batch_size, sparse, verbose) and rate build
     directions there: an `Overhangs`.  directions: one vector, an array (K, 3) or an int n -- the six axis directions and n points
     of a Fibonacci spiral (`sphere_directions`); "up" is the build direction, the bed lies below the part.  angle: degrees in
     [0, 90), the steepest overhang from the vertical that prints without support -- a face is an overhang when n.d < -sin(angle).
     bed_tolerance: faces that look down and lie within it of the lowest point are bed contact, not overhang; None: the largest of
     the grid's three steps, so that the facets by which marching cubes rounds the bottom edges count as contact.  classes: True --
-    also the class of every triangle (one direction only).  keep, simplify, mend: as for `measure`.  A multi-process run whose
-    gathered soup is on the host raises NotImplementedError."""
+    also the class of every triangle (one direction only).  keep, simplify, simplify_tolerance, simplify_levels, mend: as for
+    `measure`.  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
     from . import core
     d, sin_limit, angle, tol = check_params(directions, angle, bed_tolerance, classes)       # (before anything is meshed)
     if simplify is not None:
         generate_kwargs['simplify'] = simplify
+    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:
         generate_kwargs['mend'] = mend
     with core.meshed(sdf, keep=keep, **generate_kwargs) as m:

@@ -35,23 +35,24 @@ def shells_of_soup(soup):
         return shells_of_mesh(mesh)
 
 
-def _meshed(sdf, generate_kwargs, simplify=None, mend=False):
+def _meshed(sdf, generate_kwargs, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5):
     """`core.meshed` for `shells` and `measure_shells`: the arguments of `generate`, nothing printed, one process; simplify: the
-    shells are those of the simplified mesh (`sdf_amd/simplify.py`), mend: ... of the mended mesh (`sdf_amd/mend.py`)"""
+    shells are those of the simplified mesh (`sdf_amd/simplify.py`; simplify_tolerance, simplify_levels: simplified to a tolerance), mend: ... of the mended mesh (`sdf_amd/mend.py`)"""
     from . import core, dist
     from .mend import check_mend
     mend = check_mend(mend)      # (before anything else is looked at: a bad value is refused without a device)
     if dist.world_size() > 1:
         raise NotImplementedError('shells: a multi-process run gathers its soup per step; label it in one process, or adopt the '
                                   'gathered soup (Engine.adopt_soup) and use shells_of_mesh')
-    return core.meshed(sdf, keep=None, simplify=simplify, mend=mend, to_host=False, **dict(generate_kwargs, verbose=False))
+    return core.meshed(sdf, keep=None, simplify=simplify, mend=mend, to_host=False,
+                       **dict(generate_kwargs, verbose=False, **core._tolerance_kwargs(simplify_tolerance, simplify_levels)))
 
 
-def shells(sdf, simplify=None, mend=False, **generate_kwargs):
+def shells(sdf, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`) and label the connected shells of the welded mesh there: only the
-    Shells cross the link, not the soup.  simplify: label the mesh simplified in clusters of simplify^3 grid cells; mend: True -- ... and
-    mended (duplicate triangles dropped, oppositely wound pairs cancelled)"""
-    with _meshed(sdf, generate_kwargs, simplify, mend) as m:
+    Shells cross the link, not the soup.  simplify: label the mesh simplified in clusters of simplify^3 grid cells (simplify_tolerance,
+    simplify_levels: ... simplified to that tolerance); mend: True -- ... and mended (duplicate triangles dropped, oppositely wound pairs cancelled)"""
+    with _meshed(sdf, generate_kwargs, simplify, mend, simplify_tolerance, simplify_levels) as m:
         return shells_of_mesh(m.mesh)
 
 
@@ -61,13 +62,13 @@ def largest_first(triangles):
     return np.lexsort((np.arange(len(t)), -t))
 
 
-def measure_shells(sdf, limit=None, simplify=None, mend=False, **generate_kwargs):
+def measure_shells(sdf, limit=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
     """a list of `Measurement` (sdf_amd/measure.py), one per shell, largest first by triangle count (ties: the lower shell number);
     `limit` bounds how many.  The model is meshed ONCE; then every shell costs one selection (a compaction of the soup) plus one
     measure (moments, weld, census) on the device, so ask for `limit` shells when the crumbs are many.  A sealed cavity is
     recognisable by its negative `volume`.  simplify: the shells of the mesh simplified in clusters of simplify^3 grid cells;
-    mend: True -- ... and mended."""
-    with _meshed(sdf, generate_kwargs, simplify, mend) as m:
+    simplify_tolerance, simplify_levels: ... simplified to that tolerance; mend: True -- ... and mended."""
+    with _meshed(sdf, generate_kwargs, simplify, mend, simplify_tolerance, simplify_levels) as m:
         return measure_shells_of_mesh(m.mesh, limit)
 
 

@@ -300,7 +300,7 @@ def supports_soup(soup, sdf, directions=UP, angle=45.0, bed_tolerance=0.0, start
 
 
 def supports(sdf, directions=UP, angle=45.0, bed_tolerance=None, start=None, min_step=None, step_scale=1.0, max_steps=256, refine=16,
-             top=8, keep=None, simplify=None, mend=False, **generate_kwargs):
+             top=8, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`: step, bounds, samples, batch_size, sparse, verbose) and trace the
     support rays of build directions there: a `Supports`.  directions: one vector or an array (K, 3) -- each is traced --, or an int
     n: the mesh is rated by `overhangs` over the six axis directions and n spiral points first, and the `top` directions with the
@@ -308,12 +308,13 @@ def supports(sdf, directions=UP, angle=45.0, bed_tolerance=None, start=None, min
     (bed_tolerance=None: the largest grid step).  start: how far below the face's centroid a ray begins (a face with material that
     close is BURIED); min_step: the least advance of a step (a gap narrower than it can be stepped over); both default to a quarter
     of the smallest grid step.  step_scale in (0, 1]: shorten the steps for a field that overestimates distances.  keep, simplify,
-    mend: as for `measure`.  A model with user closures, and a multi-process run whose gathered soup is on the host, take the same
+    simplify_tolerance, simplify_levels, mend: as for `measure`.  A model with user closures, and a multi-process run whose gathered soup is on the host, take the same
     definition on the host over `Engine.eval_points`."""
     from . import core
     d, sin_limit, angle, tol, top = check_call(directions, angle, bed_tolerance, start, min_step, step_scale, max_steps, refine, top)
     if simplify is not None:
         generate_kwargs['simplify'] = simplify
+    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:
         generate_kwargs['mend'] = mend
     with core.meshed(sdf, keep=keep, **generate_kwargs) as m:

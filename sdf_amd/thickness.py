@@ -188,16 +188,18 @@ def read_thickness(m, params, with_mesh=True):
 
 
 def thickness(sdf, start=None, min_step=None, t_far=None, max_steps=256, refine=16, normal_eps=None, step_scale=1.0,
-              keep=None, simplify=None, mend=False, **generate_kwargs):
+              keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`: step, bounds, samples, batch_size, sparse, verbose) and probe the wall
     thickness at every welded vertex of the final mesh -- after keep, simplify and mend -- there: a `Thickness`.  start: how far
     inside the vertex the ray begins (a wall thinner than that is THIN); min_step: the least advance of a step (it lets a ray leave
     the surface it starts on; a gap narrower than it can be stepped over); both default to a quarter of the smallest grid step.
     t_far: where a ray gives up (OPEN), default the diagonal of the bounds.  normal_eps: the step of the central difference that
-    gives the direction, default the preview's.  step_scale in (0, 1]: shorten the steps for a field that overestimates distances."""
+    gives the direction, default the preview's.  step_scale in (0, 1]: shorten the steps for a field that overestimates distances.
+    simplify_tolerance, simplify_levels: the final mesh is the one simplified to that tolerance."""
     from . import core
     if simplify is not None:
         generate_kwargs['simplify'] = simplify
+    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:
         generate_kwargs['mend'] = mend
     check_params(1.0 if normal_eps is None else normal_eps, 1.0 if start is None else start, 1.0 if min_step is None else min_step,
