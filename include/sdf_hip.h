@@ -393,6 +393,40 @@ int sdf_mesh_vertex_thickness(sdf_mesh *mesh, sdf_tape *tape, const double *para
                               double *h_thickness, uint8_t *h_status, int32_t *h_steps);
 /* the kernel of this thread's last successful sdf_mesh_vertex_thickness alone, milliseconds by HIP events (tools/thickness_time.py) */
 double sdf_mesh_thickness_last_kernel_ms(void);
+/* A mesh held to the field (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4q, defined by
+ * tests/deviation_ref.py and reproduced bit for bit).  Float64, the interpreter of sdf_eval_points, one rounding per operation.
+ *
+ * sdf_mesh_triangle_deviation samples the field f on every triangle (A, B, C) of the float64 soup: order = n in 1 .. 8, the
+ * S = (n+1)(n+2)/2 samples in the order for i in 0..n: for j in 0..n-i, weights wa = (n-i-j)/n, wb = i/n, wc = j/n, sample point
+ * (A*wa + B*wb) + C*wc per coordinate; sample 0 is corner A.  Per triangle: h_dev float64, the sampled value of largest magnitude
+ * (a later sample replaces it only where its magnitude is strictly greater; the first NaN replaces it and stays), h_at int32, that
+ * sample's index, h_sumsq float64, the sequential sum of the squared values.  Needs no weld; serves every mesh that has (or can
+ * make) a soup on the device.  One device allocation (20 bytes per triangle), freed before it returns.  A mesh of 0 triangles
+ * returns 0 without a launch.  Refused on the host before anything is allocated or launched, with return value 2: a NULL argument,
+ * a tape of another context, a tape with user closures, order outside 1 .. 8, 2^31 or more triangles.
+ *
+ * sdf_mesh_snap moves the unique vertices P of sdf_mesh_weld onto the zero set.  params4 = eps, tol, max_move, 0 (reserved).  Every
+ * vertex starts at q = P as ITER; in each of `iters` passes a vertex still ITER evaluates v = f(q): NaN makes it NAN (4) and puts q
+ * back to P, |v| <= tol makes it SNAPPED (1); otherwise g is the central difference of sdf_mesh_vertex_normals at q with step eps,
+ * len2 = (g0*g0 + g1*g1) + g2*g2, zero or NaN makes it FLAT (3) where it is; otherwise s = (v * (2 eps)) / len2, qn = q - s g (the
+ * Newton step v grad / |grad|^2), and if |qn - P| > max_move the vertex is HELD (2) where it is, else q = qn.  After the passes a
+ * vertex still ITER is SNAPPED if |f(q)| <= tol, else LEFT (0).  The result is a NEW mesh whose soup is q taken through the welded
+ * cells, in triangle order and winding; it OWNS its soup, like a simplified mesh, and serves every reader; the source mesh stays
+ * valid and unchanged.  Vertices that land on one point make a collapsed triangle (sdf_mesh_mend drops it); topology is not
+ * preserved and creases are not restored.  h_points (n_unique x 3 float64), h_status (uint8), h_residual (float64: f at the
+ * final q, NaN for NAN) and h_evals (int32: the evaluations the vertex needed -- 1 per pass it entered, 6 more where it took the
+ * gradient, 1 for the final value of a vertex still ITER) are in the source's weld order; each may be NULL.  Refused with return value 2: a NULL mesh, tape, params4,
+ * out or stats, a mesh that is not welded, a tape of another context, a tape with user closures, a non-finite parameter, eps <= 0,
+ * tol < 0, max_move < 0, iters < 1.  Other failures return 1 with nothing left allocated; *out is written on success only. */
+typedef struct sdf_snap_stats {
+    int64_t vertices, left, snapped, held, flat, nan;
+    double kernel_ms;
+} sdf_snap_stats;
+int sdf_mesh_triangle_deviation(sdf_mesh *mesh, sdf_tape *tape, int order, double *h_dev, int32_t *h_at, double *h_sumsq);
+int sdf_mesh_snap(sdf_mesh *mesh, sdf_tape *tape, const double *params4, int iters, sdf_mesh **out, double *h_points,
+                  uint8_t *h_status, double *h_residual, int32_t *h_evals, sdf_snap_stats *stats);
+/* the kernel of this thread's last successful sdf_mesh_triangle_deviation alone, milliseconds by HIP events (tools/deviation_time.py) */
+double sdf_mesh_deviation_last_kernel_ms(void);
 /* The body of a binary little-endian PLY file of the welded mesh: h_vertices receives n_unique records of float32 x, y, z (12
  * bytes) or, with_normals = 1, float32 x, y, z, nx, ny, nz (24 bytes; needs a successful sdf_mesh_vertex_normals first);
  * h_faces receives T records of 13 bytes: uint8 3 and three little-endian int32 vertex indices.  Refused with return value 2: a

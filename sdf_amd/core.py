@@ -160,7 +160,8 @@ Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', '
 Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=, the simplified mesh under
 simplify=, the mended mesh under mend=True -- its statistics ride on it: `mesh.mend_stats`), or None when a multi-process run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape,
 engine, bounds, stats: the call's; simplify_stats: the dict of `engine.Mesh.simplify` -- of `engine.Mesh.simplify_adaptive` under
-simplify_tolerance= --, or None without either."""
+simplify_tolerance= --, or None without either.  Under snap= the statistics of `engine.Mesh.snap` ride on the mesh, like mend's:
+`mesh.snap_stats` (through a mend as well)."""
 
 
 @contextlib.contextmanager
@@ -168,7 +169,7 @@ def meshed(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False, simplify_tolerance=None, simplify_levels=5):
+        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False, simplify_tolerance=None, simplify_levels=5, snap=False):
     """the one path from a model to its mesh on the device: the arguments of `generate`, `keep` (only these
     connected shells, `shells.resolve_keep`: the device mesh is labelled, the kept shells are compacted into a mesh of their own
     and THAT is yielded; section 4h), `simplify` (a real number k > 0, `simplify.check_simplify`: after keep, the mesh is simplified on
@@ -176,7 +177,11 @@ def meshed(
     line counts; section 4j), `simplify_tolerance` and `simplify_levels` (a real number >= 0 in model units and an integer 0 .. 10,
     `simplify.check_adaptive`: in the place of the uniform clustering the mesh is simplified to that tolerance on the levels of
     simplify x 2^L grid cells, L = 0 .. simplify_levels, `engine.Mesh.simplify_adaptive`; simplify is then the finest cluster and
-    defaults to 1; section 4p), `mend` (False or True, `mend.check_mend`: after keep and after simplify -- simplifying is what makes the
+    defaults to 1; section 4p), `snap` (False, True or a dict of eps, tol, max_move, iters, `deviation.check_snap_option`: after
+    simplify and before mend, the welded vertices are put back on the zero set of the field by Newton steps on the device,
+    `engine.Mesh.snap`, and the moved mesh is what is yielded -- two vertices that land on one point make a collapsed triangle, which
+    mend drops; eps defaults to the preview's normal_eps, tol to 1e-3 x the smallest grid step, max_move to the diagonal of one
+    cluster cell, of one grid cell without simplify, iters to 4; section 4q), `mend` (False or True, `mend.check_mend`: after keep and after simplify -- simplifying is what makes the
     pairs -- duplicate triangles are dropped and oppositely wound pairs cancel on the device, `engine.Mesh.mend`, and the mended mesh
     is what is yielded and what the closing line counts; section 4k) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
     16-byte records).  Yields a `Meshed`, which the readers below take; closes what it opened on the way out, and after a body
@@ -189,6 +194,8 @@ def meshed(
     simplify, simplify_tolerance, simplify_levels = check_adaptive(simplify, simplify_tolerance, simplify_levels)      # (before anything is meshed)
     from .mend import check_mend
     mend = check_mend(mend)      # (before the engine is asked for)
+    from .deviation import check_snap_option, snap_params
+    snap = check_snap_option(snap)      # (None: the call without it)
     start = time.time()
     eng = engine.get_engine()
     tape = eng.tape_for(sdf)
@@ -243,11 +250,20 @@ def meshed(
             mesh.close()
             mesh = small
             simplify_stats = small.simplify_stats
+        if snap is not None:
+            if mesh is None:
+                raise NotImplementedError('snap: the soup of this multi-process run was gathered on the host; a mesh is snapped on '
+                                          'the device only (run it in one process, or with a device-resident exchange)')
+            moved = mesh.snap(tape, **snap_params(snap, bounds, (dx, dy, dz), simplify))
+            mesh.close()
+            mesh = moved
         if mend:
             if mesh is None:
                 raise NotImplementedError('mend: the soup of this multi-process run was gathered on the host; a mesh is mended on '
                                           'the device only (run it in one process, or with a device-resident exchange)')
             mended = mesh.mend()
+            if snap is not None:
+                mended.snap_stats = mesh.snap_stats
             mesh.close()
             mesh = mended
         yield Meshed(mesh, points, tape, eng, bounds, stats, simplify_stats)
@@ -358,7 +374,7 @@ generate.last_stats = None
 
 
 def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5,
-                  **generate_kwargs):
+                  snap=False, **generate_kwargs):
     """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
     welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
     difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
@@ -368,10 +384,15 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
     device in clusters of k^3 grid cells, after keep (`sdf_amd/simplify.py`; `generate_mesh.last_simplify` holds
     its statistics); the normals are then the field's at the NEW vertices.  mend: True -- after keep and simplify, duplicate triangles
     are dropped and oppositely wound pairs cancel (`sdf_amd/mend.py`; `generate_mesh.last_mend` holds the
-    statistics of the last call that mended).  Not in the reference."""
+    statistics of the last call that mended).  snap: True or a dict of eps, tol, max_move, iters -- after simplify and before mend the
+    vertices are put back on the zero set of the field (`sdf_amd/deviation.py`; `generate_mesh.last_snap` holds
+    the statistics of the last call that snapped); the normals are then the field's at the snapped vertices.  Not in the reference
+    (DESIGN.md section 4f)."""
     if simplify is not None:      # (simplify=None is the call without the argument)
         generate_kwargs['simplify'] = simplify
     generate_kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
+    if snap is not False:         # (snap=False is the call without the argument)
+        generate_kwargs['snap'] = snap
     if mend is not False:         # (mend=False is the call without the argument)
         generate_kwargs['mend'] = mend
     with meshed(sdf, keep=keep, **generate_kwargs) as m:
@@ -379,6 +400,8 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
         generate_mesh.last_simplify = m.simplify_stats
         if mend:
             generate_mesh.last_mend = m.mesh.mend_stats
+        if getattr(m.mesh, 'snap_stats', None) is not None:
+            generate_mesh.last_snap = m.mesh.snap_stats
     generate_mesh.last_flat = got['n_flat']
     return got['points'], got['cells'], got['normals']
 
@@ -386,10 +409,11 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
 generate_mesh.last_flat = 0
 generate_mesh.last_simplify = None
 generate_mesh.last_mend = None
+generate_mesh.last_snap = None
 
 
 def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False,
-         simplify_tolerance=None, simplify_levels=5, **kwargs):
+         simplify_tolerance=None, simplify_levels=5, snap=False, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
@@ -401,7 +425,9 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     section 4k).  thickness: True, or a dict of the probe's arguments (start, min_step, t_far, step_scale, max_steps, refine) -- the
     vertices of a .ply file carry the wall thickness of the final mesh as `property float quality` (`sdf_amd/thickness.py`, DESIGN.md
     section 4l; the direction's step is normal_eps); the native writer only, any other extension or writer raises ValueError before
-    anything is meshed, and the file's body is packed on the host: it is not the fast path.  May be combined with normals=True."""
+    anything is meshed, and the file's body is packed on the host: it is not the fast path.  May be combined with normals=True.
+    snap: True or a dict of eps, tol, max_move, iters -- after simplify and before mend the vertices are put back on the zero set of
+    the field, and the file holds the moved mesh (`sdf_amd/deviation.py`)."""
     from . import meshfile
     path = os.fspath(path)
     how = meshfile.choose_writer(path, writer, normals, bool(thickness))
@@ -411,6 +437,8 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:         # (mend=False is the call without the argument)
         kwargs['mend'] = mend
+    if snap is not False:         # (snap=False is the call without the argument)
+        kwargs['snap'] = snap
     if thickness:                 # (refused before anything is meshed, like the extension above)
         from .thickness import check_params, default_params, read_thickness
         probe = dict(thickness) if isinstance(thickness, dict) else {}

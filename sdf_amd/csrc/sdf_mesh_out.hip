@@ -1,7 +1,7 @@
 // sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
 // (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
-// welded vertices, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build directions, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_supports.h, sdf_thickness.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
+// welded vertices, the deviation of the triangles from the field and the vertices snapped onto it, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build directions, kinds, prune masks, and the end
+// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_supports.h, sdf_thickness.h, sdf_deviation.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -9,6 +9,7 @@
 
 #include "sdf_internal.h"
 #include "sdf_components.h"
+#include "sdf_deviation.h"
 #include "sdf_expand_host.h"   // (+ <chrono>, <cstring>, <mutex>, <thread>)
 #include "sdf_measure.h"
 #include "sdf_mend.h"
@@ -401,6 +402,109 @@ int sdf_mesh_vertex_thickness(sdf_mesh *m, sdf_tape *t, const double *params6, i
 }
 
 double sdf_mesh_thickness_last_kernel_ms(void) { return g_thickness_kernel_ms; }
+
+// ---- a mesh held to the field: the deviation of every triangle, the welded vertices snapped onto the zero set ----
+static thread_local double g_deviation_kernel_ms = 0.0;
+
+int sdf_mesh_triangle_deviation(sdf_mesh *m, sdf_tape *t, int order, double *h_dev, int32_t *h_at, double *h_sumsq) {
+    auto refuse = [](const std::string &why) { fail("sdf_mesh_triangle_deviation: " + why); return 2; };
+    if (!m || !t || !h_dev || !h_at || !h_sumsq) return refuse("NULL argument");
+    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
+    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): take the deviation over sdf_eval_points_extern_host");
+    if (order < 1 || order > 8) return refuse("order must lie in 1 .. 8");
+    MESH_READY(m);
+    const long long nt = (long long)m->st.n_triangles;
+    if (nt >= (1ll << 31)) return refuse("2^31 or more triangles");
+    if (nt == 0) return 0;
+    MESH_SOUP_READY(m);
+    sdf_ctx *c = m->ctx;
+    HIPCHK(set_device(c->device));
+    hipStream_t st = c->stream;
+    double *dev, *sumsq;
+    int32_t *at;
+    Scratch scratch(st);
+    scratch.part(&dev, (size_t)nt); scratch.part(&sumsq, (size_t)nt); scratch.part(&at, (size_t)nt);
+    EventTimer timer;
+    HIPCHK_MSG("sdf_mesh_triangle_deviation: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
+    HIPCHK_FN(timer.start(st));
+    HIPCHK_FN((hipError_t)launch_triangle_deviation(st, t->d_code, t->d_c64, t->full, (const double *)mesh_soup(m), nt, order, dev, at, sumsq));
+    HIPCHK_FN(timer.stop(st));
+    HIPCHK_FN(hipMemcpyAsync(h_dev, dev, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_at, at, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_sumsq, sumsq, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(stream_wait(st));
+    HIPCHK_FN(timer.ms(&g_deviation_kernel_ms));
+    return 0;
+}
+
+double sdf_mesh_deviation_last_kernel_ms(void) { return g_deviation_kernel_ms; }
+
+int sdf_mesh_snap(sdf_mesh *m, sdf_tape *t, const double *params4, int iters, sdf_mesh **out, double *h_points, uint8_t *h_status,
+                  double *h_residual, int32_t *h_evals, sdf_snap_stats *stats) {
+    auto refuse = [](const std::string &why) { fail("sdf_mesh_snap: " + why); return 2; };
+    if (!m || !t || !params4 || !out || !stats) return refuse("NULL argument");
+    if (m->weld_n < 0) return refuse("call sdf_mesh_weld first");
+    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
+    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every pass would need a host round trip");
+    for (int i = 0; i < 4; i++) if (!std::isfinite(params4[i])) return refuse("the parameters are not finite");
+    SnapArgs a;
+    a.eps = params4[0]; a.two_eps = 2.0 * params4[0]; a.tol = params4[1]; a.max_move = params4[2]; a.iters = iters;
+    if (!(a.eps > 0.0)) return refuse("eps must be positive");
+    if (!(a.tol >= 0.0)) return refuse("tol must not be negative");
+    if (!(a.max_move >= 0.0)) return refuse("max_move must not be negative");
+    if (iters < 1) return refuse("iters must be at least 1");
+    const long long nu = m->weld_n, nt = (long long)m->st.n_triangles;
+    sdf_snap_stats got = sdf_snap_stats();
+    got.vertices = (int64_t)nu;
+    DevBuf soup;                                                       // the moved vertices' own soup: the new mesh's `out`
+    if (nu > 0 && nt > 0) {                                            // (nothing to move: a mesh of 0 triangles, no launch)
+        sdf_ctx *c = m->ctx;
+        HIPCHK(set_device(c->device));
+        hipStream_t st = c->stream;
+        double *q, *residual;
+        int32_t *evals;
+        uint8_t *status;
+        Scratch scratch(st);
+        scratch.part(&q, (size_t)nu * 3); scratch.part(&residual, (size_t)nu); scratch.part(&evals, (size_t)nu); scratch.part(&status, (size_t)nu);
+        std::vector<uint8_t> codes((size_t)nu);
+        EventTimer timer;
+        HIPCHK_MSG("sdf_mesh_snap: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
+        if (soup.ensure((size_t)nt * 72)) return 1;
+        // (from here on a failure hands the soup back: the scratch block drains the stream before it goes)
+        static const char who[] = "sdf_mesh_snap: ";
+        auto run = [&]() -> int {
+            HIPCHK_MSG(who, timer.start(st));
+            HIPCHK_MSG(who, (hipError_t)launch_vertex_snap(st, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, a, q, status, residual, evals));
+            HIPCHK_MSG(who, timer.stop(st));
+            launch_k_gather_soup(dim3(blocks_of(9 * nt)), dim3(256), st, q, m->weld_inv.as<long long>(), 9 * nt, (double *)soup.p);
+            HIPCHK_MSG(who, hipGetLastError());
+            HIPCHK_MSG(who, hipMemcpyAsync(codes.data(), status, (size_t)nu, hipMemcpyDeviceToHost, st));
+            if (h_points) HIPCHK_MSG(who, hipMemcpyAsync(h_points, q, (size_t)nu * 24, hipMemcpyDeviceToHost, st));
+            if (h_residual) HIPCHK_MSG(who, hipMemcpyAsync(h_residual, residual, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
+            if (h_evals) HIPCHK_MSG(who, hipMemcpyAsync(h_evals, evals, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
+            return 0;
+        };
+        const int rc = run();
+        const hipError_t e = stream_wait(st);                          // (before `codes` goes, whatever the copies said)
+        if (rc || e != hipSuccess) {
+            soup.release();
+            if (!rc) HIPCHK_FN(e);
+            return 1;
+        }
+        if (timer.ms(&got.kernel_ms) != hipSuccess) got.kernel_ms = 0.0;
+        int64_t n[5] = {0, 0, 0, 0, 0};
+        for (long long i = 0; i < nu; i++) n[codes[(size_t)i] < 5 ? codes[(size_t)i] : 0]++;
+        got.left = n[0]; got.snapped = n[1]; got.held = n[2]; got.flat = n[3]; got.nan = n[4];
+        if (h_status) memcpy(h_status, codes.data(), (size_t)nu);
+    }
+    sdf_mesh *s = new sdf_mesh();                                      // (like a simplified mesh: it owns the soup, `out` goes back to the pool with the mesh)
+    s->ctx = m->ctx;
+    s->out = soup;
+    s->st.n_triangles = soup.p ? (int64_t)nt : 0;
+    *stats = got;
+    *out = s;
+    return 0;
+}
 
 // ---- the mesh measured on the device: moments of the soup, edge census of the welded cells ----
 static thread_local double g_measure_kernel_ms = 0.0;

@@ -32,4 +32,5 @@ void launch_k_scan_items(dim3 grid, dim3 block, hipStream_t stream, const sdfk::
 void launch_k_emit2(dim3 grid, dim3 block, hipStream_t stream, const sdfk::MeshArgs &a);
 void launch_k_stl(dim3 grid, dim3 block, hipStream_t stream, const double *pts, long long ntri, unsigned short *out);
 void launch_k_ply_vertices(dim3 grid, dim3 block, hipStream_t stream, const double *pts, const double *nrm, long long n_floats, int width, float *out);
+void launch_k_gather_soup(dim3 grid, dim3 block, hipStream_t stream, const double *pts, const long long *inv, long long n_doubles, double *out);
 void launch_k_ply_faces(dim3 grid, dim3 block, hipStream_t stream, const long long *inv, long long ntri, unsigned char *out);

@@ -357,6 +357,16 @@ __global__ __launch_bounds__(256) void k_ply_vertices(const double *__restrict__
     out[e] = (float)(c < 3 ? pts[3 * v + c] : nrm[3 * v + (c - 3)]);
 }
 
+// ---- the soup of moved vertices (sdf_mesh_snap): nine doubles per triangle, taken from the points `pts` through the
+// welded cells `inv`, in triangle order and winding.  One double per thread: the stores are consecutive. ----
+__global__ __launch_bounds__(256) void k_gather_soup(const double *__restrict__ pts, const long long *__restrict__ inv, long long n_doubles,
+                                                     double *__restrict__ out) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_doubles) return;
+    const long long corner = e / 3;
+    out[e] = pts[3 * inv[corner] + (e - 3 * corner)];
+}
+
 // face record: uint8 3, three little-endian int32: 13 bytes, not word-aligned.  A workgroup assembles its 256 records (3328 bytes = 832
 // words, so every workgroup starts on a word) as bytes in LDS and stores aligned words; what is left of the last record of the file
 // (1 to 3 bytes) is stored as bytes.
@@ -557,6 +567,9 @@ void launch_k_stl(dim3 grid, dim3 block, hipStream_t stream, const double *pts, 
 }
 void launch_k_ply_vertices(dim3 grid, dim3 block, hipStream_t stream, const double *pts, const double *nrm, long long n_floats, int width, float *out) {
     hipLaunchKernelGGL(k_ply_vertices, grid, block, 0, stream, pts, nrm, n_floats, width, out);
+}
+void launch_k_gather_soup(dim3 grid, dim3 block, hipStream_t stream, const double *pts, const long long *inv, long long n_doubles, double *out) {
+    hipLaunchKernelGGL(k_gather_soup, grid, block, 0, stream, pts, inv, n_doubles, out);
 }
 void launch_k_ply_faces(dim3 grid, dim3 block, hipStream_t stream, const long long *inv, long long ntri, unsigned char *out) {
     hipLaunchKernelGGL(k_ply_faces, grid, block, 0, stream, inv, ntri, out);

@@ -80,6 +80,10 @@ class SDF3(SDFBase):
         from .thickness import thickness
         return thickness(self, *args, **kwargs)
 
+    def deviation(self, *args, **kwargs):
+        from .deviation import deviation
+        return deviation(self, *args, **kwargs)
+
     def overhangs(self, *args, **kwargs):
         from .overhang import overhangs
         return overhangs(self, *args, **kwargs)

@@ -85,6 +85,14 @@ class SdfMendStats(ctypes.Structure):
     _fields_ = [(k, _c_i64) for k in MEND_FIELDS] + [('kernel_ms', ctypes.c_double)]
 
 
+SNAP_FIELDS = ('vertices', 'left', 'snapped', 'held', 'flat', 'nan')
+
+
+class SdfSnapStats(ctypes.Structure):
+    """mirror of `sdf_snap_stats` in include/sdf_hip.h"""
+    _fields_ = [(k, _c_i64) for k in SNAP_FIELDS] + [('kernel_ms', ctypes.c_double)]
+
+
 CONTOUR_COUNTS = ('n_points', 'n_contours', 'n_segments', 'nonfinite_cells', 'rounds')
 
 
@@ -199,6 +207,10 @@ ABI = {
     'sdf_mesh_normals_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_vertex_thickness': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _u8p, ctypes.POINTER(ctypes.c_int32)]),
     'sdf_mesh_thickness_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_triangle_deviation': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _f64p, ctypes.POINTER(ctypes.c_int32), _f64p]),
+    'sdf_mesh_deviation_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_snap': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, ctypes.POINTER(_vp), _f64p, _u8p, _f64p, ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(SdfSnapStats)]),
     'sdf_mesh_emit_ply_host': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     'sdf_mesh_moments': (ctypes.c_int, [_vp, _f64p, ctypes.POINTER(SdfMoments)]),
     'sdf_mesh_edge_census': (ctypes.c_int, [_vp, ctypes.POINTER(SdfEdgeCensus)]),
@@ -539,6 +551,68 @@ class Mesh:
         _check(eng.lib, eng.lib.sdf_mesh_vertex_thickness(self.handle, dt.handle, _dp(p6, _f64p), params[5], params[6], _dp(th, _f64p),
                                                           _dp(status, _u8p), _dp(steps, ctypes.POINTER(ctypes.c_int32))))
         return th, status, steps
+
+    def triangle_deviation(self, sdf_or_tape, order=2):
+        """(dev (T,) float64, at (T,) int32, sumsq (T,) float64): how far every triangle of the soup lies from the zero set of the
+        field (sdf_mesh_triangle_deviation, csrc/sdf_deviation.hip; defined by tests/deviation_ref.py and
+        reproduced bit for bit).  The field is sampled at the (order+1)(order+2)/2 points of a barycentric lattice (order 1 .. 8;
+        sample 0 is the first corner): dev is the sampled value of largest magnitude (NaN once a sample is NaN), at the index of that
+        sample, sumsq the sum of the squared values.  It is one-sided, mesh to surface, and |f| is a distance only where the field is
+        one.  Needs no weld.  A model with user closures takes the same definition over `Engine.eval_points` on the host.  Raises
+        ValueError, before any device work, for an order outside 1 .. 8 and for an engine in float32 precision."""
+        from .deviation import check_order, triangle_deviation
+        eng = self.engine
+        order = check_order(order)
+        if eng.precision != PRECISION_F64:
+            raise ValueError('triangle_deviation samples in float64 only; this engine is set to float32 precision')
+        dt = eng.tape_for(sdf_or_tape)
+        if dt.tape.externs:
+            return triangle_deviation(lambda P: eng.eval_points(dt, P), np.asarray(self.points()).reshape(-1, 3, 3), order)
+        t = self.n_triangles
+        dev, at, sumsq = np.empty(t, np.float64), np.empty(t, np.int32), np.empty(t, np.float64)
+        _check(eng.lib, eng.lib.sdf_mesh_triangle_deviation(self.handle, dt.handle, order, _dp(dev, _f64p), _dp(at, ctypes.POINTER(ctypes.c_int32)),
+                                                            _dp(sumsq, _f64p)))
+        return dev, at, sumsq
+
+    def snap(self, sdf_or_tape, eps, tol, max_move, iters=4):
+        """a new Mesh: this one with its welded vertices put back on the zero set of the field (sdf_mesh_snap, csrc/sdf_deviation.hip;
+        DESIGN.md section 4q; defined by tests/deviation_ref.py and reproduced bit for bit).  Up to `iters` Newton steps
+        q - f(q) g / |g|^2 with g the central difference of step eps; a vertex stops as SNAPPED (1) once |f(q)| <= tol, as HELD (2)
+        where a step would take it farther than max_move from where it began, as FLAT (3) where the field has no gradient, as NAN
+        (4, back where it began) where the field is NaN, and is LEFT (0) when the steps run out.  The result owns its soup -- the
+        moved points through the welded cells, in triangle order and winding -- and serves every reader; it carries `snap_stats`
+        (vertices, left, snapped, held, flat, nan, kernel_ms), `snap_result` = (points (U, 3), status (U,) uint8, residual (U,)) in
+        THIS mesh's weld order and `snap_evals` (U,) int32.  Vertices that land on one point make collapsed triangles (`mend`
+        drops them); creases are not restored and topology is not preserved.  This mesh stays valid.  A model with user closures
+        takes the same definition over `Engine.eval_points` on the host, and the new soup is uploaded.  Raises ValueError, before
+        any device work, for the parameters the C entry refuses and for an engine in float32 precision."""
+        from .deviation import STATUS_NAMES, check_snap, vertex_snap
+        eng = self.engine
+        eps, tol, max_move, iters = check_snap(eps, tol, max_move, iters)
+        if eng.precision != PRECISION_F64:
+            raise ValueError('snap steps in float64 only; this engine is set to float32 precision')
+        dt = eng.tape_for(sdf_or_tape)
+        if dt.tape.externs:
+            from . import core
+            pts, cells = self.weld()
+            q, status, residual, evals = vertex_snap(lambda P: eng.eval_points(dt, P), pts, eps, tol, max_move, iters)
+            held = core.adopted(q[cells])                          # (the upload lives as long as the mesh over it)
+            m = held.__enter__()
+            m._adopted = held
+            stats = dict({'vertices': len(pts)}, kernel_ms=0.0, **{n.lower(): int((status == c).sum()) for c, n in enumerate(STATUS_NAMES)})
+        else:
+            nu = self._welded()
+            q, status = np.empty((nu, 3), np.float64), np.empty(nu, np.uint8)
+            residual, evals = np.empty(nu, np.float64), np.empty(nu, np.int32)
+            p4 = np.array([eps, tol, max_move, 0.0], np.float64)
+            h, st = _vp(), SdfSnapStats()
+            _check(eng.lib, eng.lib.sdf_mesh_snap(self.handle, dt.handle, _dp(p4, _f64p), iters, ctypes.byref(h), _dp(q, _f64p), _dp(status, _u8p),
+                                                  _dp(residual, _f64p), _dp(evals, ctypes.POINTER(ctypes.c_int32)), ctypes.byref(st)))
+            m = Mesh(eng, h)
+            stats = dict({k: int(getattr(st, k)) for k in SNAP_FIELDS}, kernel_ms=float(st.kernel_ms))
+        m.emitted = False
+        m.snap_stats, m.snap_result, m.snap_evals = stats, (q, status, residual), evals
+        return m
 
     def ply_records(self, normals=False):
         """(vertex_bytes, face_bytes) uint8: the body of a binary little-endian PLY file of the welded mesh, packed on the device

@@ -55,7 +55,7 @@ def measure_mesh(mesh, origin=None):
         nonfinite_triangles=m['nonfinite'], origin=_frozen(m['origin']), sums=_frozen(m['sums']), **c)
 
 
-def measure(sdf, origin=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
+def measure(sdf, origin=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, snap=False, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`: step, bounds, samples, batch_size, sparse, verbose) and measure the
     mesh there: nothing but the result crosses the link.  origin: the point the moments are taken about (default: the midpoint of
     the soup's bounding box, which keeps the cancellation small for a model far from the world's origin; the results are given
@@ -63,13 +63,16 @@ def measure(sdf, origin=None, keep=None, simplify=None, mend=False, simplify_tol
     gives every shell its own Measurement).  simplify: measure the mesh simplified in clusters of simplify^3 grid cells, after keep
     (`sdf_amd/simplify.py`; duplicate or oppositely wound triangles that the clustering made show up in the census unless `mend`).
     simplify_tolerance, simplify_levels: measure the mesh simplified to that tolerance instead (model units).
-    mend: True -- measure the mesh mended after keep and simplify (`sdf_amd/mend.py`).  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
+    mend: True -- measure the mesh mended after keep and simplify (`sdf_amd/mend.py`).  snap: True or a dict -- measure the mesh whose
+    vertices were put back on the zero set after simplify (`sdf_amd/deviation.py`).  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
     from . import core
     if simplify is not None:
         generate_kwargs['simplify'] = simplify
     generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:
         generate_kwargs['mend'] = mend
+    if snap is not False:
+        generate_kwargs['snap'] = snap
     with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
         if m.mesh is None:
             raise NotImplementedError('measure: the soup of this multi-process run was gathered on the host; the measurements are made '

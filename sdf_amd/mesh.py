@@ -114,6 +114,31 @@ class Mesh:
         params = default_params((pts.min(axis=0), pts.max(axis=0)), steps3, start, min_step, t_far, normal_eps)
         return thickness_of_soup(pts[np.asarray(self.triangles)], f, step_scale=step_scale, max_steps=max_steps, refine=refine, **params)
 
+    def deviation(self, f, order=2):
+        """how far this mesh lies from the zero set of the field `f`, sampled on the device on every triangle (sdf_amd/deviation.py,
+        DESIGN.md section 4q): a `Deviation`"""
+        from .deviation import deviation_of_soup
+        return deviation_of_soup(np.asarray(self.points, dtype=np.float64)[np.asarray(self.triangles)], f, order)
+
+    def snap(self, f, step=None, eps=None, tol=None, max_move=None, iters=4):
+        """a new Mesh: this one with its vertices put back on the zero set of the field `f` on the device (sdf_amd/deviation.py,
+        DESIGN.md section 4q); it carries `snap_status`, `snap_residual` (per welded vertex) and `snap_stats`.  A file has no sampling
+        grid, so `step` must be given (tol = 1e-3 x the smallest step, max_move = the diagonal of one cell), or tol and max_move
+        themselves; eps defaults to 1e-4 x the half-diagonal of this mesh's bounding box"""
+        from .deviation import snap_of_soup, snap_params
+        pts = np.asarray(self.points, dtype=np.float64)
+        if len(pts) == 0:
+            raise ValueError('snap: the mesh has no vertices')
+        if step is None and (tol is None or max_move is None):
+            raise ValueError('snap: give step, or tol and max_move')
+        steps3 = (1.0, 1.0, 1.0) if step is None else tuple(np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)).tolist())
+        over = {k: v for k, v in (('eps', eps), ('tol', tol), ('max_move', max_move), ('iters', iters)) if v is not None}
+        par = snap_params(over, (pts.min(axis=0), pts.max(axis=0)), steps3)
+        q, cells, status, residual, stats = snap_of_soup(pts[np.asarray(self.triangles)], f, **par)
+        out = Mesh(q, cells)
+        out.snap_status, out.snap_residual, out.snap_stats = status, residual, stats
+        return out
+
     def overhangs(self, directions=(0.0, 0.0, 1.0), angle=45.0, bed_tolerance=None, classes=False):
         """build directions rated for this mesh on the device (sdf_amd/overhang.py): an `Overhangs`.
         directions: one vector, an array (K, 3) or an int n for the six axes and n spiral points; a file has no sampling grid, so

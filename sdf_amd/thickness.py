@@ -6,7 +6,8 @@ thickness at the vertex.  tests/thickness_ref.py is the definition; `vertex_thic
 does not reach: a model with user closures, a soup that a multi-process run gathered on the host.
 
 What it is not: it measures along the field normal, not the largest inscribed sphere; an outside gap narrower than `min_step` can
-be stepped over; the vertices of a simplified mesh lie off the surface, so measure before `simplify=` or raise `start`; a field
+be stepped over; the vertices of a simplified mesh lie off the surface, so measure before `simplify=`, raise `start` or put them back
+with `snap=True`; a field
 that is only a bound, not a distance, costs steps and not correctness."""
 import numpy as np
 
@@ -188,20 +189,24 @@ def read_thickness(m, params, with_mesh=True):
 
 
 def thickness(sdf, start=None, min_step=None, t_far=None, max_steps=256, refine=16, normal_eps=None, step_scale=1.0,
-              keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):
+              keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, snap=False, **generate_kwargs):
     """mesh `sdf` on the device (the arguments of `generate`: step, bounds, samples, batch_size, sparse, verbose) and probe the wall
     thickness at every welded vertex of the final mesh -- after keep, simplify and mend -- there: a `Thickness`.  start: how far
     inside the vertex the ray begins (a wall thinner than that is THIN); min_step: the least advance of a step (it lets a ray leave
     the surface it starts on; a gap narrower than it can be stepped over); both default to a quarter of the smallest grid step.
     t_far: where a ray gives up (OPEN), default the diagonal of the bounds.  normal_eps: the step of the central difference that
     gives the direction, default the preview's.  step_scale in (0, 1]: shorten the steps for a field that overestimates distances.
-    simplify_tolerance, simplify_levels: the final mesh is the one simplified to that tolerance."""
+    simplify_tolerance, simplify_levels: the final mesh is the one simplified to that tolerance.  snap: True or
+    a dict -- the vertices of the final mesh are put back on the zero set first (`sdf_amd/deviation.py`), so a
+    simplified mesh can be probed with the default `start`."""
     from . import core
     if simplify is not None:
         generate_kwargs['simplify'] = simplify
     generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
     if mend is not False:
         generate_kwargs['mend'] = mend
+    if snap is not False:
+        generate_kwargs['snap'] = snap
     check_params(1.0 if normal_eps is None else normal_eps, 1.0 if start is None else start, 1.0 if min_step is None else min_step,
                  np.finfo(np.float64).max if t_far is None else t_far, step_scale, max_steps, refine)      # (what can be refused before meshing)
     with core.meshed(sdf, keep=keep, **generate_kwargs) as m:

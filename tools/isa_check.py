@@ -8,10 +8,11 @@ built with `-mllvm -structurizecfg-skip-uniform-regions=1`; a toolchain that dro
 fault on the device, and one that applies it to the OTHER kernels has miscompiled a divergent loop before (k_expand, r03).  This
 script takes the gfx950 code objects out of the library's offload bundles, disassembles them (llvm-objdump) and checks, per kernel:
 
-  * every tape-interpreter kernel (k_mesh, k_skip*, k_eval_*, k_estimate_bounds, k_render, k_vertex_normals, k_vertex_thickness, k_support_rays) contains `s_setpc_b64` (the interval interpreters
+  * every tape-interpreter kernel (k_mesh, k_skip*, k_eval_*, k_estimate_bounds, k_render, k_vertex_normals, k_vertex_thickness, k_support_rays, k_triangle_deviation,
+    k_vertex_snap) contains `s_setpc_b64` (the interval interpreters
     k_cull* / k_prune_list dispatch through a switch and are listed only);
   * no kernel of the plain translation units (k_compact, k_scan_*, k_emit2, k_expand, k_pack_slab, k_mc_*, k_field_*, k_stl, k_ply_*,
-    k_cast_f32, k_collect_headers, k_ls_*, k_edt_*) contains one -- they must not have been built with the interpreters' option;
+    k_gather_soup, k_cast_f32, k_collect_headers, k_ls_*, k_edt_*) contains one -- they must not have been built with the interpreters' option;
   * every kernel the host launches is there at all;
   * the bounds estimate (k_estimate_bounds_w: 64 workgroups of ONE wave that meet through device memory, csrc/sdf_bounds.hip) contains no
     `s_barrier`.
@@ -43,10 +44,11 @@ def find_objdump():
 
 
 OBJDUMP = find_objdump()
-INTERP = ('k_mesh', 'k_skip', 'k_eval_points', 'k_eval_grid', 'k_eval_tiles', 'k_estimate_bounds', 'k_render', 'k_vertex_normals', 'k_vertex_thickness', 'k_support_rays')
+INTERP = ('k_mesh', 'k_skip', 'k_eval_points', 'k_eval_grid', 'k_eval_tiles', 'k_estimate_bounds', 'k_render', 'k_vertex_normals', 'k_vertex_thickness', 'k_support_rays',
+          'k_triangle_deviation', 'k_vertex_snap')
 INTERVAL = ('k_cull', 'k_prune_list')       # the interval-arithmetic interpreters (sdf_interval.h): a switch, no jump table
 PLAIN = ('k_compact', 'k_scan_rows', 'k_scan_items', 'k_emit2', 'k_expand', 'k_pack_slab', 'k_mc_rows', 'k_mc_emit', 'k_field_rows',
-         'k_field_emit', 'k_stl', 'k_ply_vertices', 'k_ply_faces', 'k_cast_f32', 'k_collect_headers', 'k_ls_dist', 'k_ls_sign', 'k_ls_parity', 'k_ls_compose', 'k_ls_crop', 'k_edt_scan', 'k_edt_min')
+         'k_field_emit', 'k_stl', 'k_ply_vertices', 'k_ply_faces', 'k_gather_soup', 'k_cast_f32', 'k_collect_headers', 'k_ls_dist', 'k_ls_sign', 'k_ls_parity', 'k_ls_compose', 'k_ls_crop', 'k_edt_scan', 'k_edt_min')
 
 
 def code_objects(path):
