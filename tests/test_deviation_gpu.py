@@ -19,6 +19,8 @@ from sdf_amd.mesh import Mesh
 pytestmark = pytest.mark.gpu
 
 # plain family, trig family (twice), smooth unions, the largest register files
+# (opcode coverage lives in the sweep, tests/test_probe_sweep_gpu.py: every tape of the suite goes through this kernel there; these few
+# models walk the kernel's own states)
 MODELS = ('ex_example', 'ex_gearlike', 'twist', 'ex_blobby', 'slots_plain_8_8_p8d8')
 LIBM_FREE = ('ex_example', 'ex_blobby', 'torus')
 SAMPLES = 2 ** 13

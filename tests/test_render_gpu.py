@@ -16,6 +16,8 @@ pytestmark = pytest.mark.gpu
 
 R = importlib.import_module('sdf_amd.render')       # (the package attribute `sdf_amd.render` is the function)
 # plain family, trig family (twice), smooth unions, the longest tape of the examples, the largest register files
+# (opcode coverage lives in the sweep, tests/test_probe_sweep_gpu.py: every tape of the suite goes through this kernel there; these few
+# models walk the kernel's own states)
 MODELS = ('ex_example', 'ex_gearlike', 'twist', 'ex_blobby', 'ex_knurling', 'slots_plain_8_8_p8d8')
 # whole tiles; ragged in both directions; one tile; one pixel; one row of tiles; one column of tiles
 SIZES = ((48, 32), (45, 19), (8, 8), (1, 1), (64, 1), (1, 64))
