@@ -4,17 +4,15 @@
 // over the interpreter that sdf_eval_points runs: float64, one rounding per written operation (-ffp-contract=off), divisions where the
 // definition divides, dot = (x*x + y*y) + z*z, a sample point is (A*wa + B*wb) + C*wc, a Newton step is q - s * g.
 //
-// k_triangle_deviation: one triangle of the float64 soup per lane (no weld, like the moments).  k_vertex_snap: one welded vertex per
-// lane, like k_vertex_normals.  In both the interpreter is inlined ONCE, inside one loop whose counters are wave-uniform: the samples
-// of the lattice in the one, in the other the phases value -> six gradient passes -> value -> ... -> final value, left early when
-// `__any(status == ITER)` says no lane has work.  Lanes never branch around the interpreter -- this unit is built with the
-// structurizer option that is only safe for wave-uniform control flow (build.units) -- they take their state changes by selects: a
-// lane that is done keeps evaluating at its frozen point and discards the value.  A lane beyond the last item evaluates the last item
-// and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
+// Two probe kernels (sdf_probe.h has the doctrine).  k_triangle_deviation: one triangle of the float64 soup per lane (no weld, like
+// the moments), one phase -- the samples of the lattice.  k_vertex_snap: one welded vertex per lane, the phases value -> six gradient
+// passes -> value -> ... -> final value, left early when `__any(status == ITER)` says no lane has work; a lane that is done evaluates
+// at its frozen point.
 #include <cmath>
 
 #include "sdf_interp.h"
 #include "sdf_deviation.h"
+#include "sdf_probe.h"
 
 using namespace sdfk;
 
@@ -71,17 +69,16 @@ __global__ __launch_bounds__(256) void k_vertex_snap(const uint32_t *__restrict_
     const long long l = live ? i : n - 1;
     const double px = pts[3 * l], py = pts[3 * l + 1], pz = pts[3 * l + 2];
     double qx = px, qy = py, qz = pz;
-    double gp = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0, v0 = 0.0, res = 0.0;
+    Grad g = {0.0, 0.0, 0.0, 0.0};
+    double v0 = 0.0, res = 0.0;
     int status = S_ITER, evals = 0;
     int pass = 0, k = 0;                                               // (wave-uniform, like every condition on them below)
     for (;;) {
-        // where this phase evaluates: q (k = 0), or q moved by +-eps along axis (k - 1) / 2, + eps then - eps
+        // where this phase evaluates: q (k = 0), or gradient pass k - 1 around q
         double x = qx, y = qy, z = qz;
         if (k > 0) {
-            const double h = ((k - 1) & 1) ? -a.eps : a.eps;
-            if (((k - 1) >> 1) == 0) x = x + h;
-            else if (((k - 1) >> 1) == 1) y = y + h;
-            else z = z + h;
+            const P3 p = grad_point(k - 1, a.eps, qx, qy, qz);
+            x = p.x; y = p.y; z = p.z;
         }
         const double v = (double)run_tape1<T, FULL>(code, consts, (T)x, (T)y, (T)z);
         const bool it = status == S_ITER;
@@ -102,17 +99,17 @@ __global__ __launch_bounds__(256) void k_vertex_snap(const uint32_t *__restrict_
             if (!__any(status == S_ITER)) break;
             k = 1;
         } else {
-            const double g = gp - v;
-            if (k == 2) g0 = g;
-            else if (k == 4) g1 = g;
-            else if (k == 6) g2 = g;
-            gp = v;
+            const double d = g.gp - v;                                 // (grad_take spelt out: through the helper this kernel compiles to
+            if (k == 2) g.g0 = d;                                      // other instructions, profiles/probe_spine_refactor.md)
+            else if (k == 4) g.g1 = d;
+            else if (k == 6) g.g2 = d;
+            g.gp = v;
             if (k == 6) {
                 evals += it ? 6 : 0;
-                const double len2 = (g0 * g0 + g1 * g1) + g2 * g2;
-                const bool flat = len2 == 0.0 || len2 != len2;
+                const double len2 = grad_len2(g.g0, g.g1, g.g2);
+                const bool flat = grad_flat(len2);
                 const double s = (v0 * a.two_eps) / len2;              // the Newton step v * grad / |grad|^2
-                const double nx = qx - s * g0, ny = qy - s * g1, nz = qz - s * g2;
+                const double nx = qx - s * g.g0, ny = qy - s * g.g1, nz = qz - s * g.g2;
                 const double dx = nx - px, dy = ny - py, dz = nz - pz;
                 const bool far = sqrt((dx * dx + dy * dy) + dz * dz) > a.max_move;
                 const bool move = it && !flat && !far;

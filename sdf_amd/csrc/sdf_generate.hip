@@ -1,6 +1,6 @@
 // sdf_generate.hip -- the generate pipeline of libsdf_hip.so's C ABI (gfx950 only): one call descriptor (GenCall, sdf_internal.h) from the
 // entry points sdf_generate* through a call slot, the axes' staging, the prepass, the meshing attempts and the statistics, to a mesh
-// handle.  The rest of the ABI: sdf_ctx.hip (contexts, tapes), sdf_eval.hip, sdf_runtime.hip, sdf_chunked.hip, sdf_mesh_out.hip,
+// handle.  The rest of the ABI: sdf_ctx.hip (contexts, tapes), sdf_eval.hip, sdf_runtime.hip, sdf_chunked.hip, sdf_mesh_out.hip, sdf_probe_out.hip,
 // sdf_comm.hip and the features' own units.
 //
 // Host code only: it launches through enqueue_prepass / enqueue_cull (sdf_prepass.hip), the k_mesh launchers of sdf_mesh_inst.hip and

@@ -190,8 +190,30 @@ int generate_impl(sdf_mesh *m, const GenCall &call);
 int finish_call(sdf_mesh *m, const GenCall &call, const CallState &s, bool stats_if_short, sdfk::MeshCounters &h);
 // ---- sdf_chunked.hip (batch_size > 32: through device memory, a chunk of batches per submission) ----
 int generate_big(sdf_mesh *m, const GenCall &call);
-// ---- sdf_mesh_out.hip ----
+// ---- sdf_mesh_out.hip, and what it shares with the other reader of a finished mesh, sdf_probe_out.hip ----
 int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes);
+// every reader of a mesh first collects a call that is still in flight
+#define MESH_READY(m) do { if ((m)->pend.active && sdf_mesh_wait((m), nullptr)) return 1; } while (0)
+
+// where the soup of a mesh lives: the caller's buffer of sdf_generate_to_device, or the library's
+static inline const void *mesh_soup(const sdf_mesh *m) { return m->emitted_to ? m->emitted_to : m->out.p; }
+
+// a mesh of sdf_generate_records holds 16-byte records; a reader that wants the float64 soup on the device gets it from k_expand, once
+int ensure_soup(sdf_mesh *m);
+#define MESH_SOUP_READY(m) do { if (ensure_soup(m)) return 1; } while (0)
+
+// the refusals every entry that takes build directions shares; 0 when the arguments are in order, else 1 with the message set
+int overhang_refused(const char *who, const double *h_dirs, long long n_dirs, double sin_limit, double bed_tol);
+
+// the mesh an entry derives from `from` (a selection, a simplified, mended or snapped mesh): like an adopted soup for every reader, but
+// it OWNS the soup -- `out` goes back to the pool with the mesh
+static inline sdf_mesh *derived_mesh(const sdf_mesh *from, const DevBuf &soup, int64_t n_triangles) {
+    sdf_mesh *d = new sdf_mesh();
+    d->ctx = from->ctx;
+    d->out = soup;
+    d->st.n_triangles = n_triangles;
+    return d;
+}
 // ---- sdf_weld.hip: pts = n rows of 3 doubles on the device; on success *d_uniq holds 3 * *n_unique doubles and *d_inv n int64; a
 // failed call leaves both empty.  0, or 1 with the message set ----
 namespace sdfk {

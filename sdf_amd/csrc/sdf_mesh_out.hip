@@ -1,7 +1,9 @@
-// sdf_mesh_out.hip -- what reads a finished mesh: collecting a call in flight, statistics, the soup on the device and on the host
-// (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, field normals and the wall thickness at the
-// welded vertices, the deviation of the triangles from the field and the vertices snapped onto it, binary PLY records, the moments and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build directions, kinds, prune masks, and the end
-// of a mesh.  Launches only through the launchers of sdf_plain.h, sdf_normals.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h, sdf_supports.h, sdf_thickness.h, sdf_deviation.h and sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
+// sdf_mesh_out.hip -- what reads a finished mesh and needs no tape: collecting a call in flight, statistics, the soup on the device and
+// on the host (float64, 16-byte records expanded by host threads, STL records), batch offsets, the weld, binary PLY records, the moments
+// and the edge census, the connected shells and a selection of them, the simplified mesh, the mended mesh, the rating of build
+// directions, kinds, prune masks, and the end of a mesh.  (The entries that take a tape to the mesh live in sdf_probe_out.hip.)
+// Launches only through the launchers of sdf_plain.h, sdf_measure.h, sdf_components.h, sdf_simplify.h, sdf_mend.h, sdf_overhang.h and
+// sdf_weld.hip: built WITHOUT the interpreters' structurizer option (build.units).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -9,27 +11,17 @@
 
 #include "sdf_internal.h"
 #include "sdf_components.h"
-#include "sdf_deviation.h"
 #include "sdf_expand_host.h"   // (+ <chrono>, <cstring>, <mutex>, <thread>)
 #include "sdf_measure.h"
 #include "sdf_mend.h"
-#include "sdf_normals.h"
 #include "sdf_overhang.h"
 #include "sdf_plain.h"
 #include "sdf_simplify.h"
-#include "sdf_supports.h"
-#include "sdf_thickness.h"
 
 using namespace sdfk;
 
-// every reader of a mesh first collects a call that is still in flight
-#define MESH_READY(m) do { if ((m)->pend.active && sdf_mesh_wait((m), nullptr)) return 1; } while (0)
-
-// where the soup of a mesh lives: the caller's buffer of sdf_generate_to_device, or the library's
-static const void *mesh_soup(const sdf_mesh *m) { return m->emitted_to ? m->emitted_to : m->out.p; }
-
-// a mesh of sdf_generate_records holds 16-byte records; a reader that wants the float64 soup on the device gets it from k_expand, once
-static int ensure_soup(sdf_mesh *m) {
+// (sdf_internal.h) the float64 soup of a records mesh, made on the device by k_expand, once
+int ensure_soup(sdf_mesh *m) {
     if (!m->records || m->out.p || m->st.n_triangles == 0) return 0;
     sdf_ctx *c = m->ctx;
     HIPCHK(set_device(c->device));
@@ -39,7 +31,6 @@ static int ensure_soup(sdf_mesh *m) {
     HIPCHK((hipError_t)sdf_launch_expand(c->stream, ptrs, 1, m->slab_items, m->slab_tris, (double *)m->out.p, (unsigned long long)m->st.n_triangles));
     return 0;
 }
-#define MESH_SOUP_READY(m) do { if (ensure_soup(m)) return 1; } while (0)
 
 // (Cutting a large device-to-host copy into pieces that travel on several streams at once was measured in r02: the
 // 212 MB soup took 7.7 ms as one copy, 8.7 ms as two, 9.8 ms as four -- one copy already runs at the link's rate for
@@ -51,11 +42,21 @@ int copy_to_host(sdf_ctx *c, void *h_dst, const void *d_src, size_t bytes) {
     return 0;
 }
 
-// what sdf_mesh_support_rays leaves behind: one device block per direction that has rays
-struct sdf_support_rays {
-    sdf_ctx *ctx = nullptr;
-    std::vector<SupportRaysDir> dirs;
-};
+// (sdf_internal.h) the refusals of a list of build directions: the overhang entries below, sdf_mesh_support_rays
+int overhang_refused(const char *who, const double *h_dirs, long long n_dirs, double sin_limit, double bed_tol) {
+    const std::string w(who);
+    if (n_dirs < 1) return fail(w + ": n_dirs must be at least 1");
+    if (n_dirs > OVERHANG_MAX_DIRS) return fail(w + ": more than 2^20 directions");
+    if (!(sin_limit >= 0.0 && sin_limit < 1.0)) return fail(w + ": sin_limit must lie in [0, 1)");
+    if (!(bed_tol >= 0.0)) return fail(w + ": bed_tol must not be negative or NaN");
+    for (long long k = 0; k < n_dirs; k++) {
+        const double x = h_dirs[3 * k], y = h_dirs[3 * k + 1], z = h_dirs[3 * k + 2];
+        const double len = std::sqrt((x * x + y * y) + z * z);
+        if (!(std::fabs(len - 1.0) <= 1e-12))                          // (a NaN or an infinite component fails this too)
+            return fail(w + ": direction " + std::to_string(k) + " is zero, not finite or not of unit length to 1e-12");
+    }
+    return 0;
+}
 
 extern "C" {
 
@@ -319,193 +320,6 @@ int sdf_mesh_weld_fetch(sdf_mesh *m, double *h_points, int64_t *h_cells) {
     return 0;
 }
 
-// ---- the indexed export: field normals at the welded vertices, binary PLY records ----
-static thread_local double g_normals_kernel_ms = 0.0;
-
-int sdf_mesh_vertex_normals(sdf_mesh *m, sdf_tape *t, double eps, double *h_normals, int64_t *n_flat) {
-    if (!m || !t || !n_flat) { fail("sdf_mesh_vertex_normals: NULL argument"); return 2; }
-    if (!(std::isfinite(eps) && eps > 0.0)) { fail("sdf_mesh_vertex_normals: eps must be finite and positive"); return 2; }
-    if (t->n_extern) { fail("sdf_mesh_vertex_normals: the tape reads user closures (L_EXTERN): take the normals over sdf_eval_points_extern_host"); return 2; }
-    if (m->weld_n < 0) { fail("sdf_mesh_vertex_normals: call sdf_mesh_weld first"); return 2; }
-    if (t->ctx != m->ctx) { fail("sdf_mesh_vertex_normals: the tape and the mesh belong to different contexts"); return 2; }
-    sdf_ctx *c = m->ctx;
-    const long long nu = m->weld_n;
-    *n_flat = 0;
-    if (nu == 0) { m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps; m->nrm_flat = 0; return 0; }
-    HIPCHK(set_device(c->device));
-    if (!(m->nrm_valid && m->nrm_model == t->content_hash && m->nrm_eps == eps)) {
-        m->nrm_valid = false;
-        static const char who[] = "sdf_mesh_vertex_normals: ";
-        if (!m->nrm) HIPCHK_MSG(std::string(who) + "hipMalloc(" + std::to_string((size_t)nu * 24 + 8) + "): ", m->nrm.alloc((size_t)nu * 24 + 8, c->stream));
-        double *nrm = m->nrm.as<double>();
-        unsigned long long *d_flat = reinterpret_cast<unsigned long long *>(nrm + 3 * nu);
-        EventTimer timer;
-        HIPCHK_MSG(who, hipMemsetAsync(d_flat, 0, 8, c->stream));
-        HIPCHK_MSG(who, timer.start(c->stream));
-        HIPCHK_MSG(who, (hipError_t)launch_vertex_normals(c->stream, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, eps, nrm, d_flat));
-        HIPCHK_MSG(who, timer.stop(c->stream));
-        // (the count lands in the mesh, not on this stack: a call that fails on the way out leaves no copy in flight to a dead frame)
-        HIPCHK_MSG(who, hipMemcpyAsync(&m->nrm_flat, d_flat, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK_MSG(who, stream_wait(c->stream));
-        HIPCHK_MSG(who, timer.ms(&g_normals_kernel_ms));
-        m->nrm_valid = true; m->nrm_model = t->content_hash; m->nrm_eps = eps;
-    }
-    *n_flat = (int64_t)m->nrm_flat;
-    if (h_normals) return copy_to_host(c, h_normals, m->nrm.as<double>(), (size_t)nu * 24);
-    return 0;
-}
-
-double sdf_mesh_normals_last_kernel_ms(void) { return g_normals_kernel_ms; }
-
-// ---- the wall thickness at the welded vertices: inward rays through the solid ----
-static thread_local double g_thickness_kernel_ms = 0.0;
-
-int sdf_mesh_vertex_thickness(sdf_mesh *m, sdf_tape *t, const double *params6, int max_steps, int refine, double *h_thickness,
-                              uint8_t *h_status, int32_t *h_steps) {
-    auto refuse = [](const std::string &why) { fail("sdf_mesh_vertex_thickness: " + why); return 2; };
-    if (!m || !t || !params6 || !h_thickness || !h_status || !h_steps) return refuse("NULL argument");
-    if (m->weld_n < 0) return refuse("call sdf_mesh_weld first");
-    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
-    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip");
-    for (int i = 0; i < 6; i++) if (!std::isfinite(params6[i])) return refuse("the parameters are not finite");
-    ThicknessArgs a;
-    a.normal_eps = params6[0]; a.start = params6[1]; a.min_step = params6[2]; a.t_far = params6[3]; a.step_scale = params6[4];
-    a.max_steps = max_steps; a.refine = refine;
-    if (!(a.normal_eps > 0.0)) return refuse("normal_eps must be positive");
-    if (!(a.start > 0.0)) return refuse("start must be positive");
-    if (!(a.min_step > 0.0)) return refuse("min_step must be positive");
-    if (!(a.step_scale > 0.0 && a.step_scale <= 1.0)) return refuse("step_scale must lie in (0, 1]");
-    if (a.t_far < a.start) return refuse("t_far lies before start");
-    if (max_steps < 1) return refuse("max_steps must be at least 1");
-    if (refine < 0) return refuse("refine must not be negative");
-    const long long nu = m->weld_n;
-    if (nu == 0) return 0;
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    hipStream_t st = c->stream;
-    double *thick;
-    int32_t *steps;
-    uint8_t *status;
-    Scratch scratch(st);
-    scratch.part(&thick, (size_t)nu); scratch.part(&steps, (size_t)nu); scratch.part(&status, (size_t)nu);
-    EventTimer timer;
-    HIPCHK_MSG("sdf_mesh_vertex_thickness: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
-    HIPCHK_FN(timer.start(st));
-    HIPCHK_FN((hipError_t)launch_vertex_thickness(st, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, a, thick, status, steps));
-    HIPCHK_FN(timer.stop(st));
-    HIPCHK_FN(hipMemcpyAsync(h_thickness, thick, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(hipMemcpyAsync(h_status, status, (size_t)nu, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(hipMemcpyAsync(h_steps, steps, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(stream_wait(st));
-    HIPCHK_FN(timer.ms(&g_thickness_kernel_ms));
-    return 0;
-}
-
-double sdf_mesh_thickness_last_kernel_ms(void) { return g_thickness_kernel_ms; }
-
-// ---- a mesh held to the field: the deviation of every triangle, the welded vertices snapped onto the zero set ----
-static thread_local double g_deviation_kernel_ms = 0.0;
-
-int sdf_mesh_triangle_deviation(sdf_mesh *m, sdf_tape *t, int order, double *h_dev, int32_t *h_at, double *h_sumsq) {
-    auto refuse = [](const std::string &why) { fail("sdf_mesh_triangle_deviation: " + why); return 2; };
-    if (!m || !t || !h_dev || !h_at || !h_sumsq) return refuse("NULL argument");
-    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
-    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): take the deviation over sdf_eval_points_extern_host");
-    if (order < 1 || order > 8) return refuse("order must lie in 1 .. 8");
-    MESH_READY(m);
-    const long long nt = (long long)m->st.n_triangles;
-    if (nt >= (1ll << 31)) return refuse("2^31 or more triangles");
-    if (nt == 0) return 0;
-    MESH_SOUP_READY(m);
-    sdf_ctx *c = m->ctx;
-    HIPCHK(set_device(c->device));
-    hipStream_t st = c->stream;
-    double *dev, *sumsq;
-    int32_t *at;
-    Scratch scratch(st);
-    scratch.part(&dev, (size_t)nt); scratch.part(&sumsq, (size_t)nt); scratch.part(&at, (size_t)nt);
-    EventTimer timer;
-    HIPCHK_MSG("sdf_mesh_triangle_deviation: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
-    HIPCHK_FN(timer.start(st));
-    HIPCHK_FN((hipError_t)launch_triangle_deviation(st, t->d_code, t->d_c64, t->full, (const double *)mesh_soup(m), nt, order, dev, at, sumsq));
-    HIPCHK_FN(timer.stop(st));
-    HIPCHK_FN(hipMemcpyAsync(h_dev, dev, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(hipMemcpyAsync(h_at, at, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(hipMemcpyAsync(h_sumsq, sumsq, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK_FN(stream_wait(st));
-    HIPCHK_FN(timer.ms(&g_deviation_kernel_ms));
-    return 0;
-}
-
-double sdf_mesh_deviation_last_kernel_ms(void) { return g_deviation_kernel_ms; }
-
-int sdf_mesh_snap(sdf_mesh *m, sdf_tape *t, const double *params4, int iters, sdf_mesh **out, double *h_points, uint8_t *h_status,
-                  double *h_residual, int32_t *h_evals, sdf_snap_stats *stats) {
-    auto refuse = [](const std::string &why) { fail("sdf_mesh_snap: " + why); return 2; };
-    if (!m || !t || !params4 || !out || !stats) return refuse("NULL argument");
-    if (m->weld_n < 0) return refuse("call sdf_mesh_weld first");
-    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
-    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every pass would need a host round trip");
-    for (int i = 0; i < 4; i++) if (!std::isfinite(params4[i])) return refuse("the parameters are not finite");
-    SnapArgs a;
-    a.eps = params4[0]; a.two_eps = 2.0 * params4[0]; a.tol = params4[1]; a.max_move = params4[2]; a.iters = iters;
-    if (!(a.eps > 0.0)) return refuse("eps must be positive");
-    if (!(a.tol >= 0.0)) return refuse("tol must not be negative");
-    if (!(a.max_move >= 0.0)) return refuse("max_move must not be negative");
-    if (iters < 1) return refuse("iters must be at least 1");
-    const long long nu = m->weld_n, nt = (long long)m->st.n_triangles;
-    sdf_snap_stats got = sdf_snap_stats();
-    got.vertices = (int64_t)nu;
-    DevBuf soup;                                                       // the moved vertices' own soup: the new mesh's `out`
-    if (nu > 0 && nt > 0) {                                            // (nothing to move: a mesh of 0 triangles, no launch)
-        sdf_ctx *c = m->ctx;
-        HIPCHK(set_device(c->device));
-        hipStream_t st = c->stream;
-        double *q, *residual;
-        int32_t *evals;
-        uint8_t *status;
-        Scratch scratch(st);
-        scratch.part(&q, (size_t)nu * 3); scratch.part(&residual, (size_t)nu); scratch.part(&evals, (size_t)nu); scratch.part(&status, (size_t)nu);
-        std::vector<uint8_t> codes((size_t)nu);
-        EventTimer timer;
-        HIPCHK_MSG("sdf_mesh_snap: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
-        if (soup.ensure((size_t)nt * 72)) return 1;
-        // (from here on a failure hands the soup back: the scratch block drains the stream before it goes)
-        static const char who[] = "sdf_mesh_snap: ";
-        auto run = [&]() -> int {
-            HIPCHK_MSG(who, timer.start(st));
-            HIPCHK_MSG(who, (hipError_t)launch_vertex_snap(st, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, a, q, status, residual, evals));
-            HIPCHK_MSG(who, timer.stop(st));
-            launch_k_gather_soup(dim3(blocks_of(9 * nt)), dim3(256), st, q, m->weld_inv.as<long long>(), 9 * nt, (double *)soup.p);
-            HIPCHK_MSG(who, hipGetLastError());
-            HIPCHK_MSG(who, hipMemcpyAsync(codes.data(), status, (size_t)nu, hipMemcpyDeviceToHost, st));
-            if (h_points) HIPCHK_MSG(who, hipMemcpyAsync(h_points, q, (size_t)nu * 24, hipMemcpyDeviceToHost, st));
-            if (h_residual) HIPCHK_MSG(who, hipMemcpyAsync(h_residual, residual, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
-            if (h_evals) HIPCHK_MSG(who, hipMemcpyAsync(h_evals, evals, (size_t)nu * 4, hipMemcpyDeviceToHost, st));
-            return 0;
-        };
-        const int rc = run();
-        const hipError_t e = stream_wait(st);                          // (before `codes` goes, whatever the copies said)
-        if (rc || e != hipSuccess) {
-            soup.release();
-            if (!rc) HIPCHK_FN(e);
-            return 1;
-        }
-        if (timer.ms(&got.kernel_ms) != hipSuccess) got.kernel_ms = 0.0;
-        int64_t n[5] = {0, 0, 0, 0, 0};
-        for (long long i = 0; i < nu; i++) n[codes[(size_t)i] < 5 ? codes[(size_t)i] : 0]++;
-        got.left = n[0]; got.snapped = n[1]; got.held = n[2]; got.flat = n[3]; got.nan = n[4];
-        if (h_status) memcpy(h_status, codes.data(), (size_t)nu);
-    }
-    sdf_mesh *s = new sdf_mesh();                                      // (like a simplified mesh: it owns the soup, `out` goes back to the pool with the mesh)
-    s->ctx = m->ctx;
-    s->out = soup;
-    s->st.n_triangles = soup.p ? (int64_t)nt : 0;
-    *stats = got;
-    *out = s;
-    return 0;
-}
-
 // ---- the mesh measured on the device: moments of the soup, edge census of the welded cells ----
 static thread_local double g_measure_kernel_ms = 0.0;
 
@@ -608,11 +422,7 @@ int sdf_mesh_select_shells(sdf_mesh *m, const unsigned char *h_keep, int64_t n_k
             return 1;
         }
     }
-    sdf_mesh *sel = new sdf_mesh();                                    // (like an adopted soup for every reader, but it owns the soup:
-    sel->ctx = m->ctx;                                                 // `out` goes back to the pool with the mesh)
-    sel->out = soup;
-    sel->st.n_triangles = (int64_t)kept;
-    *out = sel;
+    *out = derived_mesh(m, soup, (int64_t)kept);
     return 0;
 }
 
@@ -643,11 +453,7 @@ int sdf_mesh_simplify(sdf_mesh *m, const double *origin3, const double *cell3, d
             return 1;
         }
     }
-    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
-    s->ctx = m->ctx;
-    s->out = soup;
-    s->st.n_triangles = stats->triangles_out;
-    *out = s;
+    *out = derived_mesh(m, soup, stats->triangles_out);
     return 0;
 }
 
@@ -690,11 +496,7 @@ int sdf_mesh_simplify_adaptive(sdf_mesh *m, const double *origin3, const double 
             return 1;
         }
     }
-    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
-    s->ctx = m->ctx;
-    s->out = soup;
-    s->st.n_triangles = stats->triangles_out;
-    *out = s;
+    *out = derived_mesh(m, soup, stats->triangles_out);
     return 0;
 }
 
@@ -727,11 +529,7 @@ int sdf_mesh_mend(sdf_mesh *m, sdf_mesh **out, sdf_mend_stats *stats) {
             return 1;
         }
     }
-    sdf_mesh *s = new sdf_mesh();                                      // (like a selection: it owns the soup, `out` goes back to the pool with the mesh)
-    s->ctx = m->ctx;
-    s->out = soup;
-    s->st.n_triangles = stats->triangles_out;
-    *out = s;
+    *out = derived_mesh(m, soup, stats->triangles_out);
     return 0;
 }
 
@@ -743,22 +541,6 @@ double sdf_mesh_mend_last_kernel_ms(double *parts3) {
 // ---- build directions rated: extents, overhang and bed-contact totals per direction, classes per triangle ----
 static thread_local double g_overhang_kernel_ms = 0.0;
 static thread_local long long g_overhang_slabs = 0;
-
-// the refusals both entries share; 0 when the arguments are in order
-static int overhang_refused(const char *who, const double *h_dirs, long long n_dirs, double sin_limit, double bed_tol) {
-    const std::string w(who);
-    if (n_dirs < 1) return fail(w + ": n_dirs must be at least 1");
-    if (n_dirs > OVERHANG_MAX_DIRS) return fail(w + ": more than 2^20 directions");
-    if (!(sin_limit >= 0.0 && sin_limit < 1.0)) return fail(w + ": sin_limit must lie in [0, 1)");
-    if (!(bed_tol >= 0.0)) return fail(w + ": bed_tol must not be negative or NaN");
-    for (long long k = 0; k < n_dirs; k++) {
-        const double x = h_dirs[3 * k], y = h_dirs[3 * k + 1], z = h_dirs[3 * k + 2];
-        const double len = std::sqrt((x * x + y * y) + z * z);
-        if (!(std::fabs(len - 1.0) <= 1e-12))                          // (a NaN or an infinite component fails this too)
-            return fail(w + ": direction " + std::to_string(k) + " is zero, not finite or not of unit length to 1e-12");
-    }
-    return 0;
-}
 
 int sdf_mesh_overhangs(sdf_mesh *m, const double *h_dirs, int64_t n_dirs, double sin_limit, double bed_tol, size_t max_scratch_bytes,
                        double *h_values, int64_t *h_counts) {
@@ -799,82 +581,7 @@ double sdf_overhang_last_kernel_ms(int64_t *n_slabs) {
     return g_overhang_kernel_ms;
 }
 
-// ---- support rays through the field: the true support volume per build direction ----
-static thread_local double g_supports_ms[4] = {0.0, 0.0, 0.0, 0.0};
-
-int sdf_mesh_support_rays(sdf_mesh *m, sdf_tape *t, const double *h_dirs, int64_t n_dirs, const double *params8, int max_steps, int refine,
-                          sdf_support_rays **out, double *h_values, int64_t *h_counts) {
-    auto refuse = [](const std::string &why) { fail("sdf_mesh_support_rays: " + why); return 2; };
-    if (out) *out = nullptr;
-    if (!m || !t || !h_dirs || !params8 || !out || !h_values || !h_counts) return refuse("NULL argument");
-    if (t->ctx != m->ctx) return refuse("the tape and the mesh belong to different contexts");
-    if (t->n_extern) return refuse("the tape reads user closures (L_EXTERN): every step of every ray would need a host round trip");
-    for (int i = 0; i < 8; i++) if (!std::isfinite(params8[i])) return refuse("the parameters are not finite");
-    SupportParams p;
-    p.sin_limit = params8[0]; p.bed_tol = params8[1]; p.start = params8[2]; p.min_step = params8[3]; p.step_scale = params8[4];
-    p.max_steps = max_steps; p.refine = refine;
-    if (!(p.start > 0.0)) return refuse("start must be positive");
-    if (!(p.min_step > 0.0)) return refuse("min_step must be positive");
-    if (!(p.step_scale > 0.0 && p.step_scale <= 1.0)) return refuse("step_scale must lie in (0, 1]");
-    if (max_steps < 1) return refuse("max_steps must be at least 1");
-    if (refine < 0) return refuse("refine must not be negative");
-    if (n_dirs > SUPPORT_MAX_DIRS) return refuse("more than 1024 directions");
-    if (overhang_refused("sdf_mesh_support_rays", h_dirs, (long long)n_dirs, p.sin_limit, p.bed_tol)) return 2;
-    MESH_READY(m);
-    if ((long long)m->st.n_triangles >= (1ll << 31)) return refuse("2^31 or more triangles");
-    if (m->st.n_triangles > 0 && !mesh_soup(m) && !m->records) return refuse("the mesh has no soup on the device");
-    for (int k = 0; k < 4; k++) g_supports_ms[k] = 0.0;
-    for (int64_t k = 0; k < n_dirs; k++) {                             // the empty result: no launch for a mesh of 0 triangles
-        h_values[7 * k] = INFINITY; h_values[7 * k + 1] = -INFINITY;
-        for (int c = 2; c < 7; c++) h_values[7 * k + c] = 0.0;
-        for (int c = 0; c < 6; c++) h_counts[6 * k + c] = 0;
-    }
-    sdf_support_rays *res = new sdf_support_rays();
-    struct Guard { sdf_support_rays *r; ~Guard() { delete r; } } guard{res};      // (its blocks go back with it)
-    res->ctx = m->ctx;
-    res->dirs.resize((size_t)n_dirs);
-    if (m->st.n_triangles > 0) {
-        MESH_SOUP_READY(m);
-        HIPCHK(set_device(m->ctx->device));
-        if (support_rays_run(m->ctx->stream, t->d_code, t->d_c64, t->full, (const double *)mesh_soup(m), (long long)m->st.n_triangles, h_dirs,
-                             (long long)n_dirs, p, &res->dirs, h_values, h_counts, g_supports_ms)) return 1;
-    }
-    guard.r = nullptr;
-    *out = res;
-    return 0;
-}
-
-int sdf_support_rays_fetch(sdf_support_rays *r, int64_t k, int32_t *h_triangle, double *h_height, uint8_t *h_status, int32_t *h_steps,
-                           double *h_origin) {
-    if (!r) { fail("sdf_support_rays_fetch: NULL argument"); return 2; }
-    if (k < 0 || k >= (int64_t)r->dirs.size()) { fail("sdf_support_rays_fetch: no such direction"); return 2; }
-    const SupportRaysDir &d = r->dirs[(size_t)k];
-    if (d.m < 1) return 0;                                             // nothing on the device
-    sdf_ctx *c = r->ctx;
-    HIPCHK_FN(set_device(c->device));
-    const char *base = d.block.as<char>();
-    const size_t nm = (size_t)d.m;
-    if (h_origin) HIPCHK_FN(hipMemcpyAsync(h_origin, base, nm * 24, hipMemcpyDeviceToHost, c->stream));
-    if (h_height) HIPCHK_FN(hipMemcpyAsync(h_height, base + d.o_height, nm * 8, hipMemcpyDeviceToHost, c->stream));
-    if (h_triangle) HIPCHK_FN(hipMemcpyAsync(h_triangle, base + d.o_triangle, nm * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_steps) HIPCHK_FN(hipMemcpyAsync(h_steps, base + d.o_steps, nm * 4, hipMemcpyDeviceToHost, c->stream));
-    if (h_status) HIPCHK_FN(hipMemcpyAsync(h_status, base + d.o_status, nm, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK_FN(stream_wait(c->stream));
-    return 0;
-}
-
-int sdf_support_rays_destroy(sdf_support_rays *r) {
-    if (!r) return 0;
-    (void)hipSetDevice(r->ctx->device);
-    delete r;
-    return 0;
-}
-
-double sdf_mesh_supports_last_kernel_ms(double *parts4) {
-    for (int k = 0; parts4 && k < 4; k++) parts4[k] = g_supports_ms[k];
-    return g_supports_ms[0] + g_supports_ms[1] + g_supports_ms[2] + g_supports_ms[3];
-}
-
+// ---- the indexed export: binary PLY records of the welded mesh, with the field normals that sdf_mesh_vertex_normals left ----
 int sdf_mesh_emit_ply_host(sdf_mesh *m, int with_normals, void *h_vertices, void *h_faces) {
     if (!m || !h_vertices || !h_faces) { fail("sdf_mesh_emit_ply_host: NULL argument"); return 2; }
     if (m->weld_n < 0) { fail("sdf_mesh_emit_ply_host: call sdf_mesh_weld first"); return 2; }

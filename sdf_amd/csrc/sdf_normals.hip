@@ -4,13 +4,11 @@
 // x_k + eps minus the value at x_k + (-eps), len = sqrt((g0*g0 + g1*g1) + g2*g2), n = g / len by division.  A vertex whose len is 0
 // or NaN is FLAT: its normal is (0, 0, 0) and it is counted.
 //
-// One welded vertex per lane.  The interpreter is inlined ONCE: the six evaluations are passes of one loop whose counter is
-// wave-uniform -- the order of k_render's normal phase (sdf_render.hip): plus first, then minus.  Lanes never branch around the
-// interpreter -- this unit is built with the structurizer option that is only safe for wave-uniform control flow (build.units): a lane
-// beyond the last vertex evaluates at the last vertex and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
+// A probe kernel (sdf_probe.h has the doctrine): one welded vertex per lane, one phase -- the six passes of the central difference.
 // The flat vertices are counted by one integer atomic add per wave that has any.
 #include "sdf_interp.h"
 #include "sdf_normals.h"
+#include "sdf_probe.h"
 
 using namespace sdfk;
 
@@ -24,28 +22,20 @@ __global__ __launch_bounds__(256) void k_vertex_normals(const uint32_t *__restri
     const bool live = i < n;
     const long long j = live ? i : n - 1;
     const double px = pts[3 * j], py = pts[3 * j + 1], pz = pts[3 * j + 2];
-    double gp = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    Grad g = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
-    for (int k = 0; k < 6; k++) {                                      // pass k: axis k / 2, + eps then - eps
-        const double h = (k & 1) ? -eps : eps;
-        double x = px, y = py, z = pz;
-        if ((k >> 1) == 0) x = x + h;
-        else if ((k >> 1) == 1) y = y + h;
-        else z = z + h;
-        const double v = (double)run_tape1<T, FULL>(code, consts, (T)x, (T)y, (T)z);
-        const double g = gp - v;
-        if (k == 1) g0 = g;
-        else if (k == 3) g1 = g;
-        else if (k == 5) g2 = g;
-        gp = v;
+    for (int k = 0; k < 6; k++) {
+        const P3 p = grad_point(k, eps, px, py, pz);
+        const double v = (double)run_tape1<T, FULL>(code, consts, (T)p.x, (T)p.y, (T)p.z);
+        g = grad_take(g, k, v);
     }
-    const double len = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
-    const bool flat = len == 0.0 || len != len;
+    const double len = sqrt(grad_len2(g.g0, g.g1, g.g2));
+    const bool flat = grad_flat(len);
     const unsigned long long flat_lanes = __ballot(live && flat);
     if (live) {
-        out[3 * i] = flat ? 0.0 : g0 / len;
-        out[3 * i + 1] = flat ? 0.0 : g1 / len;
-        out[3 * i + 2] = flat ? 0.0 : g2 / len;
+        out[3 * i] = flat ? 0.0 : g.g0 / len;
+        out[3 * i + 1] = flat ? 0.0 : g.g1 / len;
+        out[3 * i + 2] = flat ? 0.0 : g.g2 / len;
     }
     if (flat_lanes != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_flat, (unsigned long long)__popcll(flat_lanes));
 }

@@ -4,14 +4,11 @@
 // tests/supports_ref.py is the definition; this kernel reproduces it bit for bit over the interpreter that sdf_eval_points runs:
 // float64, one rounding per written operation (-ffp-contract=off), dot = (x*x' + y*y') + z*z', a point on a ray is c + t * nd.
 //
-// k_vertex_thickness (sdf_thickness.hip) turned inside out: it marches while v >= 0 and stops on v < 0.  One overhanging triangle
-// per lane, in triangle order (d_triangle, numbered by the driver in sdf_overhang.hip).  The interpreter is inlined ONCE: the march
-// and the bisection are phases of one loop whose phase and counter are wave-uniform: the march ends when `__any(status == MARCH)` says
-// so or after max_steps passes, REFINE is skipped when no lane of the wave is PART, and a wave whose rays all begin at or below the
-// bed evaluates nothing.  Lanes never branch around the interpreter -- this unit is built with the structurizer option that is only
-// safe for wave-uniform control flow (build.units) -- they take their state changes by selects: a lane that is done keeps evaluating
-// at its frozen parameter and discards the value.  A lane beyond the last ray repeats the last ray and stores nothing; a wave that
-// lies wholly beyond it leaves (wave-uniform).
+// A probe kernel (sdf_probe.h has the doctrine), k_vertex_thickness (sdf_thickness.hip) turned inside out: it marches while v >= 0
+// and stops on v < 0.  One overhanging triangle per lane, in triangle order (d_triangle, numbered by the driver in sdf_overhang.hip),
+// the phases MARCH -> REFINE: the march ends when `__any(status == MARCH)` says so or after max_steps passes, REFINE is skipped when
+// no lane of the wave is PART, and a wave whose rays all begin at or below the bed evaluates nothing.  A lane that is done evaluates
+// at its frozen parameter; a lane beyond the last ray repeats the last ray.
 #include "sdf_interp.h"
 #include "sdf_supports.h"
 

@@ -4,16 +4,13 @@
 // definition; this kernel reproduces it bit for bit over the interpreter that sdf_eval_points runs: float64, one rounding per written
 // operation (-ffp-contract=off), divisions where the definition divides, dot = (x*x + y*y) + z*z, a point on a ray is p + t * d.
 //
-// One welded vertex per lane, like k_vertex_normals.  The interpreter is inlined ONCE: the six evaluations of the normal, the march
-// and the bisection are phases of one loop whose phase and counter are wave-uniform -- k_render's structure (sdf_render.hip) in the
-// order NORMAL -> MARCH -> REFINE: the march ends when `__any(status == MARCH)` says so or after max_steps passes, REFINE is skipped
-// when no lane of the wave is THICK.  Lanes never branch around the interpreter -- this unit is built with the structurizer option
-// that is only safe for wave-uniform control flow (build.units) -- they take their state changes by selects: a lane that is done keeps
-// evaluating at its frozen parameter and discards the value, a FLAT lane (direction 0) evaluates at its vertex.  A lane beyond the
-// last vertex evaluates at the last vertex and stores nothing; a wave that lies wholly beyond it leaves (wave-uniform).
+// A probe kernel (sdf_probe.h has the doctrine): one welded vertex per lane, the phases NORMAL -> MARCH -> REFINE: the march ends
+// when `__any(status == MARCH)` says so or after max_steps passes, REFINE is skipped when no lane of the wave is THICK.  A lane that
+// is done evaluates at its frozen parameter, a FLAT lane (direction 0) at its vertex.
 #include <cmath>
 
 #include "sdf_interp.h"
+#include "sdf_probe.h"
 #include "sdf_thickness.h"
 
 using namespace sdfk;
@@ -32,7 +29,7 @@ __global__ __launch_bounds__(256) void k_vertex_thickness(const uint32_t *__rest
     const bool live = i < n;
     const long long j = live ? i : n - 1;
     const double px = pts[3 * j], py = pts[3 * j + 1], pz = pts[3 * j + 2];
-    double gp = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    Grad g = {0.0, 0.0, 0.0, 0.0};
     double dx = 0.0, dy = 0.0, dz = 0.0;
     double t = a.start, lo = 0.0, hi = a.start;
     int status = W_MARCH, steps = 0;
@@ -43,27 +40,24 @@ __global__ __launch_bounds__(256) void k_vertex_thickness(const uint32_t *__rest
         const bool fix = status == W_THICK;
         const double s = (phase == PH_REFINE && fix) ? mid : t;
         double x = px + s * dx, y = py + s * dy, z = pz + s * dz;
-        if (phase == PH_NORMAL) {                                      // pass k: axis k / 2, + eps then - eps
-            const double h = (k & 1) ? -a.normal_eps : a.normal_eps;
-            x = px; y = py; z = pz;
-            if ((k >> 1) == 0) x = x + h;
-            else if ((k >> 1) == 1) y = y + h;
-            else z = z + h;
+        if (phase == PH_NORMAL) {
+            const P3 p = grad_point(k, a.normal_eps, px, py, pz);
+            x = p.x; y = p.y; z = p.z;
         }
         const double v = (double)run_tape1<T, FULL>(code, consts, (T)x, (T)y, (T)z);
         if (phase == PH_NORMAL) {
-            const double g = gp - v;
-            if (k == 1) g0 = g;
-            else if (k == 3) g1 = g;
-            else if (k == 5) g2 = g;
-            gp = v;
+            const double d = g.gp - v;                                 // (grad_take spelt out: through the helper this kernel compiles to
+            if (k == 1) g.g0 = d;                                      // other instructions, profiles/probe_spine_refactor.md)
+            else if (k == 3) g.g1 = d;
+            else if (k == 5) g.g2 = d;
+            g.gp = v;
             k++;
             if (k == 6) {
-                const double len = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
-                const bool flat = len == 0.0 || len != len;
-                dx = flat ? 0.0 : -(g0 / len);                         // inward for this library's winding
-                dy = flat ? 0.0 : -(g1 / len);
-                dz = flat ? 0.0 : -(g2 / len);
+                const double len = sqrt(grad_len2(g.g0, g.g1, g.g2));
+                const bool flat = grad_flat(len);
+                dx = flat ? 0.0 : -(g.g0 / len);                       // inward for this library's winding
+                dy = flat ? 0.0 : -(g.g1 / len);
+                dz = flat ? 0.0 : -(g.g2 / len);
                 status = flat ? W_FLAT : W_MARCH;
                 if (!__any(status == W_MARCH)) break;                  // a wave of flat vertices: no ray to march
                 phase = PH_MARCH; k = 0;

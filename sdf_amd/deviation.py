@@ -12,6 +12,8 @@ clustering rounded, and it does not preserve topology (vertices that land on one
 those)."""
 import numpy as np
 
+from .meshfile import central_difference, frozen as _frozen
+
 LEFT, SNAPPED, HELD, FLAT, NAN = 0, 1, 2, 3, 4
 STATUS_NAMES = ('LEFT', 'SNAPPED', 'HELD', 'FLAT', 'NAN')
 _ITER = 5
@@ -135,13 +137,7 @@ def vertex_snap(ev, points, eps, tol, max_move, iters=4):
             m, v = m[~nan & ~ok], v[~nan & ~ok]
             if len(m) == 0:
                 continue
-            g = np.empty((len(m), 3))
-            for k in range(3):
-                Q = q[m]
-                Q[:, k] = q[m, k] + eps
-                plus = f(Q)
-                Q[:, k] = q[m, k] + (-eps)
-                g[:, k] = plus - f(Q)
+            g = central_difference(f, q[m], eps)
             evals[m] += 6
             len2 = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
             flat = (len2 == 0) | np.isnan(len2)
@@ -159,12 +155,6 @@ def vertex_snap(ev, points, eps, tol, max_move, iters=4):
         status[it & (np.abs(residual) <= tol)] = SNAPPED
         status[status == _ITER] = LEFT
     return q, status, residual, evals
-
-
-def _frozen(a):
-    a = np.array(a)
-    a.setflags(write=False)
-    return a
 
 
 class Deviation:

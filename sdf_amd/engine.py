@@ -516,10 +516,8 @@ class Mesh:
         eps = float(eps)
         if not (np.isfinite(eps) and eps > 0):
             raise ValueError('eps must be finite and positive, got %r' % eps)
-        if eng.precision != PRECISION_F64:
-            raise ValueError('vertex_normals takes the gradient in float64 only; this engine is set to float32 precision')
-        dt = eng.tape_for(sdf_or_tape)
-        if dt.tape.externs:
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_normals takes the gradient')
+        if on_host:
             from . import meshfile
             return meshfile.vertex_normals(lambda P: eng.eval_points(dt, P), self.weld()[0], eps)
         nu = self._welded()
@@ -540,10 +538,8 @@ class Mesh:
         from .thickness import check_params, vertex_thickness      # (the package's attribute `thickness` is the function)
         eng = self.engine
         params = check_params(normal_eps, start, min_step, t_far, step_scale, max_steps, refine)
-        if eng.precision != PRECISION_F64:
-            raise ValueError('vertex_thickness marches in float64 only; this engine is set to float32 precision')
-        dt = eng.tape_for(sdf_or_tape)
-        if dt.tape.externs:
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_thickness marches')
+        if on_host:
             return vertex_thickness(lambda P: eng.eval_points(dt, P), self.weld()[0], *params)
         nu = self._welded()
         th, status, steps = np.empty(nu, np.float64), np.empty(nu, np.uint8), np.empty(nu, np.int32)
@@ -563,10 +559,8 @@ class Mesh:
         from .deviation import check_order, triangle_deviation
         eng = self.engine
         order = check_order(order)
-        if eng.precision != PRECISION_F64:
-            raise ValueError('triangle_deviation samples in float64 only; this engine is set to float32 precision')
-        dt = eng.tape_for(sdf_or_tape)
-        if dt.tape.externs:
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'triangle_deviation samples')
+        if on_host:
             return triangle_deviation(lambda P: eng.eval_points(dt, P), np.asarray(self.points()).reshape(-1, 3, 3), order)
         t = self.n_triangles
         dev, at, sumsq = np.empty(t, np.float64), np.empty(t, np.int32), np.empty(t, np.float64)
@@ -589,10 +583,8 @@ class Mesh:
         from .deviation import STATUS_NAMES, check_snap, vertex_snap
         eng = self.engine
         eps, tol, max_move, iters = check_snap(eps, tol, max_move, iters)
-        if eng.precision != PRECISION_F64:
-            raise ValueError('snap steps in float64 only; this engine is set to float32 precision')
-        dt = eng.tape_for(sdf_or_tape)
-        if dt.tape.externs:
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'snap steps')
+        if on_host:
             from . import core
             pts, cells = self.weld()
             q, status, residual, evals = vertex_snap(lambda P: eng.eval_points(dt, P), pts, eps, tol, max_move, iters)
@@ -821,11 +813,9 @@ class Mesh:
         from .supports import check_params, support_rays_host
         eng = self.engine
         d, params = check_params(directions, sin_limit, bed_tol, start, min_step, step_scale, max_steps, refine)
-        if eng.precision != PRECISION_F64:
-            raise ValueError('support_rays marches in float64 only; this engine is set to float32 precision')
-        dt = eng.tape_for(sdf_or_tape)
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'support_rays marches')
         k = len(d)
-        if dt.tape.externs:
+        if on_host:
             soup = self.points().reshape(-1, 3, 3)
             got = [support_rays_host(lambda P: eng.eval_points(dt, P), soup, d[i], *params) for i in range(k)]
             return {'lo': np.array([g['lo'] for g in got]), 'hi': np.array([g['hi'] for g in got]),
@@ -1026,6 +1016,14 @@ class Engine:
             self._tapes[key] = dt
         return dt
 
+    def _probe_tape(self, sdf, verb):
+        """the six field probes, behind the checks of their own parameters: refuse float32 precision (`verb`: what the probe does
+        in float64), then (the device tape, whether it reads user closures -- the probe's definition on the host serves those)"""
+        if self.precision != PRECISION_F64:
+            raise ValueError('%s in float64 only; this engine is set to float32 precision' % verb)
+        dt = self.tape_for(sdf)
+        return dt, bool(dt.tape.externs)
+
     # -- f(P) --
     def eval_points(self, sdf, pts):
         dt = self.tape_for(sdf)
@@ -1169,10 +1167,8 @@ class Engine:
         (height, width) int32 and `status` (height, width) uint8 (1 hit, 0 miss).  frame: 18 doubles o0, ou, ov, c, du, dv
         (sdf_amd/render.py `camera` makes one).  Raises ValueError, before any device work, for what the entry point refuses
         (include/sdf_hip.h), for a model with user closures and for a context in float32 precision."""
-        if self.precision != PRECISION_F64:
-            raise ValueError('render_buffers traces in float64 only; this engine is set to float32 precision')
-        dt = self.tape_for(sdf)
-        if dt.tape.externs:
+        dt, on_host = self._probe_tape(sdf, 'render_buffers traces')
+        if on_host:
             raise ValueError('render_buffers cannot trace a model with user closures: every step of every ray would need a host round trip')
         frame = np.ascontiguousarray(frame, dtype=np.float64).reshape(-1)
         if frame.size != 18:

@@ -7,6 +7,8 @@ import collections
 
 import numpy as np
 
+from .meshfile import frozen as _frozen
+
 Measurement = collections.namedtuple('Measurement', (
     'volume', 'area', 'centroid', 'inertia', 'bounds', 'triangles', 'zero_area_triangles', 'nonfinite_triangles',
     'vertices', 'faces', 'collapsed', 'edges', 'paired', 'boundary', 'misoriented', 'nonmanifold', 'euler', 'closed', 'oriented',
@@ -37,12 +39,6 @@ def derive(m):
     return {'area': area, 'volume': volume, 'centroid': centroid, 'inertia': inertia}
 
 
-def _frozen(a):
-    a = np.array(a, dtype=np.float64)
-    a.setflags(write=False)
-    return a
-
-
 def measure_mesh(mesh, origin=None):
     """the Measurement of a device mesh (`engine.Mesh`): moments, derived values, census (welds if needed)"""
     m = mesh.moments(origin)
@@ -50,9 +46,9 @@ def measure_mesh(mesh, origin=None):
     d = derive(m)
     lo, hi = m['box']
     return Measurement(
-        volume=float(d['volume']), area=float(d['area']), centroid=_frozen(d['centroid']), inertia=_frozen(d['inertia']),
+        volume=float(d['volume']), area=float(d['area']), centroid=_frozen(d['centroid'], np.float64), inertia=_frozen(d['inertia'], np.float64),
         bounds=(tuple(lo.tolist()), tuple(hi.tolist())), triangles=m['triangles'], zero_area_triangles=m['zero_area'],
-        nonfinite_triangles=m['nonfinite'], origin=_frozen(m['origin']), sums=_frozen(m['sums']), **c)
+        nonfinite_triangles=m['nonfinite'], origin=_frozen(m['origin'], np.float64), sums=_frozen(m['sums'], np.float64), **c)
 
 
 def measure(sdf, origin=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, snap=False, **generate_kwargs):

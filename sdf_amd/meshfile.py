@@ -80,6 +80,28 @@ def write_obj(path, points, cells, normals=None):
             fp.write(''.join(['f %d %d %d\n' % (a, b, d) for a, b, d in c.tolist()]))
 
 
+def frozen(a, dtype=None):
+    """a read-only copy of `a` (as `dtype`, if given): what the result objects of the package hand out"""
+    a = np.array(a, dtype=dtype)
+    a.setflags(write=False)
+    return a
+
+
+def central_difference(f, P, eps):
+    """g (N, 3) float64, the host definition of the probes' central difference over f(Q) -> (N,) float64 at the points P (N, 3)
+    float64: for axis k the value at x_k + eps minus the value at x_k + (-eps), plus taken first -- one rounding per operation,
+    what the device kernels reproduce bit for bit (csrc/sdf_probe.h)"""
+    g = np.empty((len(P), 3))
+    for k in range(3):
+        Q = P.copy()
+        Q[:, k] = P[:, k] + eps
+        plus = f(Q)
+        Q[:, k] = P[:, k] + (-eps)
+        minus = f(Q)
+        g[:, k] = plus - minus
+    return g
+
+
 def vertex_normals(ev, points, eps):
     """the normal's definition on the host over an evaluator ev(P) -> (N,) float64: where the device kernel does not reach (a
     model with user closures, a soup gathered on the host).  float64, one rounding per operation: for axis k the value at
@@ -91,14 +113,7 @@ def vertex_normals(ev, points, eps):
         raise ValueError('eps must be finite and positive, got %r' % eps)
     if len(P) == 0:
         return np.zeros((0, 3)), 0
-    g = np.empty_like(P)
-    for k in range(3):
-        Q = P.copy()
-        Q[:, k] = P[:, k] + eps
-        plus = np.asarray(ev(Q), dtype=np.float64).reshape(-1)
-        Q[:, k] = P[:, k] + (-eps)
-        minus = np.asarray(ev(Q), dtype=np.float64).reshape(-1)
-        g[:, k] = plus - minus
+    g = central_difference(lambda Q: np.asarray(ev(Q), dtype=np.float64).reshape(-1), P, eps)
     ln = np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
     flat = (ln == 0) | np.isnan(ln)
     with np.errstate(invalid='ignore', divide='ignore'):

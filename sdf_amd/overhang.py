@@ -15,6 +15,8 @@ import math
 
 import numpy as np
 
+from .meshfile import frozen as _frozen
+
 UP = (0.0, 0.0, 1.0)
 NEITHER, OVERHANG, CONTACT, NONFINITE = 0, 1, 2, 3      # the classes of `Overhangs.classes`
 MAX_DIRECTIONS = 1 << 20
@@ -126,21 +128,15 @@ def check_params(directions, angle, bed_tolerance, classes):
     return d, sin_limit_of(angle), angle, bed_tolerance
 
 
-def _frozen(a, dtype=np.float64):
-    a = np.array(a, dtype=dtype)
-    a.setflags(write=False)
-    return a
-
-
 def _rated(mesh, d, sin_limit, angle, tol, classes, max_scratch_bytes=0):
     r = mesh.overhangs(d, sin_limit, tol, max_scratch_bytes)
     v = derive(r)
     cls = _frozen(mesh.overhang_classes(d[0], sin_limit, tol), np.uint8) if classes else None
     return Overhangs(
-        directions=_frozen(d), lo=_frozen(r['lo']), hi=_frozen(r['hi']), height=_frozen(v['height']),
-        overhang_area=_frozen(v['overhang_area']), support_volume=_frozen(v['support_volume']), contact_area=_frozen(v['contact_area']),
+        directions=_frozen(d, np.float64), lo=_frozen(r['lo'], np.float64), hi=_frozen(r['hi'], np.float64), height=_frozen(v['height'], np.float64),
+        overhang_area=_frozen(v['overhang_area'], np.float64), support_volume=_frozen(v['support_volume'], np.float64), contact_area=_frozen(v['contact_area'], np.float64),
         overhang_triangles=_frozen(r['overhang_triangles'], np.int64), contact_triangles=_frozen(r['contact_triangles'], np.int64),
-        angle=angle, bed_tolerance=tol, sums=_frozen(r['sums']), classes=cls)
+        angle=angle, bed_tolerance=tol, sums=_frozen(r['sums'], np.float64), classes=cls)
 
 
 def overhangs_of_mesh(mesh, directions=UP, angle=45.0, bed_tolerance=None, classes=False, max_scratch_bytes=0):

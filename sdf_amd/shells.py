@@ -9,16 +9,12 @@ import numbers
 
 import numpy as np
 
+from .meshfile import frozen as _frozen
+
 Shells = collections.namedtuple('Shells', ('count', 'triangles', 'vertices', 'bounds', 'vertex_shell', 'triangle_shell', 'rounds'))
 Shells.__doc__ = """what `shells` returns (immutable).  count: K; per shell k, numbered by its lexicographically smallest vertex:
 triangles[k], vertices[k] (int64) and bounds[k] (2, 3) float64; vertex_shell (U,) int32 over the welded vertices, triangle_shell
 (T,) int32 over the triangles in soup order; rounds: the passes the labelling took."""
-
-
-def _frozen(a):
-    a = np.array(a)
-    a.setflags(write=False)
-    return a
 
 
 def shells_of_mesh(mesh):

@@ -13,6 +13,7 @@ many near-vertical faces are BURIED, which is why `buried_area` is reported; a f
 step_scale < 1."""
 import numpy as np
 
+from .meshfile import frozen as _frozen
 from .overhang import UP, normalise, overhangs_of_mesh, rotation_to_z, sin_limit_of, sphere_directions
 
 BED, PART, BURIED, UNRESOLVED, NAN = 0, 1, 2, 3, 4
@@ -191,12 +192,6 @@ def derive(r):
                 'height': np.asarray(r['hi'], dtype=np.float64) - np.asarray(r['lo'], dtype=np.float64)}
 
 
-def _frozen(a, dtype=np.float64):
-    a = np.array(a, dtype=dtype)
-    a.setflags(write=False)
-    return a
-
-
 class Supports:
     """what `supports` returns (the arrays are read-only).  Per traced direction, each (K,): directions (K, 3) -- unit, "up" --,
     support_volume = on_bed_volume + on_part_volume (the columns that stand on the bed, and those that rest on the part itself),
@@ -208,10 +203,10 @@ class Supports:
 
     def __init__(self, directions, raw, angle, bed_tolerance, params, proxy=None, traced=None):
         v = derive(raw)
-        self.directions = _frozen(directions)
+        self.directions = _frozen(directions, np.float64)
         for k in ('support_volume', 'on_bed_volume', 'on_part_volume', 'touch_area', 'projected_area', 'buried_area', 'height'):
-            setattr(self, k, _frozen(v[k]))
-        self.lo, self.hi, self.sums = _frozen(raw['lo']), _frozen(raw['hi']), _frozen(raw['sums'])
+            setattr(self, k, _frozen(v[k], np.float64))
+        self.lo, self.hi, self.sums = _frozen(raw['lo'], np.float64), _frozen(raw['hi'], np.float64), _frozen(raw['sums'], np.float64)
         self.counts = _frozen(raw['counts'], np.int64)
         self._rays = [tuple(_frozen(a, a.dtype) for a in ray) for ray in raw['rays']]
         self.angle, self.bed_tolerance, self.params = angle, bed_tolerance, dict(params)

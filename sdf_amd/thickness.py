@@ -11,6 +11,8 @@ with `snap=True`; a field
 that is only a bound, not a distance, costs steps and not correctness."""
 import numpy as np
 
+from .meshfile import central_difference, frozen as _frozen
+
 OPEN, THICK, THIN, FLAT, NAN = 0, 1, 2, 3, 4
 STATUS_NAMES = ('OPEN', 'THICK', 'THIN', 'FLAT', 'NAN')
 _MARCH = 5
@@ -51,13 +53,7 @@ def vertex_thickness(ev, points, normal_eps, start, min_step, t_far, step_scale=
     def f(Q):
         return np.asarray(ev(np.ascontiguousarray(Q)), dtype=np.float64).reshape(-1)
 
-    g = np.empty_like(P)
-    for k in range(3):
-        Q = P.copy()
-        Q[:, k] = P[:, k] + normal_eps
-        plus = f(Q)
-        Q[:, k] = P[:, k] + (-normal_eps)
-        g[:, k] = plus - f(Q)
+    g = central_difference(f, P, normal_eps)
     with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
         ln = np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
         flat = (ln == 0) | np.isnan(ln)
@@ -92,12 +88,6 @@ def vertex_thickness(ev, points, normal_eps, start, min_step, t_far, step_scale=
         hi[r[~neg]] = mid[~neg]
     th = np.where((status == THICK) | (status == THIN), hi, np.where(status == OPEN, np.inf, np.nan))
     return th, status, steps
-
-
-def _frozen(a):
-    a = np.array(a)
-    a.setflags(write=False)
-    return a
 
 
 class Thickness:

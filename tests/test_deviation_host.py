@@ -175,7 +175,8 @@ def test_abi_and_surface():
     assert engine.ABI_VERSION == 17 and lib.sdf_abi_version() == 17
     assert int(re.search(r'#define SDF_ABI_VERSION (\d+)', hdr).group(1)) == 17
     units = [l.split() for l in open(os.path.join(ROOT, 'sdf_amd', 'csrc', 'build.units')) if l.strip() and not l.lstrip().startswith('#')]
-    assert units[-1] == ['sdf_deviation', 'sdf_deviation.hip', 'interp']
+    # the kernels' unit with the interpreters' flags, the last of the kernel units; behind it only the probes' host entries (plain)
+    assert units[-2:] == [['sdf_deviation', 'sdf_deviation.hip', 'interp'], ['sdf_probe_out', 'sdf_probe_out.hip', 'plain']]
     import sdf_amd
     assert callable(sdf_amd.deviation) and callable(sdf_amd.deviation_of_soup) and sdf_amd.Deviation is Deviation
     assert callable(d3.SDF3.deviation) and callable(mesh_module.Mesh.deviation) and callable(mesh_module.Mesh.snap)
