@@ -8,7 +8,7 @@
 #include "sdf_runtime.h"
 namespace sdfk {
 // what a labelled mesh keeps, one device block: [vertex_shell V x i32 | triangle_shell T x i32 | triangles K x u64 | vertices K x u64 |
-// box K x 6 keys of box_key (sdf_measure.h): lo x, y, z, hi x, y, z], every part 256-byte aligned
+// box K x 6 keys of box_key (sdf_block.h): lo x, y, z, hi x, y, z], every part 256-byte aligned
 struct ShellParts {
     int *vertex_shell, *triangle_shell;
     unsigned long long *triangles, *vertices, *box;

@@ -11,10 +11,10 @@
 // a stale value is an EARLIER value of the word, which is the vertex itself or one of its true ancestors, so a walk over stale
 // words ends at a true ancestor and at worst asks for an exchange that fails.  k_shell_compress then points every vertex at its
 // root.  Whether the labelling is complete is decided across a kernel boundary: k_shell_hook counts the cells whose three roots
-// were not one (one integer atomic per workgroup), the host reads the counter, and only a full pass that counts none ends the loop.
+// were not one (block_count of sdf_block.h), the host reads the counter, and only a full pass that counts none ends the loop.
 //
 // Numbering: the roots are flagged, a library exclusive scan (hipCUB, like the weld's) numbers them, one lane per vertex and one
-// per cell write the shells.  Counts and boxes: integer atomics only, on the ordered keys of k_soup_box, filter first -- a lane
+// per cell write the shells.  Counts and boxes: integer atomics only, on the ordered keys of sdf_block.h, filter first -- a lane
 // accumulates in registers while its run of one shell lasts, a wave whose lanes agree adds up across its lanes, the four waves of a
 // workgroup that agree add up in LDS, and one lane issues the atomics; only mixed waves fall back to per-lane atomics.
 //
@@ -22,12 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstring>
 #include <string>
 #include <utility>
 
+#include "sdf_block.h"
 #include "sdf_components.h"
-#include "sdf_measure.h"
 #include "sdf_prims.h"
 
 namespace sdfk {
@@ -76,14 +75,8 @@ __global__ __launch_bounds__(256) void k_shell_hook(const long long *__restrict_
         hooks = ra != rb || rb != rc;
         if (hooks) shell_unite(parent, shell_unite(parent, ra, rb), rc);
     }
-    __shared__ unsigned wave_n[4];
-    const unsigned n = (unsigned)__popcll(__ballot(hooks));
-    if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-        if (total) atomicAdd(n_hooking, total);
-    }
+    const bool is[1] = {hooks};
+    block_count(is, n_hooking);
 }
 
 // one lane per vertex: to its root (a word another lane has already lowered is a true ancestor too)
@@ -171,15 +164,8 @@ __global__ __launch_bounds__(256) void k_shell_tally(const int *__restrict__ she
     if (have != 0ull) {                                                // (uniform)
         const int s0 = __shfl(s, __ffsll((long long)have) - 1);
         if (__ballot(cnt != 0 && s != s0) == 0ull) {
-            for (int h = 32; h >= 1; h >>= 1) {                        // (a lane that holds nothing holds the identities)
-                cnt += __shfl_down(cnt, h);
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const unsigned long long a = __shfl_down(lo[c], h), b = __shfl_down(hi[c], h);
-                    lo[c] = a < lo[c] ? a : lo[c];
-                    hi[c] = b > hi[c] ? b : hi[c];
-                }
-            }
+            cnt = wave_sum(cnt);                                       // (a lane that holds nothing holds the identities)
+            if (BOX) wave_box_min_max(lo, hi);
             wave_s = s0;
         } else if (cnt) {
             tally_flush<BOX>(s, cnt, lo, hi, count, box);              // a mixed wave: per-lane atomics
@@ -250,10 +236,7 @@ ShellParts shell_parts(void *block, long long nv, long long nt, long long k) {
 }
 
 void shell_bounds(const unsigned long long *h_keys, long long n_shells, double *h_bounds) {
-    for (long long i = 0; i < 6 * n_shells; i++) {
-        const unsigned long long u = box_bits(h_keys[i]);
-        memcpy(h_bounds + i, &u, 8);
-    }
+    for (long long i = 0; i < 6 * n_shells; i++) h_bounds[i] = box_value(h_keys[i]);
 }
 
 int components_label(hipStream_t st, const long long *d_cells, const double *d_points, long long n_tris, long long n_vertices,

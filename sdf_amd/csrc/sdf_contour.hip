@@ -6,7 +6,7 @@
 //
 // Samples V[nw][nx][ny], cells g = w * ncell + ix * (ny - 1) + iy, one lane per cell with the lanes along iy.
 //   k_contour_count    the cell's code (its case, bit 4: the centre value is inside) and its number of segments, 0 .. 2; the cells with
-//                      a non-finite corner are counted (integer atomics, one per workgroup).  The library scan gives the offsets.
+//                      a non-finite corner are counted (block_count of sdf_block.h).  The library scan gives the offsets.
 //   k_contour_emit     per segment s: its start vertex; its successor -- the slot of the cell across the edge where s ends whose `from`
 //                      is that edge, from the neighbour's code and offset -- is not stored: s writes s + 1 into pred[successor] (a
 //                      zeroed array; a segment has at most one predecessor, so a plain store).  A segment without a successor (the
@@ -30,6 +30,7 @@
 #include <cmath>
 #include <string>
 
+#include "sdf_block.h"
 #include "sdf_contour.h"
 #include "sdf_internal.h"
 #include "sdf_prims.h"
@@ -75,18 +76,6 @@ __device__ __forceinline__ void edge_vertex(const double *__restrict__ L, const 
     }
 }
 
-// adds the workgroup's sum of v to *total: every lane of the workgroup calls it
-__device__ __forceinline__ void block_add(unsigned v, unsigned long long *total) {
-    __shared__ unsigned w_v[4];
-    for (int h = 32; h >= 1; h >>= 1) v += __shfl_down(v, h);
-    if ((threadIdx.x & 63u) == 0u) w_v[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long sum = (unsigned long long)w_v[0] + w_v[1] + w_v[2] + w_v[3];
-        if (sum) atomicAdd(total, sum);
-    }
-}
-
 // the points of samples [s0, s0 + m) of the grid, dim doubles each: (X[ix], Y[iy]) and, dim 3, W[w]
 __global__ __launch_bounds__(256) void k_contour_points(const double *__restrict__ X, const double *__restrict__ Y, const double *__restrict__ W,
                                                         int nx, int ny, int dim, long long s0, int m, double *__restrict__ pts) {
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(256) void k_contour_points(const double *__restrict
 __global__ __launch_bounds__(256) void k_contour_count(const double *__restrict__ V, const CGrid gr, int n_cells, int *__restrict__ cnt,
                                                        unsigned char *__restrict__ code, ContourHead *head) {
     const int g = (int)(blockIdx.x * 256u + threadIdx.x);
-    unsigned bad = 0u;
+    bool bad[1] = {false};
     if (g < n_cells) {
         const int cy = gr.ny - 1, ncell = (gr.nx - 1) * cy;
         const int w = g / ncell, c = g - w * ncell, ix = c / cy, iy = c - ix * cy;
@@ -113,11 +102,11 @@ __global__ __launch_bounds__(256) void k_contour_count(const double *__restrict_
         const double centre = ((c0 + c1) + (c3 + c2)) * 0.25;
         unsigned k = (c0 < gr.level ? 1u : 0u) | (c1 < gr.level ? 2u : 0u) | (c2 < gr.level ? 4u : 0u) | (c3 < gr.level ? 8u : 0u);
         k = finite ? (k | (centre < gr.level ? 16u : 0u)) : 0u;
-        bad = finite ? 0u : 1u;
+        bad[0] = !finite;
         code[g] = (unsigned char)k;
         cnt[g] = CONTOUR_CASES[k & 15u][0];
     }
-    block_add(bad, &head->nonfinite);
+    block_count(bad, &head->nonfinite);
 }
 
 // pred: n_seg ints, zeroed; start: n_seg x 2 doubles; tail: n_seg

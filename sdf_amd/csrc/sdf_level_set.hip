@@ -16,7 +16,7 @@
 //   k_ls_sign     one wave per triangle: every column of its xy bounding box it covers flips bit k0 of that column's mask
 //                 (atomicXor: the order of the flips does not matter)
 //   k_ls_parity   one thread per column: prefix XOR along k -> the inside bit of every voxel
-//   k_ls_compose  one thread per voxel: v, plus the index box of the active voxels (block reduction, then atomics)
+//   k_ls_compose  one thread per voxel: v, plus the index box of the active voxels (the box reduction of sdf_block.h)
 //   k_ls_crop     the active box, packed for the copy to the host
 // Built with -ffp-contract=off (csrc/build.sh): every multiply and add rounds separately, as NumPy's do.
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <string>
 
+#include "sdf_block.h"
 #include "sdf_internal.h"
 
 namespace sdfk {
@@ -235,22 +236,8 @@ __global__ __launch_bounds__(256) void k_ls_compose(const unsigned long long *__
             for (int a = 0; a < 3; a++) { mn[a] = min(mn[a], c[a]); mx[a] = max(mx[a], c[a]); }
         }
     }
-    for (int a = 0; a < 3; a++)
-        for (int o = 32; o > 0; o >>= 1) { mn[a] = min(mn[a], __shfl_xor(mn[a], o)); mx[a] = max(mx[a], __shfl_xor(mx[a], o)); }
-    __shared__ int part[4][6];
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int a = 0; a < 3; a++) { part[wv][a] = mn[a]; part[wv][3 + a] = mx[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x;
-        int r = part[0][a];
-        for (int w = 1; w < 4; w++) r = a < 3 ? min(r, part[w][a]) : max(r, part[w][a]);
-        if (a < 3 ? r != 0x7fffffff : r >= 0) {
-            if (a < 3) atomicMin(box + a, r);
-            else atomicMax(box + a, r);
-        }
-    }
+    wave_box_min_max(mn, mx);                                          // (sdf_block.h, on int keys; the host starts the box at these identities)
+    block_box_merge(mn, mx, box);
 }
 
 // the active box [c0, c0 + dims) of the work grid, packed [i][j][k]

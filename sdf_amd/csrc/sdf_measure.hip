@@ -16,13 +16,15 @@
 // sort (hipCUB, like the weld's); k_edge_classes gives every sorted key a lane: the key that starts a run of one undirected edge
 // looks two keys ahead -- run length 1, 2, "3 or more" and two direction bits decide the class -- so no lane walks a long run.
 // The counters are integer atomics, one per workgroup and class.
+//
+// The tree, the box reduced across a workgroup, its keys and the counters' sums are sdf_block.h's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
-#include <cstring>
 #include <string>
 
+#include "sdf_block.h"
 #include "sdf_measure.h"
 #include "sdf_runtime.h"
 
@@ -48,13 +50,6 @@ __device__ __forceinline__ void stage_tile(const double *__restrict__ soup, long
     } else {
         for (int j = tid; j < nd; j += MOMENT_TILE) tile[j] = src[j];
     }
-}
-
-__device__ __forceinline__ bool finite9(const double *v) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) ok = ok && __builtin_isfinite(v[k]);
-    return ok;
 }
 
 // the bounding box of the triangles whose vertices are all finite, on box_key's keys: box[0..2] min, box[3..5] max
@@ -84,57 +79,8 @@ __global__ __launch_bounds__(256) void k_soup_box(const double *__restrict__ sou
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        for (int h = 32; h >= 1; h >>= 1) {
-            const unsigned long long a = __shfl_down(lo[k], h), b = __shfl_down(hi[k], h);
-            lo[k] = a < lo[k] ? a : lo[k];
-            hi[k] = b > hi[k] ? b : hi[k];
-        }
-    }
-    // the four waves meet in LDS; six lanes take one bound each and touch the box only where they improve it (a stale read of the
-    // box can only ask for an atomic that was not needed): a handful of integer atomics per launch, not six per wave
-    __shared__ unsigned long long wave_box[4][6];
-    __syncthreads();
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { wave_box[tid >> 6][k] = lo[k]; wave_box[tid >> 6][3 + k] = hi[k]; }
-    }
-    __syncthreads();
-    if (tid < 6) {
-        unsigned long long v = wave_box[0][tid];
-        for (int w = 1; w < 4; w++) {
-            const unsigned long long x = wave_box[w][tid];
-            v = tid < 3 ? (x < v ? x : v) : (x > v ? x : v);
-        }
-        const unsigned long long now = __atomic_load_n(box + tid, __ATOMIC_RELAXED);
-        if (tid < 3) { if (v < now) atomicMin(box + tid, v); }
-        else if (v > now) atomicMax(box + tid, v);
-    }
-}
-
-// the halving tree over the 256 lanes' accumulators: x[:h] + x[h:], h = 128 ... 1; lane 0 ends with the sums.  `tile`: >= 128 x 11
-// doubles of LDS that no lane still reads.
-__device__ __forceinline__ void tree256(double *acc, double *tile) {
-    const int tid = (int)threadIdx.x;
-    for (int h = 128; h >= 64; h >>= 1) {
-        if (tid >= h && tid < 2 * h) {
-#pragma unroll
-            for (int k = 0; k < MOMENT_SUMS; k++) tile[k * 128 + (tid - h)] = acc[k];
-        }
-        __syncthreads();
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < MOMENT_SUMS; k++) acc[k] = acc[k] + tile[k * 128 + tid];
-        }
-        __syncthreads();
-    }
-    if (tid < 64) {                                                    // (wave 0, whole)
-        for (int h = 32; h >= 1; h >>= 1) {
-#pragma unroll
-            for (int k = 0; k < MOMENT_SUMS; k++) acc[k] = acc[k] + __shfl_down(acc[k], h);
-        }
-    }
+    wave_box_min_max(lo, hi);
+    block_box_merge(lo, hi, box);
 }
 
 // one chunk of MOMENT_CHUNK triangles per workgroup: partials[chunk][11]; counts[0] += zero-area, counts[1] += non-finite triangles
@@ -149,7 +95,7 @@ __global__ __launch_bounds__(256) void k_soup_moments(const double *__restrict__
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const unsigned long long kl = box[k], kh = box[3 + k];
-            const double lo = __longlong_as_double((long long)box_bits(kl)), hi = __longlong_as_double((long long)box_bits(kh));
+            const double lo = box_value(kl), hi = box_value(kh);
             o[k] = kl > kh ? 0.0 : lo + (hi - lo) / 2.0;
         }
         o0 = o[0]; o1 = o[1]; o2 = o[2];
@@ -203,7 +149,7 @@ __global__ __launch_bounds__(256) void k_soup_moments(const double *__restrict__
         n_bad += (unsigned)__popcll(__ballot(bad));
     }
     __syncthreads();                                                   // (the last tile has been read: the tree takes the LDS over)
-    tree256(acc, tile);
+    tree256<MOMENT_SUMS>(acc, tile);
     if (tid == 0) {
 #pragma unroll
         for (int k = 0; k < MOMENT_SUMS; k++) partials[(long long)blockIdx.x * MOMENT_SUMS + k] = acc[k];
@@ -221,7 +167,7 @@ __global__ __launch_bounds__(256) void k_moment_partials(const double *__restric
     double acc[MOMENT_SUMS];
 #pragma unroll
     for (int k = 0; k < MOMENT_SUMS; k++) acc[k] = i < n ? in[i * MOMENT_SUMS + k] : 0.0;
-    tree256(acc, tile);
+    tree256<MOMENT_SUMS>(acc, tile);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < MOMENT_SUMS; k++) out[(long long)blockIdx.x * MOMENT_SUMS + k] = acc[k];
@@ -245,13 +191,11 @@ __global__ __launch_bounds__(256) void k_edge_keys(const long long *__restrict__
             keys[3 * i + e] = collapsed ? EDGE_COLLAPSED : (lo << 32) + hi * 2ull + (u > v ? 1ull : 0ull);
         }
     }
-    const unsigned long long any = __ballot(collapsed);
-    if (any != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(n_collapsed, (unsigned long long)__popcll(any));
+    wave_add(wave_count(collapsed), n_collapsed);
 }
 
 // one lane per sorted key, a workgroup strides over the keys; classes[0..3] += paired, boundary, misoriented, non-manifold edges.
-// Every lane counts in registers; the lanes of a wave, then the four waves, are added up and ONE integer atomic per workgroup and
-// class that has any goes out (one per wave and key tile was measured first: 138,000 atomics on one cache line, 1.4 - 2.7 ms).
+// Every lane counts in registers; block_add (sdf_block.h) sends one integer atomic per workgroup and class that has any.
 __global__ __launch_bounds__(256) void k_edge_classes(const unsigned long long *__restrict__ keys, long long n, unsigned long long *__restrict__ classes) {
     unsigned cnt[4] = {0u, 0u, 0u, 0u};
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -265,24 +209,7 @@ __global__ __launch_bounds__(256) void k_edge_classes(const unsigned long long *
             for (int c = 0; c < 4; c++) cnt[c] += cls == c ? 1u : 0u;
         }
     }
-    __shared__ unsigned wave_cnt[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        for (int h = 32; h >= 1; h >>= 1) cnt[c] += __shfl_down(cnt[c], h);
-        if ((threadIdx.x & 63u) == 0u) wave_cnt[threadIdx.x >> 6][c] = cnt[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const unsigned long long total = (unsigned long long)wave_cnt[0][threadIdx.x] + wave_cnt[1][threadIdx.x] + wave_cnt[2][threadIdx.x] + wave_cnt[3][threadIdx.x];
-        if (total) atomicAdd(classes + threadIdx.x, total);
-    }
-}
-
-static double key_value(unsigned long long k) {
-    const unsigned long long u = box_bits(k);
-    double v;
-    memcpy(&v, &u, 8);
-    return v;
+    block_add(cnt, classes);
 }
 
 int measure_moments(hipStream_t st, const double *d_soup, long long n_tris, const double *origin, sdf_moments *out, double *kernel_ms) {
@@ -325,8 +252,8 @@ int measure_moments(hipStream_t st, const double *d_soup, long long n_tris, cons
     for (int k = 0; k < MOMENT_SUMS; k++) out->sums[k] = h_sums[k];
     for (int k = 0; k < 3; k++) {
         out->origin[k] = h_head.origin[k];
-        out->box_lo[k] = key_value(h_head.box[k]);
-        out->box_hi[k] = key_value(h_head.box[3 + k]);
+        out->box_lo[k] = box_value(h_head.box[k]);
+        out->box_hi[k] = box_value(h_head.box[3 + k]);
     }
     out->n_triangles = (int64_t)n_tris;
     out->n_zero_area = (int64_t)h_head.counts[0];

@@ -12,8 +12,8 @@
 // k_mend_runs: one lane per sorted position.  The lane whose face differs from its predecessor's is the head of a run; it walks the
 // run, counts n0 and n1, and either sets the keep flag of the one survivor -- position head when side 0 has the majority, head + n0
 // when side 1 has it: the first in soup order, because the sorts are stable -- or, n0 == n1, keeps nothing.  duplicates, cancelled
-// and faces are summed across the workgroup and added with integer atomics, one per counter and workgroup: integer sums do not
-// depend on their order.  A run is thousands of entries long only for a face repeated that often: legal, and slow for its lane only.
+// and faces are summed across the workgroup and added with integer atomics, one per counter and workgroup (block_add of
+// sdf_block.h).  A run is thousands of entries long only for a face repeated that often: legal, and slow for its lane only.
 //
 // Emission is a selection's: keep flags in soup order, number_flags, and the copy kernel of sdf_components.hip, nine doubles per
 // survivor from the SOURCE soup, bit for bit.
@@ -23,6 +23,7 @@
 
 #include <string>
 
+#include "sdf_block.h"
 #include "sdf_components.h"
 #include "sdf_mend.h"
 #include "sdf_prims.h"
@@ -30,21 +31,10 @@
 namespace sdfk {
 
 // what the passes leave for the host
+enum { DUPLICATES, CANCELLED, FACES, MEND_RUNS };                      // the counters of k_mend_runs, one block_add
 struct MendHead {
-    unsigned long long collapsed, duplicates, cancelled, faces;
+    unsigned long long collapsed, runs[MEND_RUNS];
 };
-
-// adds the workgroup's sum of v to *total: every lane of the workgroup calls it.  (The sums of one workgroup stay below the
-// triangle count, which fits 31 bits.)
-__device__ __forceinline__ void block_add(unsigned v, unsigned (*w_v)[4], int slot, unsigned long long *total) {
-    for (int h = 32; h >= 1; h >>= 1) v += __shfl_down(v, h);
-    if ((threadIdx.x & 63u) == 0u) w_v[slot][threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long sum = (unsigned long long)w_v[slot][0] + w_v[slot][1] + w_v[slot][2] + w_v[slot][3];
-        if (sum) atomicAdd(total, sum);
-    }
-}
 
 // one lane per triangle (n_tris, 3 n_tris and n_vertices are below 2^31: 32-bit indexing throughout)
 __global__ __launch_bounds__(256) void k_mend_keys(const long long *__restrict__ cells, unsigned n_tris, unsigned n_vertices, int vb,
@@ -63,8 +53,8 @@ __global__ __launch_bounds__(256) void k_mend_keys(const long long *__restrict__
         lo[t] = dead ? 0u : (top << 1) | side;
         idx[t] = t;
     }
-    __shared__ unsigned w_v[1][4];
-    block_add(dead ? 1u : 0u, w_v, 0, &head->collapsed);
+    const bool is[1] = {dead};
+    block_count(is, &head->collapsed);
 }
 
 // one lane per position of the order by lo
@@ -80,7 +70,7 @@ __global__ __launch_bounds__(256) void k_mend_runs(const unsigned long long *__r
                                                    const unsigned *__restrict__ lo, unsigned n_tris, unsigned long long dead_key,
                                                    int *__restrict__ keep, MendHead *head) {
     const unsigned p = blockIdx.x * 256u + threadIdx.x;
-    unsigned duplicates = 0u, cancelled = 0u, faces = 0u;
+    unsigned duplicates = 0u, cancelled = 0u, faces = 0u;              // (the sums of one workgroup stay below the triangle count: 31 bits)
     if (p < n_tris) {
         const unsigned long long h = hi[p];
         if (h < dead_key) {
@@ -98,10 +88,8 @@ __global__ __launch_bounds__(256) void k_mend_runs(const unsigned long long *__r
             }
         }
     }
-    __shared__ unsigned w_v[3][4];
-    block_add(duplicates, w_v, 0, &head->duplicates);
-    block_add(cancelled, w_v, 1, &head->cancelled);
-    block_add(faces, w_v, 2, &head->faces);
+    const unsigned runs[MEND_RUNS] = {duplicates, cancelled, faces};   // (in the enum's order)
+    block_add(runs, head->runs);
 }
 
 int mend_device(hipStream_t st, const double *d_soup, const long long *d_cells, long long n_vertices, long long n_tris, DevBuf *out,
@@ -155,7 +143,7 @@ int mend_device(hipStream_t st, const double *d_soup, const long long *d_cells, 
     HIPCHK_MSG(who, hipMemcpyAsync(&h_head, head, sizeof(MendHead), hipMemcpyDeviceToHost, st));       // (lands behind number_flags' wait)
     long long kept = 0;
     if (number_flags(who, "keep flags", st, keep, pos, n_tris, tmp, tmp_bytes, &kept)) return 1;
-    if (kept + (long long)(h_head.collapsed + h_head.duplicates + h_head.cancelled) != n_tris)
+    if (kept + (long long)(h_head.collapsed + h_head.runs[DUPLICATES] + h_head.runs[CANCELLED]) != n_tris)
         return fail(std::string(who) + "the counts of the runs are inconsistent");
     if (kept > 0) {
         if (out->ensure((size_t)kept * 72)) return 1;
@@ -169,9 +157,9 @@ int mend_device(hipStream_t st, const double *d_soup, const long long *d_cells, 
     stats->triangles_in = (int64_t)n_tris;
     stats->triangles_out = (int64_t)kept;
     stats->collapsed = (int64_t)h_head.collapsed;
-    stats->duplicates = (int64_t)h_head.duplicates;
-    stats->cancelled = (int64_t)h_head.cancelled;
-    stats->faces = (int64_t)h_head.faces;
+    stats->duplicates = (int64_t)h_head.runs[DUPLICATES];
+    stats->cancelled = (int64_t)h_head.runs[CANCELLED];
+    stats->faces = (int64_t)h_head.runs[FACES];
     stats->kernel_ms = kernel_ms[0] + kernel_ms[1] + kernel_ms[2];
     return 0;
 }

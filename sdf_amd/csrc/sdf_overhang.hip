@@ -14,11 +14,12 @@
 //
 // Two passes.  k_overhang_extents: lo and hi of h(p) = (px dx + py dy) + pz dz per direction over the finite triangles, the same
 // staging with the coordinates and a flag; the workgroups stride over the tiles and meet in 64-bit integer atomic min / max on
-// box_key's keys (sdf_measure.h) -- order-free and exact.  k_overhang_terms: the three terms and the two counts of a chunk, written
+// box_key's keys (sdf_block.h) -- order-free and exact.  k_overhang_terms: the three terms and the two counts of a chunk, written
 // as partials[direction][chunk][3] and one packed count word.  k_overhang_partials -- the shape of k_moment_partials, one partial
-// per lane, the halving tree x[:h] + x[h:], h = 128 ... 1 -- takes 256 partials of one direction to one per launch until one is left
-// (a single chunk goes through it once: x + 0.0 changes no bit of x >= +0.0); its first launch also adds up the packed counts, one
-// integer atomic per workgroup and counter.  The directions go in slabs so that the partials stay under a cap; a slab changes which
+// per lane, the halving tree x[:h] + x[h:], h = 128 ... 1, spelt out in the kernel (a second copy of sdf_block.h's tree256, to be kept
+// in step with it by hand: the kernel holds its parent's instructions that way, see the note there) -- takes 256 partials of one direction to one per launch until one is left
+// (a single chunk goes through it once: x + 0.0 changes no bit of x >= +0.0); its first launch also adds up the packed counts,
+// one integer atomic per workgroup and counter.  The directions go in slabs so that the partials stay under a cap; a slab changes which
 // launch serves a direction and nothing a direction computes.
 //
 // k_overhang_classes: one direction, one triangle per lane, the same predicates, one byte per triangle.
@@ -28,12 +29,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstring>
 #include <deque>
 #include <string>
 #include <vector>
 
-#include "sdf_measure.h"
+#include "sdf_block.h"
 #include "sdf_overhang.h"
 #include "sdf_prims.h"
 #include "sdf_runtime.h"
@@ -51,8 +51,6 @@ constexpr int EXTENT_STAGED = 10;                  // a, b, c, finite (1.0 / 0.0
 // triangles, most of a call with one direction (profiles/overhang01_build_directions.md); the atomics are two per lane and only
 // where a bound improves
 constexpr int EXTENT_MAX_BLOCKS = 1024;
-
-__device__ __forceinline__ double key_double(unsigned long long k) { return __longlong_as_double((long long)box_bits(k)); }
 
 // one lane per direction of the slab: the empty extents, no triangles counted
 __global__ __launch_bounds__(256) void k_overhang_init(long long n_dirs, unsigned long long *__restrict__ ext, unsigned long long *__restrict__ counts) {
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(256) void k_overhang_extents(const double *__restri
         if (tid < cnt) {
             const double *src = soup + 9 * (t0 + tid);
             double *dst = tile + EXTENT_STAGED * tid;
-            bool ok = true;
+            bool ok = true;                                            // (not finite9: through it the kernel's float64 instructions moved)
 #pragma unroll
             for (int c = 0; c < 9; c++) { const double v = src[c]; ok = ok && __builtin_isfinite(v); dst[c] = v; }
             dst[9] = ok ? 1.0 : 0.0;
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(256) void k_overhang_extents(const double *__restri
 
 // the nine coordinates of a triangle -> n, dbl, finite; as tests/overhang_ref.py::triangle_parts writes them
 __device__ __forceinline__ bool triangle_parts(const double *v, double *n, double *dbl) {
-    bool ok = true;
+    bool ok = true;                                                    // (not finite9 behind the normal: that moved k_overhang_terms' float64 instructions)
 #pragma unroll
     for (int c = 0; c < 9; c++) ok = ok && __builtin_isfinite(v[c]);
     const double ux = v[3] - v[0], uy = v[4] - v[1], uz = v[5] - v[2];
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(256) void k_overhang_terms(const double *__restrict
     const long long k = (long long)(blockIdx.x % n_dgroups) * OVERHANG_TILE + tid;
     const bool active = k < n_dirs;
     const double dx = active ? dirs[3 * k] : 0.0, dy = active ? dirs[3 * k + 1] : 0.0, dz = active ? dirs[3 * k + 2] : 0.0;
-    const double lo = active ? key_double(ext[2 * k]) : 0.0;
+    const double lo = active ? box_value(ext[2 * k]) : 0.0;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     unsigned n_over = 0u, n_contact = 0u;
     const long long c0 = chunk * OVERHANG_CHUNK;
@@ -202,6 +200,8 @@ __global__ __launch_bounds__(256) void k_overhang_partials(const double *__restr
     double acc[SUMS];
 #pragma unroll
     for (int c = 0; c < SUMS; c++) acc[c] = i < n ? in[(dir * n + i) * SUMS + c] : 0.0;
+    // (tree256 of sdf_block.h, spelt out: through the helper the kernel differs from its parent by one scalar instruction, and the
+    // kernel is held to its parent's form, see below)
     for (int h = 128; h >= 64; h >>= 1) {                              // x[:h] + x[h:]: through LDS across the waves
         if (tid >= h && tid < 2 * h) {
 #pragma unroll
@@ -226,6 +226,7 @@ __global__ __launch_bounds__(256) void k_overhang_partials(const double *__restr
     }
     if (packed) {                                                      // (uniform; a group's counts stay below 2^18)
         const unsigned w = i < n ? packed[dir * n + i] : 0u;
+        // (not block_add: with it a figure of the rating and one of the support rays lay above the parent's three runs)
         unsigned a = w & 0xffffu, b = w >> 16;
         for (int h = 32; h >= 1; h >>= 1) { a += __shfl_down(a, h); b += __shfl_down(b, h); }
         if ((tid & 63) == 0) { wave_cnt[0][tid >> 6] = a; wave_cnt[1][tid >> 6] = b; }
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256) void k_overhang_classes(const double *__restri
                                                           unsigned char *__restrict__ classes) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tris) return;
-    const double dx = dirs[0], dy = dirs[1], dz = dirs[2], lo = key_double(ext[0]);
+    const double dx = dirs[0], dy = dirs[1], dz = dirs[2], lo = box_value(ext[0]);
     double v[9], n[3], dbl;
 #pragma unroll
     for (int c = 0; c < 9; c++) v[c] = soup[9 * t + c];
@@ -257,13 +258,6 @@ __global__ __launch_bounds__(256) void k_overhang_classes(const double *__restri
     const bool on_bed = top <= bed_tol;
     const bool over = !on_bed && dn < -(sin_limit * dbl), contact = on_bed && dn < 0.0;
     classes[t] = !ok ? 3 : over ? 1 : contact ? 2 : 0;
-}
-
-static double key_value(unsigned long long k) {
-    const unsigned long long u = box_bits(k);
-    double v;
-    memcpy(&v, &u, 8);
-    return v;
 }
 
 static unsigned extent_blocks(long long n_tris) {
@@ -338,8 +332,8 @@ int overhang_rate(hipStream_t st, const double *d_soup, long long n_tris, const 
     *kernel_ms = total_ms;
     *n_slabs = slabs;
     for (long long k = 0; k < n_dirs; k++) {
-        h_values[5 * k] = key_value(h_ext[2 * k]);
-        h_values[5 * k + 1] = key_value(h_ext[2 * k + 1]);
+        h_values[5 * k] = box_value(h_ext[2 * k]);
+        h_values[5 * k + 1] = box_value(h_ext[2 * k + 1]);
         for (int c = 0; c < OVERHANG_SUMS; c++) h_values[5 * k + 2 + c] = h_sums[OVERHANG_SUMS * k + c];
         h_counts[2 * k] = (int64_t)h_cnt[2 * k];
         h_counts[2 * k + 1] = (int64_t)h_cnt[2 * k + 1];
@@ -415,6 +409,7 @@ __global__ __launch_bounds__(256) void k_support_chunks(const double *__restrict
 
 // one ray per lane: the rays of each status, one integer atomic per workgroup and counter
 __global__ __launch_bounds__(256) void k_support_counts(const unsigned char *__restrict__ status, long long m, unsigned long long *__restrict__ counts) {
+    // (not block_count: with it a figure of the support rays lay above the parent's three runs)
     __shared__ unsigned wave_cnt[SUPPORT_STATUSES][4];
     const int tid = (int)threadIdx.x;
     const long long i = (long long)blockIdx.x * 256 + tid;
@@ -501,7 +496,7 @@ int support_rays_run(hipStream_t st, const uint32_t *d_code, const double *d_con
         timers.emplace_back(); EventTimer &t_sums = timers.back();
         SupportArgs a;
         a.dx = h_dirs[3 * k]; a.dy = h_dirs[3 * k + 1]; a.dz = h_dirs[3 * k + 2];
-        a.lo = key_value(h_ext[2 * (size_t)k]);
+        a.lo = box_value(h_ext[2 * (size_t)k]);
         a.start = p.start; a.min_step = p.min_step; a.step_scale = p.step_scale; a.max_steps = p.max_steps; a.refine = p.refine;
         HIPCHK_MSG(who, t_rays.start(st));
         HIPCHK_MSG(who, (hipError_t)launch_support_rays(st, d_code, d_consts, full, d_soup, triangle, m, a, height, status, steps, origin, terms));
@@ -536,8 +531,8 @@ int support_rays_run(hipStream_t st, const uint32_t *d_code, const double *d_con
         }
     }
     for (long long k = 0; k < n_dirs; k++) {
-        h_values[7 * k] = key_value(h_ext[2 * k]);
-        h_values[7 * k + 1] = key_value(h_ext[2 * k + 1]);
+        h_values[7 * k] = box_value(h_ext[2 * k]);
+        h_values[7 * k + 1] = box_value(h_ext[2 * k + 1]);
         for (int c = 0; c < SUPPORT_SUMS; c++) h_values[7 * k + 2 + c] = h_sums[SUPPORT_SUMS * k + c];
         for (int c = 0; c < SUPPORT_STATUSES; c++) h_counts[6 * k + c] = (int64_t)h_cnt[SUPPORT_STATUSES * k + c];
         h_counts[6 * k + 5] = (int64_t)(*out)[(size_t)k].m;

@@ -2,7 +2,8 @@
 // slot behind sdf_last_error, waiting without going to sleep, the allocation hook of the tests, the pool of device blocks, and the
 // small tools of a feature call -- a scratch block (Scratch), the owner of a block the call leaves behind (DevBlock), the checked
 // launch of a 256-lane kernel (launch_rows, launch_grid), the memory guard, an event-pair timer (EventTimer).  The fifth tool of a
-// reader unit, number_flags, has device code behind it and lives in sdf_prims.h.
+// reader unit, number_flags, has device code behind it and lives in sdf_prims.h; what the readers' KERNELS share -- box keys, a
+// workgroup's sums and boxes, the float64 tree -- is sdf_block.h, for units of flag class `plain` only.
 #pragma once
 #include <hip/hip_runtime.h>
 

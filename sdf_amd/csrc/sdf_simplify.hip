@@ -4,7 +4,7 @@
 // by one, in its order: this unit is built with -ffp-contract=off, like sdf_measure.hip, and nothing below is fused.
 //
 // The passes.  k_cluster_box: one lane per welded vertex, the floor of its grid coordinates as ordered integer keys (box_key of
-// sdf_measure.h), reduced across the workgroup, six integer atomics per workgroup; it also counts the vertices that are not finite.
+// sdf_block.h), reduced across the workgroup, at most six integer atomics per workgroup; it also counts the vertices that are not finite.
 // The host reads the box and refuses a mesh the keys cannot hold.  k_cluster_keys: one lane per vertex, the 63-bit key.  A stable
 // library sort (hipCUB, like the weld's) of (key, welded index), adjacent-difference flags and a library exclusive scan number the
 // clusters by ascending key: k_cluster_number writes the cluster of every vertex, the key of every cluster and where its run of the
@@ -37,10 +37,9 @@
 #include <stdint.h>
 
 #include <cmath>
-#include <cstring>
 #include <string>
 
-#include "sdf_measure.h"
+#include "sdf_block.h"
 #include "sdf_prims.h"
 #include "sdf_simplify.h"
 
@@ -81,30 +80,14 @@ __global__ __launch_bounds__(256) void k_cluster_box(const double *__restrict__ 
             for (int c = 0; c < 3; c++) lo[c] = hi[c] = box_key(grid_floor(p[c], g.origin[c], g.cell[c]));
         }
     }
-    for (int h = 32; h >= 1; h >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const unsigned long long a = __shfl_down(lo[c], h), b = __shfl_down(hi[c], h);
-            lo[c] = a < lo[c] ? a : lo[c];
-            hi[c] = b > hi[c] ? b : hi[c];
-        }
-    }
-    __shared__ unsigned long long w_v[4][6];
+    wave_box_min_max(lo, hi);
+    // n_bad keeps its own lines: block_count next to block_box_merge would be a second barrier.  The waves' counts are published by
+    // the one barrier inside block_box_merge
     __shared__ unsigned w_bad[4];
-    const unsigned n_bad = (unsigned)__popcll(__ballot(bad));
-    if ((threadIdx.x & 63u) == 0u) {
-        const int w = (int)(threadIdx.x >> 6);
-#pragma unroll
-        for (int c = 0; c < 3; c++) { w_v[w][c] = lo[c]; w_v[w][3 + c] = hi[c]; }
-        w_bad[w] = n_bad;
-    }
-    __syncthreads();
+    const unsigned n_bad = wave_count(bad);
+    if ((threadIdx.x & 63u) == 0u) w_bad[threadIdx.x >> 6] = n_bad;
+    block_box_merge(lo, hi, head->box);                                // (a workgroup of bad vertices holds the identities)
     if (threadIdx.x == 0) {
-        for (int c = 0; c < 3; c++) {
-            unsigned long long l = w_v[0][c], h = w_v[0][3 + c];
-            for (int w = 1; w < 4; w++) { l = w_v[w][c] < l ? w_v[w][c] : l; h = w_v[w][3 + c] > h ? w_v[w][3 + c] : h; }
-            if (l <= h) { atomicMin(head->box + c, l); atomicMax(head->box + 3 + c, h); }      // (a workgroup of bad vertices holds the identities)
-        }
         const unsigned total = w_bad[0] + w_bad[1] + w_bad[2] + w_bad[3];
         if (total) atomicAdd(&head->n_bad, total);
     }
@@ -267,14 +250,8 @@ __global__ __launch_bounds__(256) void k_cluster_vertex(const double *__restrict
         }
     }
     if constexpr (!ADAPTIVE) {
-        __shared__ unsigned long long w_n[4];
-        const unsigned long long n = ((unsigned long long)__popcll(__ballot(is_flat)) << 32) | (unsigned long long)__popcll(__ballot(fell_back));
-        if ((threadIdx.x & 63u) == 0u) w_n[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long total = w_n[0] + w_n[1] + w_n[2] + w_n[3];
-            if (total) atomicAdd(&head->counters, total);
-        }
+        const unsigned long long n[1] = {((unsigned long long)wave_count(is_flat) << 32) | wave_count(fell_back)};
+        block_add_waves(n, &head->counters);                           // (packed: one atomic for both)
     }
 }
 
@@ -324,8 +301,7 @@ __global__ __launch_bounds__(256) void k_adaptive_choose(const int *__restrict__
             used[k] = 1;
         }
     }
-    const unsigned long long n = (unsigned long long)__popcll(__ballot(take));
-    if ((threadIdx.x & 63u) == 0u && n) atomicAdd(counters + 0, n);
+    wave_add(wave_count(take), counters + 0);
 }
 
 // one lane per cluster of the level, after k_adaptive_choose: the used clusters and their flags, one integer atomic per wave each
@@ -334,14 +310,9 @@ __global__ __launch_bounds__(256) void k_adaptive_count(const unsigned char *__r
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool u = k < n_clusters && used[k] != 0;
     const unsigned char f = u ? cflags[k] : (unsigned char)0;
-    const unsigned long long n_used = (unsigned long long)__popcll(__ballot(u));
-    const unsigned long long n_flat = (unsigned long long)__popcll(__ballot((f & IS_FLAT) != 0));
-    const unsigned long long n_back = (unsigned long long)__popcll(__ballot((f & FELL_BACK) != 0));
-    if ((threadIdx.x & 63u) == 0u) {
-        if (n_used) atomicAdd(counters + 1, n_used);
-        if (n_flat) atomicAdd(counters + 2, n_flat);
-        if (n_back) atomicAdd(counters + 3, n_back);
-    }
+    wave_add(wave_count(u), counters + 1);
+    wave_add(wave_count((f & IS_FLAT) != 0), counters + 2);
+    wave_add(wave_count((f & FELL_BACK) != 0), counters + 3);
 }
 
 __global__ __launch_bounds__(256) void k_adaptive_unchosen(long long *__restrict__ id, long long n_vertices) {
@@ -424,9 +395,7 @@ static int cluster_level(const char *who, hipStream_t st, const double *d_points
     if (h_head.n_bad) return fail(std::string(who) + std::to_string(h_head.n_bad) + " vertices are not finite");
     int x_bits = KEY_BITS;
     for (int c = 0; c < 3; c++) {
-        double lo, hi;
-        const unsigned long long ul = box_bits(h_head.box[c]), uh = box_bits(h_head.box[3 + c]);
-        memcpy(&lo, &ul, 8); memcpy(&hi, &uh, 8);
+        const double lo = box_value(h_head.box[c]), hi = box_value(h_head.box[3 + c]);
         if (!(std::fabs(lo) < 9007199254740992.0 && std::fabs(hi) < 9007199254740992.0) || !(hi - lo < (double)(1ll << KEY_BITS)))
             return fail(std::string(who) + "the clusters span 2^21 or more cells on an axis (the cell is too small for this mesh)");
         g.fqmin[c] = lo;

@@ -77,6 +77,18 @@ def test_a_random_field(eng):
     same(contour.contour_grid(V, X, Y, level, eng=eng), want, 'random with non-finite samples')
 
 
+@pytest.mark.parametrize('ny', (2, 66, 258))
+def test_nonfinite_cells_are_counted_at_ragged_sizes(eng, ny):
+    """1, 65 and 257 cells -- one lane, a partial last wave, a partial last workgroup -- with non-finite samples at both ends: the
+    workgroup's count is the definition's"""
+    V, X, Y, level = cases.random_field(2, ny, 1, seed=ny)
+    V[0, 0, ny - 1] = np.nan
+    V[0, 1, 0] = np.inf
+    want = ref.contours(V, X, Y, level)
+    assert want['nonfinite_cells'] == (1 if ny == 2 else 2)
+    same(contour.contour_grid(V, X, Y, level, eng=eng), want, '2 x %d with non-finite samples' % ny)
+
+
 def test_one_contour_that_needs_every_round(eng):
     """a comb drawn into 257 x 257 samples: ONE closed loop of tens of thousands of segments, so the last doubling round still moves
     information -- a round count that is one short, or a round that reads what it writes, changes the leader or the positions"""

@@ -378,6 +378,27 @@ def test_a_vertex_that_is_not_finite(bad, eng):
         s.close()
 
 
+@pytest.mark.parametrize('v', (1, 65, 257))
+def test_the_refusal_counts_the_vertices_that_are_not_finite(v, eng):
+    """1, 65 and 257 welded vertices -- one lane, a partial last wave, a partial last workgroup -- of a strip whose welded order is its
+    own (x ascends); the vertices that are not finite lie in every wave and in both workgroups, and the refusal quotes how many the
+    mesh's own weld holds"""
+    x = np.arange(v, dtype=np.float64)
+    p = np.stack([x, np.sin(x), np.cos(x)], axis=1)
+    marks = [k for k in (0, 63, 64, 130, 200, 255, 256) if k < v]
+    p[marks, 2] = np.where(np.arange(len(marks)) % 2, -np.inf, np.inf)      # (infinities weld like any value; a NaN equals nothing)
+    i = np.arange(max(v - 2, 1))
+    tris = np.stack([p[i], p[np.minimum(i + 1, v - 1)], p[np.minimum(i + 2, v - 1)]], axis=1)
+    s = Soup(eng, tris)
+    try:
+        pts, cells = s.mesh.weld()
+        assert len(pts) == v and list(np.flatnonzero(~np.isfinite(pts).all(axis=1))) == marks
+        with pytest.raises(engine.SdfHipError, match=': %d vertices are not finite' % len(marks)):
+            s.mesh.simplify(np.zeros(3), np.ones(3))
+    finally:
+        s.close()
+
+
 def _free(lib):
     f, t = ctypes.c_size_t(0), ctypes.c_size_t(0)
     assert lib.sdf_device_mem_info(0, ctypes.byref(f), ctypes.byref(t)) == 0
