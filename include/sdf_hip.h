@@ -393,6 +393,28 @@ int sdf_mesh_vertex_thickness(sdf_mesh *mesh, sdf_tape *tape, const double *para
                               double *h_thickness, uint8_t *h_status, int32_t *h_steps);
 /* the kernel of this thread's last successful sdf_mesh_vertex_thickness alone, milliseconds by HIP events (tools/thickness_time.py) */
 double sdf_mesh_thickness_last_kernel_ms(void);
+/* The curvature of the field's level set at the welded vertices (added under ABI 17: the version is unchanged, nothing above changes;
+ * DESIGN.md section 4t, defined by tests/curvature_ref.py and reproduced bit for bit): at every unique vertex p of sdf_mesh_weld the
+ * field f is evaluated 19 times -- v0 = f(p); for axis a = x, y, z the values va+, va- at p with coordinate a moved by + eps and by
+ * + (-eps); for the pairs (a, b) = (x, y), (x, z), (y, z) the values v++, v+-, v-+, v-- with a moved by +-eps, then b.  From them
+ * G_a = (va+ - va-) / (2 eps), H_aa = ((va+ - v0) + (va- - v0)) / (eps eps), H_ab = ((v++ - v+-) - (v-+ - v--)) / ((4 eps) eps);
+ * L2 = (Gx Gx + Gy Gy) + Gz Gz, L = sqrt(L2), tr = (Hxx + Hyy) + Hzz, gMg = ((Gx Gx Mxx + Gy Gy Myy) + Gz Gz Mzz) + 2 ((Gx Gy Mxy +
+ * Gx Gz Mxz) + Gy Gz Myz) for a symmetric M (products left to right); mean = (L2 tr - gHg) / ((2 L2) L); gauss = gAg / (L2 L2)
+ * with A the cofactors of H (Axx = Hyy Hzz - Hyz Hyz, Ayy = Hxx Hzz - Hxz Hxz, Azz = Hxx Hyy - Hxy Hxy, Axy = Hxz Hyz - Hxy Hzz,
+ * Axz = Hxy Hyz - Hxz Hyy, Ayz = Hxy Hxz - Hxx Hyz); disc = mean mean - gauss, 0 where it is not > 0; k1 = mean + sqrt(disc),
+ * k2 = mean - sqrt(disc).  The field is negative inside, so convex is positive: a sphere of radius R has k1 = k2 = 1 / R, a cavity
+ * is negative.  Status, in this order: NAN (2) where one of the 19 values is not finite; FLAT (1) where L2 == 0 or L is not finite;
+ * NAN (2) where one of the four results is not finite; else CURVED (0).  A vertex that is not CURVED holds the bits
+ * 0x7ff8000000000000 in all four outputs.  Outputs, one per welded vertex: h_curv4 4 x float64 (mean, gauss, k1, k2), h_status
+ * uint8; h_counts3: the vertices of status 0, 1, 2.  Float64, the interpreter of sdf_eval_points, one rounding per operation.  It
+ * serves every mesh of the context that has been welded, like sdf_mesh_vertex_thickness.  Synchronous, on the context's stream; one
+ * device allocation (33 bytes per vertex), freed before it returns; nothing is kept with the mesh.  A mesh of 0 vertices returns 0
+ * without a launch.  Refused on the host before anything is allocated or launched, with return value 2: a NULL argument, a mesh
+ * that is not welded, a tape of another context, a tape with user closures (sdf_tape_extern_count > 0), an eps that is not finite
+ * or not above 0.  Other failures return 1. */
+int sdf_mesh_vertex_curvature(sdf_mesh *mesh, sdf_tape *tape, double eps, double *h_curv4, uint8_t *h_status, int64_t *h_counts3);
+/* the kernel of this thread's last successful sdf_mesh_vertex_curvature alone, milliseconds by HIP events (tools/curvature_time.py) */
+double sdf_mesh_curvature_last_kernel_ms(void);
 /* A mesh held to the field (added under ABI 17: the version is unchanged, nothing above changes; DESIGN.md section 4q, defined by
  * tests/deviation_ref.py and reproduced bit for bit).  Float64, the interpreter of sdf_eval_points, one rounding per operation.
  *

@@ -413,7 +413,7 @@ generate_mesh.last_snap = None
 
 
 def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False,
-         simplify_tolerance=None, simplify_levels=5, snap=False, **kwargs):
+         simplify_tolerance=None, simplify_levels=5, snap=False, curvature=False, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
@@ -427,10 +427,14 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     section 4l; the direction's step is normal_eps); the native writer only, any other extension or writer raises ValueError before
     anything is meshed, and the file's body is packed on the host: it is not the fast path.  May be combined with normals=True.
     snap: True or a dict of eps, tol, max_move, iters -- after simplify and before mend the vertices are put back on the zero set of
-    the field, and the file holds the moved mesh (`sdf_amd/deviation.py`)."""
+    the field, and the file holds the moved mesh (`sdf_amd/deviation.py`).  curvature: 'mean', 'gauss', 'k1',
+    'k2' or 'max' (of k1 and k2 the one of larger magnitude, signed), or a dict of `quality` (one of these, default 'mean') and `eps`
+    -- the vertices of a .ply file carry that curvature of the field at the final mesh's vertices as `property float quality`
+    (`sdf_amd/curvature.py`; eps defaults to the smallest grid step), through the same door and under the same
+    rules as thickness=; a file has one quality column, so thickness= and curvature= together raise ValueError."""
     from . import meshfile
     path = os.fspath(path)
-    how = meshfile.choose_writer(path, writer, normals, bool(thickness))
+    how = meshfile.choose_writer(path, writer, normals, bool(thickness), bool(curvature))
     ply = path.lower().endswith('.ply')
     if simplify is not None:      # (simplify=None is the call without the argument)
         kwargs['simplify'] = simplify
@@ -447,8 +451,15 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
             raise ValueError('thickness: unknown probe arguments %s' % sorted(unknown))
         check_params(1.0 if normal_eps is None else normal_eps, probe.get('start', 1.0), probe.get('min_step', 1.0),
                      probe.get('t_far', np.finfo(np.float64).max), probe.get('step_scale', 1.0), probe.get('max_steps', 256), probe.get('refine', 16))
+    if curvature:                 # (refused before anything is meshed, too)
+        from .curvature import default_eps, quality_of, read_curvature, save_option
+        which, curvature_eps = save_option(curvature)
     with meshed(*args, keep=keep, **kwargs) as m:
-        if thickness:
+        if curvature:
+            got = read_export(m, bool(normals), normal_eps)
+            steps3 = grid_axes(m.bounds, args[1] if len(args) > 1 else kwargs.get('step'), args[3] if len(args) > 3 else kwargs.get('samples', SAMPLES))[3]
+            quality = quality_of(read_curvature(m, default_eps(steps3, curvature_eps), with_mesh=False)[2], which)
+        elif thickness:
             got = read_export(m, bool(normals), normal_eps)
             steps3 = grid_axes(m.bounds, args[1] if len(args) > 1 else kwargs.get('step'), args[3] if len(args) > 3 else kwargs.get('samples', SAMPLES))[3]
             params = dict(default_params(m.bounds, steps3, probe.get('start'), probe.get('min_step'), probe.get('t_far'), normal_eps),
@@ -460,7 +471,7 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
             records = read_stl_records(m)
         else:
             points, cells = read_weld(m)
-    if thickness:
+    if thickness or curvature:
         vb, fb = meshfile.ply_records(got['points'], got['cells'], got['normals'], quality)
         meshfile.write_ply(path, vb, fb, got['n_vertices'], got['n_faces'], bool(normals), quality=True)
     elif how == 'native' and ply:

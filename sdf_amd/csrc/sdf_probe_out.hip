@@ -1,13 +1,14 @@
 // sdf_probe_out.hip -- the host entries of the field probes: what takes a tape to a finished mesh or to an image --
-// field normals and the wall thickness at the welded vertices, the deviation of the triangles from the field and the vertices snapped
-// onto it, the support rays, the sphere-traced image.  Host code only: it launches through the launchers of sdf_normals.h,
-// sdf_thickness.h, sdf_deviation.h, sdf_supports.h, sdf_render.h and sdf_plain.h, built WITHOUT the interpreters' structurizer option
+// field normals, the wall thickness and the curvature at the welded vertices, the deviation of the triangles from the field and the
+// vertices snapped onto it, the support rays, the sphere-traced image.  Host code only: it launches through the launchers of sdf_normals.h,
+// sdf_thickness.h, sdf_curvature.h, sdf_deviation.h, sdf_supports.h, sdf_render.h and sdf_plain.h, built WITHOUT the interpreters' structurizer option
 // (build.units).  Every entry returns 0: done, 1: HIP error, 2: refused (nothing allocated, nothing launched); sdf_last_error says why.
 // What the entries share stands in front of them, and an entry uses it where its own lines stood.
 #include <cmath>
 #include <cstring>
 
 #include "sdf_internal.h"
+#include "sdf_curvature.h"
 #include "sdf_deviation.h"
 #include "sdf_normals.h"
 #include "sdf_plain.h"
@@ -125,6 +126,37 @@ int sdf_mesh_vertex_thickness(sdf_mesh *m, sdf_tape *t, const double *params6, i
 }
 
 double sdf_mesh_thickness_last_kernel_ms(void) { return g_thickness_kernel_ms; }
+
+// ---- the curvature of the field's level set at the welded vertices: mean, Gaussian, principal ----
+static thread_local double g_curvature_kernel_ms = 0.0;
+
+int sdf_mesh_vertex_curvature(sdf_mesh *m, sdf_tape *t, double eps, double *h_curv4, uint8_t *h_status, int64_t *h_counts3) {
+    if (!m || !t || !h_curv4 || !h_status || !h_counts3) REFUSE("NULL argument");
+    if (probe_refused(__func__, m, t, true, "take the curvature over sdf_eval_points_extern_host")) return 2;
+    if (!(std::isfinite(eps) && eps > 0.0)) REFUSE("eps must be finite and positive");
+    const long long nu = m->weld_n;
+    for (int k = 0; k < 3; k++) h_counts3[k] = 0;
+    if (nu == 0) return 0;
+    sdf_ctx *c = m->ctx;
+    HIPCHK(set_device(c->device));
+    hipStream_t st = c->stream;
+    double *curv;
+    unsigned long long *counts;
+    uint8_t *status;
+    Scratch scratch(st);
+    scratch.part(&curv, (size_t)nu * 4); scratch.part(&counts, (size_t)3); scratch.part(&status, (size_t)nu);
+    EventTimer timer;
+    HIPCHK_MSG("sdf_mesh_vertex_curvature: hipMalloc(" + std::to_string(scratch.bytes) + "): ", scratch.alloc());
+    HIPCHK_FN(hipMemsetAsync(counts, 0, 24, st));
+    TIMED_LAUNCH(st, HIPCHK_FN((hipError_t)launch_vertex_curvature(st, t->d_code, t->d_c64, t->full, m->weld_pts.as<double>(), nu, eps, curv, status, counts)));
+    HIPCHK_FN(hipMemcpyAsync(h_curv4, curv, (size_t)nu * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_status, status, (size_t)nu, hipMemcpyDeviceToHost, st));
+    HIPCHK_FN(hipMemcpyAsync(h_counts3, counts, 24, hipMemcpyDeviceToHost, st));
+    TIMED_RESULTS(st, &g_curvature_kernel_ms);
+    return 0;
+}
+
+double sdf_mesh_curvature_last_kernel_ms(void) { return g_curvature_kernel_ms; }
 
 // ---- a mesh held to the field: the deviation of every triangle, the welded vertices snapped onto the zero set ----
 static thread_local double g_deviation_kernel_ms = 0.0;

@@ -80,6 +80,10 @@ class SDF3(SDFBase):
         from .thickness import thickness
         return thickness(self, *args, **kwargs)
 
+    def curvature(self, *args, **kwargs):
+        from .curvature import curvature
+        return curvature(self, *args, **kwargs)
+
     def deviation(self, *args, **kwargs):
         from .deviation import deviation
         return deviation(self, *args, **kwargs)

@@ -207,6 +207,8 @@ ABI = {
     'sdf_mesh_normals_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_vertex_thickness': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _u8p, ctypes.POINTER(ctypes.c_int32)]),
     'sdf_mesh_thickness_last_kernel_ms': (ctypes.c_double, []),
+    'sdf_mesh_vertex_curvature': (ctypes.c_int, [_vp, _vp, ctypes.c_double, _f64p, _u8p, ctypes.POINTER(ctypes.c_int64)]),
+    'sdf_mesh_curvature_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_triangle_deviation': (ctypes.c_int, [_vp, _vp, ctypes.c_int, _f64p, ctypes.POINTER(ctypes.c_int32), _f64p]),
     'sdf_mesh_deviation_last_kernel_ms': (ctypes.c_double, []),
     'sdf_mesh_snap': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, ctypes.POINTER(_vp), _f64p, _u8p, _f64p, ctypes.POINTER(ctypes.c_int32),
@@ -547,6 +549,28 @@ class Mesh:
         _check(eng.lib, eng.lib.sdf_mesh_vertex_thickness(self.handle, dt.handle, _dp(p6, _f64p), params[5], params[6], _dp(th, _f64p),
                                                           _dp(status, _u8p), _dp(steps, ctypes.POINTER(ctypes.c_int32))))
         return th, status, steps
+
+    def vertex_curvature(self, sdf_or_tape, eps):
+        """(curv (U, 4) float64: mean, gauss, k1, k2; status (U,) uint8; counts (3,) int64): the curvature of the FIELD's level set at
+        the U welded vertices (sdf_mesh_vertex_curvature, csrc/sdf_curvature.hip; defined by
+        tests/curvature_ref.py and reproduced bit for bit).  The gradient and the Hessian are second differences of 19 values at
+        step eps; mean and Gaussian curvature are closed forms in them, k1 >= k2 the principal curvatures; convex is positive.
+        status: 0 CURVED, 1 FLAT (no gradient), 2 NAN (the field or a result was not finite); a vertex that is not CURVED holds
+        np.nan's bits in all four.  counts: the vertices of each status, counted on the device.  A model with user closures takes
+        the same definition over `Engine.eval_points` on the host.  Raises ValueError, before any device work, for an eps that is
+        not finite and positive and for an engine in float32 precision."""
+        from .curvature import check_params, vertex_curvature       # (the package's attribute `curvature` is the function)
+        eng = self.engine
+        eps = check_params(eps)
+        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_curvature takes second differences')
+        if on_host:
+            curv, status = vertex_curvature(lambda P: eng.eval_points(dt, P), self.weld()[0], eps)
+            return curv, status, np.bincount(status, minlength=3).astype(np.int64)
+        nu = self._welded()
+        curv, status, counts = np.empty((nu, 4), np.float64), np.empty(nu, np.uint8), np.zeros(3, np.int64)
+        _check(eng.lib, eng.lib.sdf_mesh_vertex_curvature(self.handle, dt.handle, eps, _dp(curv, _f64p), _dp(status, _u8p),
+                                                          _dp(counts, ctypes.POINTER(ctypes.c_int64))))
+        return curv, status, counts
 
     def triangle_deviation(self, sdf_or_tape, order=2):
         """(dev (T,) float64, at (T,) int32, sumsq (T,) float64): how far every triangle of the soup lies from the zero set of the
@@ -1017,7 +1041,7 @@ class Engine:
         return dt
 
     def _probe_tape(self, sdf, verb):
-        """the six field probes, behind the checks of their own parameters: refuse float32 precision (`verb`: what the probe does
+        """the seven field probes, behind the checks of their own parameters: refuse float32 precision (`verb`: what the probe does
         in float64), then (the device tape, whether it reads user closures -- the probe's definition on the host serves those)"""
         if self.precision != PRECISION_F64:
             raise ValueError('%s in float64 only; this engine is set to float32 precision' % verb)

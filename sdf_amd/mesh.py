@@ -114,6 +114,17 @@ class Mesh:
         params = default_params((pts.min(axis=0), pts.max(axis=0)), steps3, start, min_step, t_far, normal_eps)
         return thickness_of_soup(pts[np.asarray(self.triangles)], f, step_scale=step_scale, max_steps=max_steps, refine=refine, **params)
 
+    def curvature(self, f, step=None, eps=None):
+        """the curvature of the field `f` at the vertices of this mesh (sdf_amd/curvature.py): a `Curvature`
+        over the vertices of the soup welded on the device.  A file has no sampling grid, so `step` must be given (eps = the
+        smallest of its components: curvature at the scale the mesh can show), or eps itself."""
+        from .curvature import curvature_of_soup, default_eps
+        pts = np.asarray(self.points, dtype=np.float64)
+        if len(pts) == 0:
+            raise ValueError('curvature: the mesh has no vertices')
+        steps3 = None if step is None else tuple(np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)).tolist())
+        return curvature_of_soup(pts[np.asarray(self.triangles)], f, default_eps(steps3, eps))
+
     def deviation(self, f, order=2):
         """how far this mesh lies from the zero set of the field `f`, sampled on the device on every triangle (sdf_amd/deviation.py,
         DESIGN.md section 4q): a `Deviation`"""

@@ -130,20 +130,24 @@ def _has_meshio():
         return False
 
 
-def choose_writer(path, writer=None, normals=False, thickness=False):
+def choose_writer(path, writer=None, normals=False, thickness=False, curvature=False):
     """which writer `save` uses for `path`: 'stl', 'meshio' or 'native'.  writer=None: native when normals are asked for,
     else meshio where it imports (as before there was a native writer), else native for .ply / .obj.  Raises ValueError for
     what no writer serves (vertex normals in an STL file or through meshio, a native extension other than .ply / .obj, an
     unknown writer) and ImportError where only meshio could serve and it is not installed.  thickness: the file is to carry the
-    wall thickness per vertex -- .ply and the native writer only, anything else raises ValueError."""
+    wall thickness per vertex -- .ply and the native writer only, anything else raises ValueError.  curvature: it is to carry a
+    curvature per vertex, through the same door; a file has one `quality` column, so both together raise ValueError."""
     ext = os.path.splitext(os.fspath(path))[1].lower()
     if writer not in (None, 'native', 'meshio'):
         raise ValueError("writer must be None, 'native' or 'meshio', got %r" % (writer,))
-    if thickness:
+    if thickness and curvature:
+        raise ValueError('a .ply file has one `quality` property: give thickness= or curvature=, not both')
+    if thickness or curvature:
+        what = 'wall thickness' if thickness else 'curvature'
         if ext != '.ply':
-            raise ValueError("the wall thickness is written as a .ply file's `quality` property, not into %r" % (ext,))
+            raise ValueError("the %s is written as a .ply file's `quality` property, not into %r" % (what, ext))
         if writer == 'meshio':
-            raise ValueError("the meshio writer does not write the wall thickness: use writer='native'")
+            raise ValueError("the meshio writer does not write the %s: use writer='native'" % what)
         return 'native'
     if ext == '.stl':
         if normals:

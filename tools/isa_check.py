@@ -45,7 +45,7 @@ def find_objdump():
 
 OBJDUMP = find_objdump()
 INTERP = ('k_mesh', 'k_skip', 'k_eval_points', 'k_eval_grid', 'k_eval_tiles', 'k_estimate_bounds', 'k_render', 'k_vertex_normals', 'k_vertex_thickness', 'k_support_rays',
-          'k_triangle_deviation', 'k_vertex_snap')
+          'k_triangle_deviation', 'k_vertex_snap', 'k_vertex_curvature')
 INTERVAL = ('k_cull', 'k_prune_list')       # the interval-arithmetic interpreters (sdf_interval.h): a switch, no jump table
 PLAIN = ('k_compact', 'k_scan_rows', 'k_scan_items', 'k_emit2', 'k_expand', 'k_pack_slab', 'k_mc_rows', 'k_mc_emit', 'k_field_rows',
          'k_field_emit', 'k_stl', 'k_ply_vertices', 'k_ply_faces', 'k_gather_soup', 'k_cast_f32', 'k_collect_headers', 'k_ls_dist', 'k_ls_sign', 'k_ls_parity', 'k_ls_compose', 'k_ls_crop', 'k_edt_scan', 'k_edt_min')
