@@ -156,6 +156,13 @@ def grid_axes(bounds, step=None, samples=SAMPLES):
     return X, Y, Z, (dx, dy, dz)
 
 
+def need_device_mesh(mesh, name, words):
+    """the refusal, in `name`'s words, of a soup that a multi-process run gathered on the host: there is no mesh on the device to read"""
+    if mesh is None:
+        raise NotImplementedError('%s: the soup of this multi-process run was gathered on the host; %s on the device only '
+                                  '(run it in one process, or with a device-resident exchange)' % (name, words))
+
+
 Meshed = collections.namedtuple('Meshed', ('mesh', 'points', 'tape', 'engine', 'bounds', 'stats', 'simplify_stats'), defaults=(None,))
 Meshed.__doc__ = """what `meshed` yields.  mesh: the `engine.Mesh` on the device (the selection under keep=, the simplified mesh under
 simplify=, the mended mesh under mend=True -- its statistics ride on it: `mesh.mend_stats`), or None when a multi-process run gathered its soup on the host -- then points is that soup, (3T, 3) float64; tape,
@@ -232,40 +239,38 @@ def meshed(
         else:
             mesh = eng.generate(tape, X, Y, Z, batch_size, sparse, records=to_host)
             stats = mesh.stats()
-        if keep is not None:
-            if mesh is None:
-                raise NotImplementedError('keep: the soup of this multi-process run was gathered on the host; shells are found and '
-                                          'selected on the device only (run it in one process, or with a device-resident exchange)')
+
+        # the stages, each from the current mesh to the new one; the frame below them refuses, calls, closes and hands over
+        def kept(mesh):
             # (choosing by size brings the per-shell counts over the link and nothing else; a callable is handed the whole `Shells`)
             got = shells_of_mesh(mesh) if callable(keep) else mesh.shell_summary()['triangles']
-            sel = mesh.select(resolve_keep(keep, got))
-            mesh.close()
-            mesh = sel
-        if simplify is not None:
-            if mesh is None:
-                raise NotImplementedError('simplify: the soup of this multi-process run was gathered on the host; a mesh is simplified on '
-                                          'the device only (run it in one process, or with a device-resident exchange)')
+            return mesh.select(resolve_keep(keep, got))
+
+        def simplified(mesh):
+            nonlocal simplify_stats
             origin, cell = resolve_cell(simplify, X, Y, Z, (dx, dy, dz))
             small = mesh.simplify(origin, cell) if simplify_tolerance is None else mesh.simplify_adaptive(origin, cell, simplify_tolerance, simplify_levels)
-            mesh.close()
-            mesh = small
             simplify_stats = small.simplify_stats
-        if snap is not None:
-            if mesh is None:
-                raise NotImplementedError('snap: the soup of this multi-process run was gathered on the host; a mesh is snapped on '
-                                          'the device only (run it in one process, or with a device-resident exchange)')
-            moved = mesh.snap(tape, **snap_params(snap, bounds, (dx, dy, dz), simplify))
-            mesh.close()
-            mesh = moved
-        if mend:
-            if mesh is None:
-                raise NotImplementedError('mend: the soup of this multi-process run was gathered on the host; a mesh is mended on '
-                                          'the device only (run it in one process, or with a device-resident exchange)')
-            mended = mesh.mend()
+            return small
+
+        def snapped(mesh):
+            return mesh.snap(tape, **snap_params(snap, bounds, (dx, dy, dz), simplify))
+
+        def mended(mesh):
+            new = mesh.mend()
             if snap is not None:
-                mended.snap_stats = mesh.snap_stats
-            mesh.close()
-            mesh = mended
+                new.snap_stats = mesh.snap_stats
+            return new
+
+        for name, asked, words, stage in (('keep', keep is not None, 'shells are found and selected', kept),
+                                          ('simplify', simplify is not None, 'a mesh is simplified', simplified),
+                                          ('snap', snap is not None, 'a mesh is snapped', snapped),
+                                          ('mend', mend, 'a mesh is mended', mended)):
+            if asked:
+                need_device_mesh(mesh, name, words)
+                new = stage(mesh)
+                mesh.close()
+                mesh = new
         yield Meshed(mesh, points, tape, eng, bounds, stats, simplify_stats)
         triangles = mesh.n_triangles if mesh is not None else len(points) // 3
     finally:
@@ -279,11 +284,35 @@ def meshed(
     generate.last_stats = stats
 
 
-def _tolerance_kwargs(simplify_tolerance, simplify_levels):
-    """what a reader passes on to `meshed` for its two keywords: nothing when they are the defaults (the call without them)"""
-    if simplify_tolerance is None and isinstance(simplify_levels, int) and not isinstance(simplify_levels, bool) and simplify_levels == 5:
-        return {}
-    return {'simplify_tolerance': simplify_tolerance, 'simplify_levels': simplify_levels}
+def pipeline_kwargs(generate_kwargs, simplify=None, simplify_tolerance=None, simplify_levels=5, mend=False, snap=False):
+    """the keywords of `meshed` for a facade's call: its generate_kwargs and, of the pipeline's options, those that are not the
+    default.  A default is left out, not passed: `meshed` is looked up at call time, and what stands in for it -- the stand-ins of
+    the host tests, a caller's own wrapper -- then sees the call that was made and needs no knowledge of a keyword it was never
+    given; only the defaults themselves are left out, what merely compares equal (5.0, True, None for False) goes on for
+    `meshed` to judge.  `overhangs` and `supports` have no snap= and pass none: one in their generate_kwargs rides on as it is."""
+    kw = dict(generate_kwargs)
+    if simplify is not None:
+        kw['simplify'] = simplify
+    if not (simplify_tolerance is None and isinstance(simplify_levels, int) and not isinstance(simplify_levels, bool) and simplify_levels == 5):
+        kw.update(simplify_tolerance=simplify_tolerance, simplify_levels=simplify_levels)
+    if mend is not False:
+        kw['mend'] = mend
+    if snap is not False:
+        kw['snap'] = snap
+    return kw
+
+
+def grid_steps(m, call):
+    """(dx, dy, dz) of the meshing call that the `Meshed` m came from: out of its bounds and the `step` and `samples` among the
+    call's keywords, as `meshed` computed them"""
+    return grid_axes(m.bounds, call.get('step'), call.get('samples', SAMPLES))[3]
+
+
+def default_normal_eps(bounds):
+    """the step of the central difference that gives a normal, 1e-4 x the half-diagonal of the bounds: the preview's value
+    (render.render_buffers), so that a file, a probe and a preview of one model see the same normals"""
+    lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
+    return 1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2)
 
 
 @contextlib.contextmanager
@@ -328,18 +357,16 @@ def read_export(m, normals=False, eps=None, ply=False):
     the half-diagonal of the bounds; k_vertex_normals) -- a dict of `n_vertices`, `n_faces`, `normals` ((U, 3) float64 or None),
     `n_flat` and, with `ply`, the device-packed PLY body `ply` = (vertex_bytes, face_bytes); otherwise `points`, `cells` of the weld.
     A soup gathered on the host takes its normals from the definition over eval_points and its PLY body from the host packer."""
-    from . import meshfile
+    from . import engine, meshfile
     out = {'normals': None, 'n_flat': 0}
     if normals and eps is None:
-        # (the preview's value, render.render_buffers: a file and a preview of one model show the same normals)
-        lo, hi = np.asarray(m.bounds[0], dtype=np.float64), np.asarray(m.bounds[1], dtype=np.float64)
-        eps = 1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2)
+        eps = default_normal_eps(m.bounds)
     mesh = m.mesh
     if mesh is None:
         pts, cells = read_weld(m)
         out.update(points=pts, cells=cells, n_vertices=len(pts), n_faces=len(cells))
         if normals:
-            out['normals'], out['n_flat'] = meshfile.vertex_normals(lambda P: m.engine.eval_points(m.tape, P), pts, eps)
+            out['normals'], out['n_flat'] = meshfile.vertex_normals(engine.evaluator(m.engine, m.tape), pts, eps)
         if ply:
             out['ply'] = meshfile.ply_records(pts, cells, out['normals'])
         return out
@@ -388,14 +415,7 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
     vertices are put back on the zero set of the field (`sdf_amd/deviation.py`; `generate_mesh.last_snap` holds
     the statistics of the last call that snapped); the normals are then the field's at the snapped vertices.  Not in the reference
     (DESIGN.md section 4f)."""
-    if simplify is not None:      # (simplify=None is the call without the argument)
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if snap is not False:         # (snap=False is the call without the argument)
-        generate_kwargs['snap'] = snap
-    if mend is not False:         # (mend=False is the call without the argument)
-        generate_kwargs['mend'] = mend
-    with meshed(sdf, keep=keep, **generate_kwargs) as m:
+    with meshed(sdf, keep=keep, **pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
         got = read_export(m, bool(normals), normal_eps)
         generate_mesh.last_simplify = m.simplify_stats
         if mend:
@@ -436,13 +456,7 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     path = os.fspath(path)
     how = meshfile.choose_writer(path, writer, normals, bool(thickness), bool(curvature))
     ply = path.lower().endswith('.ply')
-    if simplify is not None:      # (simplify=None is the call without the argument)
-        kwargs['simplify'] = simplify
-    kwargs.update(_tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:         # (mend=False is the call without the argument)
-        kwargs['mend'] = mend
-    if snap is not False:         # (snap=False is the call without the argument)
-        kwargs['snap'] = snap
+    call = dict(zip(('sdf', 'step', 'bounds', 'samples'), args), **kwargs)      # (the positional arguments of `meshed`, by name)
     if thickness:                 # (refused before anything is meshed, like the extension above)
         from .thickness import check_params, default_params, read_thickness
         probe = dict(thickness) if isinstance(thickness, dict) else {}
@@ -454,15 +468,13 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     if curvature:                 # (refused before anything is meshed, too)
         from .curvature import default_eps, quality_of, read_curvature, save_option
         which, curvature_eps = save_option(curvature)
-    with meshed(*args, keep=keep, **kwargs) as m:
+    with meshed(*args, keep=keep, **pipeline_kwargs(kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
         if curvature:
             got = read_export(m, bool(normals), normal_eps)
-            steps3 = grid_axes(m.bounds, args[1] if len(args) > 1 else kwargs.get('step'), args[3] if len(args) > 3 else kwargs.get('samples', SAMPLES))[3]
-            quality = quality_of(read_curvature(m, default_eps(steps3, curvature_eps), with_mesh=False)[2], which)
+            quality = quality_of(read_curvature(m, default_eps(grid_steps(m, call), curvature_eps), with_mesh=False)[2], which)
         elif thickness:
             got = read_export(m, bool(normals), normal_eps)
-            steps3 = grid_axes(m.bounds, args[1] if len(args) > 1 else kwargs.get('step'), args[3] if len(args) > 3 else kwargs.get('samples', SAMPLES))[3]
-            params = dict(default_params(m.bounds, steps3, probe.get('start'), probe.get('min_step'), probe.get('t_far'), normal_eps),
+            params = dict(default_params(m.bounds, grid_steps(m, call), probe.get('start'), probe.get('min_step'), probe.get('t_far'), normal_eps),
                           step_scale=float(probe.get('step_scale', 1.0)), max_steps=int(probe.get('max_steps', 256)), refine=int(probe.get('refine', 16)))
             quality = read_thickness(m, params, with_mesh=False)[2]
         elif how == 'native':

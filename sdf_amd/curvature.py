@@ -222,10 +222,10 @@ def default_eps(steps3, eps=None):
 def read_curvature(m, eps, with_mesh=True):
     """the probe on a `core.Meshed`: on the device, or -- a soup gathered on the host -- by the definition over eval_points.
     Returns (points, cells, curv, status); points and cells are None unless with_mesh."""
-    from . import core
+    from . import core, engine
     if m.mesh is None:
         pts, cells = core.read_weld(m)
-        return (pts, cells) + vertex_curvature(lambda P: m.engine.eval_points(m.tape, P), pts, eps)
+        return (pts, cells) + vertex_curvature(engine.evaluator(m.engine, m.tape), pts, eps)
     curv, status, _ = m.mesh.vertex_curvature(m.tape, eps)
     pts, cells = m.mesh.weld() if with_mesh else (None, None)
     return pts, cells, curv, status
@@ -241,18 +241,11 @@ def curvature(sdf, step=None, eps=None, keep=None, simplify=None, mend=False, si
     from . import core
     if step is not None:
         generate_kwargs['step'] = step
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    if snap is not False:
-        generate_kwargs['snap'] = snap
+    kw = core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)
     if eps is not None:
         check_params(eps)                                           # (what can be refused before meshing)
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
-        steps3 = core.grid_axes(m.bounds, generate_kwargs.get('step'), generate_kwargs.get('samples', core.SAMPLES))[3]
-        eps = default_eps(steps3, eps)
+    with core.meshed(sdf, keep=keep, **kw) as m:
+        eps = default_eps(core.grid_steps(m, kw), eps)
         pts, cells, curv, status = read_curvature(m, eps)
         return Curvature(pts, cells, curv, status, {'eps': eps})
 

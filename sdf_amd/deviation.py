@@ -60,12 +60,12 @@ def check_snap_option(snap):
 
 
 def snap_params(over, bounds, steps3, cluster=None):
-    """the arguments of `engine.Mesh.snap` for a mesh on the grid steps3 within bounds: eps = the preview's normal_eps (1e-4 x the
-    half-diagonal of the bounds), tol = 1e-3 x the smallest grid step, max_move = the diagonal of one cluster cell (cluster x the
+    """the arguments of `engine.Mesh.snap` for a mesh on the grid steps3 within bounds: eps = the preview's normal_eps
+    (`core.default_normal_eps`), tol = 1e-3 x the smallest grid step, max_move = the diagonal of one cluster cell (cluster x the
     grid step; one grid cell without simplify), iters = 4 -- each overridden by the dict `over`"""
-    lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
+    from . import core
     cell = np.asarray(steps3, dtype=np.float64) * (1.0 if cluster is None else float(cluster))
-    par = {'eps': 1e-4 * float(np.sqrt(np.dot(hi - lo, hi - lo)) / 2), 'tol': 1e-3 * float(min(steps3)),
+    par = {'eps': core.default_normal_eps(bounds), 'tol': 1e-3 * float(min(steps3)),
            'max_move': float(np.sqrt(np.dot(cell, cell))), 'iters': 4}
     par.update(over)
     eps, tol, max_move, iters = check_snap(par['eps'], par['tol'], par['max_move'], par['iters'])
@@ -239,10 +239,10 @@ class Deviation:
 def read_deviation(m, order):
     """the deviation of a `core.Meshed`: on the device, or -- a soup gathered on the host -- by the definition over eval_points.
     Returns (points, cells, dev, at, sumsq)."""
-    from . import core
+    from . import core, engine
     pts, cells = core.read_weld(m)
     if m.mesh is None:
-        return (pts, cells) + triangle_deviation(lambda P: m.engine.eval_points(m.tape, P), np.asarray(m.points).reshape(-1, 3, 3), order)
+        return (pts, cells) + triangle_deviation(engine.evaluator(m.engine, m.tape), np.asarray(m.points).reshape(-1, 3, 3), order)
     return (pts, cells) + m.mesh.triangle_deviation(m.tape, order)
 
 
@@ -253,14 +253,7 @@ def deviation(sdf, order=2, keep=None, simplify=None, simplify_tolerance=None, s
     iters -- the welded vertices are put back on the zero set first (`core.meshed`)."""
     from . import core
     order = check_order(order)
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if snap is not False:
-        generate_kwargs['snap'] = snap
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
+    with core.meshed(sdf, keep=keep, **core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
         pts, cells, dev, at, sumsq = read_deviation(m, order)
         return Deviation(pts, cells, dev, at, sumsq, order, getattr(m.mesh, 'snap_stats', None))
 

@@ -364,6 +364,16 @@ def _dp(a, t):
     return a.ctypes.data_as(t)
 
 
+def _stats_dict(st, fields, **more):
+    """the statistics dict of a ctypes struct: its integer `fields`, what the caller adds, kernel_ms"""
+    return dict({k: int(getattr(st, k)) for k in fields}, **more, kernel_ms=float(st.kernel_ms))
+
+
+def evaluator(eng, tape):
+    """the field of `tape` as a host evaluator P -> (N,) float64: what a probe's definition on the host takes"""
+    return lambda P: eng.eval_points(tape, P)
+
+
 class DeviceTape:
     """a lowered model resident on the device (`sdf_tape*`)"""
 
@@ -501,6 +511,14 @@ class Mesh:
                                                                        _dp(cells, ctypes.POINTER(ctypes.c_int64))))
         return pts, cells
 
+    def _derived(self, handle, **attrs):
+        """the Mesh that select, simplify, simplify_adaptive, mend or snap made, from its handle: nothing emitted, and the
+        attributes its maker names"""
+        m = Mesh(self.engine, handle)
+        m.emitted = False
+        vars(m).update(attrs)
+        return m
+
     def _welded(self):
         """number of unique vertices; welds (on the device) if that has not happened yet"""
         nu = ctypes.c_int64(0)
@@ -518,10 +536,10 @@ class Mesh:
         eps = float(eps)
         if not (np.isfinite(eps) and eps > 0):
             raise ValueError('eps must be finite and positive, got %r' % eps)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_normals takes the gradient')
-        if on_host:
+        dt, ev = eng._probe_tape(sdf_or_tape, 'vertex_normals takes the gradient')
+        if ev:
             from . import meshfile
-            return meshfile.vertex_normals(lambda P: eng.eval_points(dt, P), self.weld()[0], eps)
+            return meshfile.vertex_normals(ev, self.weld()[0], eps)
         nu = self._welded()
         out = pinned_empty(eng.lib, (nu, 3), np.float64)
         flat = ctypes.c_int64(0)
@@ -540,9 +558,9 @@ class Mesh:
         from .thickness import check_params, vertex_thickness      # (the package's attribute `thickness` is the function)
         eng = self.engine
         params = check_params(normal_eps, start, min_step, t_far, step_scale, max_steps, refine)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_thickness marches')
-        if on_host:
-            return vertex_thickness(lambda P: eng.eval_points(dt, P), self.weld()[0], *params)
+        dt, ev = eng._probe_tape(sdf_or_tape, 'vertex_thickness marches')
+        if ev:
+            return vertex_thickness(ev, self.weld()[0], *params)
         nu = self._welded()
         th, status, steps = np.empty(nu, np.float64), np.empty(nu, np.uint8), np.empty(nu, np.int32)
         p6 = np.array(params[:5] + [0.0], np.float64)
@@ -562,9 +580,9 @@ class Mesh:
         from .curvature import check_params, vertex_curvature       # (the package's attribute `curvature` is the function)
         eng = self.engine
         eps = check_params(eps)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'vertex_curvature takes second differences')
-        if on_host:
-            curv, status = vertex_curvature(lambda P: eng.eval_points(dt, P), self.weld()[0], eps)
+        dt, ev = eng._probe_tape(sdf_or_tape, 'vertex_curvature takes second differences')
+        if ev:
+            curv, status = vertex_curvature(ev, self.weld()[0], eps)
             return curv, status, np.bincount(status, minlength=3).astype(np.int64)
         nu = self._welded()
         curv, status, counts = np.empty((nu, 4), np.float64), np.empty(nu, np.uint8), np.zeros(3, np.int64)
@@ -583,9 +601,9 @@ class Mesh:
         from .deviation import check_order, triangle_deviation
         eng = self.engine
         order = check_order(order)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'triangle_deviation samples')
-        if on_host:
-            return triangle_deviation(lambda P: eng.eval_points(dt, P), np.asarray(self.points()).reshape(-1, 3, 3), order)
+        dt, ev = eng._probe_tape(sdf_or_tape, 'triangle_deviation samples')
+        if ev:
+            return triangle_deviation(ev, np.asarray(self.points()).reshape(-1, 3, 3), order)
         t = self.n_triangles
         dev, at, sumsq = np.empty(t, np.float64), np.empty(t, np.int32), np.empty(t, np.float64)
         _check(eng.lib, eng.lib.sdf_mesh_triangle_deviation(self.handle, dt.handle, order, _dp(dev, _f64p), _dp(at, ctypes.POINTER(ctypes.c_int32)),
@@ -607,14 +625,14 @@ class Mesh:
         from .deviation import STATUS_NAMES, check_snap, vertex_snap
         eng = self.engine
         eps, tol, max_move, iters = check_snap(eps, tol, max_move, iters)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'snap steps')
-        if on_host:
+        dt, ev = eng._probe_tape(sdf_or_tape, 'snap steps')
+        if ev:
             from . import core
             pts, cells = self.weld()
-            q, status, residual, evals = vertex_snap(lambda P: eng.eval_points(dt, P), pts, eps, tol, max_move, iters)
+            q, status, residual, evals = vertex_snap(ev, pts, eps, tol, max_move, iters)
             held = core.adopted(q[cells])                          # (the upload lives as long as the mesh over it)
             m = held.__enter__()
-            m._adopted = held
+            m._adopted, m.emitted = held, False
             stats = dict({'vertices': len(pts)}, kernel_ms=0.0, **{n.lower(): int((status == c).sum()) for c, n in enumerate(STATUS_NAMES)})
         else:
             nu = self._welded()
@@ -624,9 +642,7 @@ class Mesh:
             h, st = _vp(), SdfSnapStats()
             _check(eng.lib, eng.lib.sdf_mesh_snap(self.handle, dt.handle, _dp(p4, _f64p), iters, ctypes.byref(h), _dp(q, _f64p), _dp(status, _u8p),
                                                   _dp(residual, _f64p), _dp(evals, ctypes.POINTER(ctypes.c_int32)), ctypes.byref(st)))
-            m = Mesh(eng, h)
-            stats = dict({k: int(getattr(st, k)) for k in SNAP_FIELDS}, kernel_ms=float(st.kernel_ms))
-        m.emitted = False
+            m, stats = self._derived(h), _stats_dict(st, SNAP_FIELDS)
         m.snap_stats, m.snap_result, m.snap_evals = stats, (q, status, residual), evals
         return m
 
@@ -721,9 +737,7 @@ class Mesh:
         self._labelled()
         h = _vp()
         _check(eng.lib, eng.lib.sdf_mesh_select_shells(self.handle, _dp(mask, _u8p), len(mask), ctypes.byref(h)))
-        m = Mesh(eng, h)
-        m.emitted = False
-        return m
+        return self._derived(h)
 
     def simplify(self, origin, cell, reg=1e-3):
         """a new Mesh: this one simplified on the device (sdf_mesh_simplify, csrc/sdf_simplify.hip; defined by
@@ -741,10 +755,7 @@ class Mesh:
             raise ValueError('simplify: origin and cell have 3 components each, got %r and %r' % (origin, cell))
         h, st = _vp(), SdfSimplifyStats()
         _check(eng.lib, eng.lib.sdf_mesh_simplify(self.handle, _dp(o, _f64p), _dp(c, _f64p), float(reg), ctypes.byref(h), ctypes.byref(st)))
-        m = Mesh(eng, h)
-        m.emitted = False
-        m.simplify_stats = dict({k: int(getattr(st, k)) for k in SIMPLIFY_FIELDS}, kernel_ms=float(st.kernel_ms))
-        return m
+        return self._derived(h, simplify_stats=_stats_dict(st, SIMPLIFY_FIELDS))
 
     def simplify_adaptive(self, origin, cell, tolerance, levels=5, reg=1e-3):
         """a new Mesh: this one simplified to a tolerance on the device (sdf_mesh_simplify_adaptive, csrc/sdf_simplify.hip; DESIGN.md
@@ -772,11 +783,8 @@ class Mesh:
         h, st = _vp(), SdfAdaptiveStats()
         _check(eng.lib, eng.lib.sdf_mesh_simplify_adaptive(self.handle, _dp(o, _f64p), _dp(c, _f64p), float(reg), tol, lv, ctypes.byref(h),
                                                            ctypes.byref(st)))
-        m = Mesh(eng, h)
-        m.emitted = False
-        m.simplify_stats = dict({k: int(getattr(st, k)) for k in ADAPTIVE_FIELDS}, clusters_used=[int(n) for n in st.clusters_used[:lv + 1]],
-                                vertices=[int(n) for n in st.vertices[:lv + 1]], kernel_ms=float(st.kernel_ms), tolerance=tol)
-        return m
+        stats = _stats_dict(st, ADAPTIVE_FIELDS, clusters_used=[int(n) for n in st.clusters_used[:lv + 1]], vertices=[int(n) for n in st.vertices[:lv + 1]])
+        return self._derived(h, simplify_stats=dict(stats, tolerance=tol))
 
     def mend(self):
         """a new Mesh: this one mended on the device (sdf_mesh_mend, csrc/sdf_mend.hip; defined by
@@ -791,10 +799,7 @@ class Mesh:
             raise ValueError('mend: this mesh has been closed')
         h, st = _vp(), SdfMendStats()
         _check(eng.lib, eng.lib.sdf_mesh_mend(self.handle, ctypes.byref(h), ctypes.byref(st)))
-        m = Mesh(eng, h)
-        m.emitted = False
-        m.mend_stats = dict({k: int(getattr(st, k)) for k in MEND_FIELDS}, kernel_ms=float(st.kernel_ms))
-        return m
+        return self._derived(h, mend_stats=_stats_dict(st, MEND_FIELDS))
 
     def overhangs(self, directions, sin_limit, bed_tol, max_scratch_bytes=0):
         """build directions rated on the device (sdf_mesh_overhangs, csrc/sdf_overhang.hip; defined by
@@ -837,11 +842,11 @@ class Mesh:
         from .supports import check_params, support_rays_host
         eng = self.engine
         d, params = check_params(directions, sin_limit, bed_tol, start, min_step, step_scale, max_steps, refine)
-        dt, on_host = eng._probe_tape(sdf_or_tape, 'support_rays marches')
+        dt, ev = eng._probe_tape(sdf_or_tape, 'support_rays marches')
         k = len(d)
-        if on_host:
+        if ev:
             soup = self.points().reshape(-1, 3, 3)
-            got = [support_rays_host(lambda P: eng.eval_points(dt, P), soup, d[i], *params) for i in range(k)]
+            got = [support_rays_host(ev, soup, d[i], *params) for i in range(k)]
             return {'lo': np.array([g['lo'] for g in got]), 'hi': np.array([g['hi'] for g in got]),
                     'sums': np.array([g['sums'] for g in got]).reshape(k, 5), 'counts': np.array([g['counts'] for g in got], np.int64).reshape(k, 5),
                     'rays': [(g['triangle'], g['height'], g['status'], g['steps'], g['origin']) for g in got]}
@@ -1042,11 +1047,12 @@ class Engine:
 
     def _probe_tape(self, sdf, verb):
         """the seven field probes, behind the checks of their own parameters: refuse float32 precision (`verb`: what the probe does
-        in float64), then (the device tape, whether it reads user closures -- the probe's definition on the host serves those)"""
+        in float64), then (the device tape, its `evaluator` if it reads user closures -- the probe's definition on the host serves
+        those -- and None if not: the C call)"""
         if self.precision != PRECISION_F64:
             raise ValueError('%s in float64 only; this engine is set to float32 precision' % verb)
         dt = self.tape_for(sdf)
-        return dt, bool(dt.tape.externs)
+        return dt, evaluator(self, dt) if dt.tape.externs else None
 
     # -- f(P) --
     def eval_points(self, sdf, pts):
@@ -1191,8 +1197,8 @@ class Engine:
         (height, width) int32 and `status` (height, width) uint8 (1 hit, 0 miss).  frame: 18 doubles o0, ou, ov, c, du, dv
         (sdf_amd/render.py `camera` makes one).  Raises ValueError, before any device work, for what the entry point refuses
         (include/sdf_hip.h), for a model with user closures and for a context in float32 precision."""
-        dt, on_host = self._probe_tape(sdf, 'render_buffers traces')
-        if on_host:
+        dt, ev = self._probe_tape(sdf, 'render_buffers traces')
+        if ev:
             raise ValueError('render_buffers cannot trace a model with user closures: every step of every ray would need a host round trip')
         frame = np.ascontiguousarray(frame, dtype=np.float64).reshape(-1)
         if frame.size != 18:

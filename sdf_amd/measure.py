@@ -62,17 +62,8 @@ def measure(sdf, origin=None, keep=None, simplify=None, mend=False, simplify_tol
     mend: True -- measure the mesh mended after keep and simplify (`sdf_amd/mend.py`).  snap: True or a dict -- measure the mesh whose
     vertices were put back on the zero set after simplify (`sdf_amd/deviation.py`).  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
     from . import core
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    if snap is not False:
-        generate_kwargs['snap'] = snap
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
-        if m.mesh is None:
-            raise NotImplementedError('measure: the soup of this multi-process run was gathered on the host; the measurements are made '
-                                      'on the device only (run it in one process, or with a device-resident exchange)')
+    with core.meshed(sdf, keep=keep, **core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
+        core.need_device_mesh(m.mesh, 'measure', 'the measurements are made')
         return measure_mesh(m.mesh, origin)
 
 

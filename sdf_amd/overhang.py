@@ -166,16 +166,9 @@ def overhangs(sdf, directions=UP, angle=45.0, bed_tolerance=None, classes=False,
     `measure`.  A multi-process run whose gathered soup is on the host raises NotImplementedError."""
     from . import core
     d, sin_limit, angle, tol = check_params(directions, angle, bed_tolerance, classes)       # (before anything is meshed)
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
-        if m.mesh is None:
-            raise NotImplementedError('overhangs: the soup of this multi-process run was gathered on the host; build directions are '
-                                      'rated on the device only (run it in one process, or with a device-resident exchange)')
+    kw = core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend)
+    with core.meshed(sdf, keep=keep, **kw) as m:
+        core.need_device_mesh(m.mesh, 'overhangs', 'build directions are rated')
         if tol is None:
-            steps3 = core.grid_axes(m.bounds, generate_kwargs.get('step'), generate_kwargs.get('samples', core.SAMPLES))[3]
-            tol = float(max(steps3))
+            tol = float(max(core.grid_steps(m, kw)))
         return _rated(m.mesh, d, sin_limit, angle, tol, classes)

@@ -41,7 +41,7 @@ def _meshed(sdf, generate_kwargs, simplify=None, mend=False, simplify_tolerance=
         raise NotImplementedError('shells: a multi-process run gathers its soup per step; label it in one process, or adopt the '
                                   'gathered soup (Engine.adopt_soup) and use shells_of_mesh')
     return core.meshed(sdf, keep=None, simplify=simplify, mend=mend, to_host=False,
-                       **dict(generate_kwargs, verbose=False, **core._tolerance_kwargs(simplify_tolerance, simplify_levels)))
+                       **core.pipeline_kwargs(dict(generate_kwargs, verbose=False), simplify_tolerance=simplify_tolerance, simplify_levels=simplify_levels))
 
 
 def shells(sdf, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5, **generate_kwargs):

@@ -305,15 +305,11 @@ def supports(sdf, directions=UP, angle=45.0, bed_tolerance=None, start=None, min
     of the smallest grid step.  step_scale in (0, 1]: shorten the steps for a field that overestimates distances.  keep, simplify,
     simplify_tolerance, simplify_levels, mend: as for `measure`.  A model with user closures, and a multi-process run whose gathered soup is on the host, take the same
     definition on the host over `Engine.eval_points`."""
-    from . import core
+    from . import core, engine
     d, sin_limit, angle, tol, top = check_call(directions, angle, bed_tolerance, start, min_step, step_scale, max_steps, refine, top)
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
-        steps3 = core.grid_axes(m.bounds, generate_kwargs.get('step'), generate_kwargs.get('samples', core.SAMPLES))[3]
+    kw = core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend)
+    with core.meshed(sdf, keep=keep, **kw) as m:
+        steps3 = core.grid_steps(m, kw)
         if tol is None:
             tol = float(max(steps3))
         quarter = float(min(steps3)) / 4
@@ -325,8 +321,8 @@ def supports(sdf, directions=UP, angle=45.0, bed_tolerance=None, start=None, min
             raise NotImplementedError('supports: the soup of this multi-process run was gathered on the host; directions are rated on '
                                       'the device only -- give the directions to trace')
         params = dict(start=start, min_step=min_step, step_scale=float(step_scale), max_steps=int(max_steps), refine=int(refine))
-        soup = m.points.reshape(-1, 3, 3)
-        got = [support_rays_host(lambda P: m.engine.eval_points(m.tape, P), soup, d[i], sin_limit, tol, **params) for i in range(len(d))]
+        soup, ev = m.points.reshape(-1, 3, 3), engine.evaluator(m.engine, m.tape)
+        got = [support_rays_host(ev, soup, d[i], sin_limit, tol, **params) for i in range(len(d))]
         raw = {'lo': [g['lo'] for g in got], 'hi': [g['hi'] for g in got], 'sums': np.array([g['sums'] for g in got]).reshape(-1, N_SUMS),
                'counts': np.array([g['counts'] for g in got]).reshape(-1, 5),
                'rays': [(g['triangle'], g['height'], g['status'], g['steps'], g['origin']) for g in got]}

@@ -155,13 +155,14 @@ class Thickness:
 
 def default_params(bounds, steps3, start=None, min_step=None, t_far=None, normal_eps=None):
     """the defaults of `thickness`: start = min_step = a quarter of the smallest grid step, t_far = the diagonal of the bounds,
-    normal_eps = the preview's value (1e-4 x the half-diagonal, as `core.read_export` computes it)"""
+    normal_eps = the preview's value (`core.default_normal_eps`)"""
+    from . import core
     lo, hi = np.asarray(bounds[0], dtype=np.float64), np.asarray(bounds[1], dtype=np.float64)
     diagonal = float(np.sqrt(np.dot(hi - lo, hi - lo)))
     quarter = float(min(steps3)) / 4 if steps3 is not None else None
     if quarter is None and (start is None or min_step is None):
         raise ValueError('thickness: give step, or start and min_step')
-    return {'normal_eps': 1e-4 * float(diagonal / 2) if normal_eps is None else float(normal_eps),
+    return {'normal_eps': core.default_normal_eps(bounds) if normal_eps is None else float(normal_eps),
             'start': quarter if start is None else float(start), 'min_step': quarter if min_step is None else float(min_step),
             't_far': diagonal if t_far is None else float(t_far)}
 
@@ -169,10 +170,10 @@ def default_params(bounds, steps3, start=None, min_step=None, t_far=None, normal
 def read_thickness(m, params, with_mesh=True):
     """the probe on a `core.Meshed`: on the device, or -- a soup gathered on the host -- by the definition over eval_points.
     Returns (points, cells, thickness, status, steps); points and cells are None unless with_mesh."""
-    from . import core
+    from . import core, engine
     if m.mesh is None:
         pts, cells = core.read_weld(m)
-        return (pts, cells) + vertex_thickness(lambda P: m.engine.eval_points(m.tape, P), pts, **params)
+        return (pts, cells) + vertex_thickness(engine.evaluator(m.engine, m.tape), pts, **params)
     got = m.mesh.vertex_thickness(m.tape, **params)
     pts, cells = m.mesh.weld() if with_mesh else (None, None)
     return (pts, cells) + got
@@ -190,18 +191,11 @@ def thickness(sdf, start=None, min_step=None, t_far=None, max_steps=256, refine=
     a dict -- the vertices of the final mesh are put back on the zero set first (`sdf_amd/deviation.py`), so a
     simplified mesh can be probed with the default `start`."""
     from . import core
-    if simplify is not None:
-        generate_kwargs['simplify'] = simplify
-    generate_kwargs.update(core._tolerance_kwargs(simplify_tolerance, simplify_levels))
-    if mend is not False:
-        generate_kwargs['mend'] = mend
-    if snap is not False:
-        generate_kwargs['snap'] = snap
+    kw = core.pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)
     check_params(1.0 if normal_eps is None else normal_eps, 1.0 if start is None else start, 1.0 if min_step is None else min_step,
                  np.finfo(np.float64).max if t_far is None else t_far, step_scale, max_steps, refine)      # (what can be refused before meshing)
-    with core.meshed(sdf, keep=keep, **generate_kwargs) as m:
-        steps3 = core.grid_axes(m.bounds, generate_kwargs.get('step'), generate_kwargs.get('samples', core.SAMPLES))[3]
-        params = dict(default_params(m.bounds, steps3, start, min_step, t_far, normal_eps), step_scale=float(step_scale),
+    with core.meshed(sdf, keep=keep, **kw) as m:
+        params = dict(default_params(m.bounds, core.grid_steps(m, kw), start, min_step, t_far, normal_eps), step_scale=float(step_scale),
                       max_steps=int(max_steps), refine=int(refine))
         pts, cells, th, status, steps = read_thickness(m, params)
         return Thickness(pts, cells, th, status, steps, params)
