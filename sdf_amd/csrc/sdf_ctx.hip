@@ -139,7 +139,7 @@ static int ctx_init(sdf_ctx *c) {
     if (const char *e = getenv("SDF_DEFER")) c->defer = atoi(e) ? 1 : 0;
     if (const char *e = getenv("SDF_CULL_LEVELS")) c->cull_levels = atoi(e);
     if (const char *e = getenv("SDF_PARK_SPINS")) c->park_spins = std::max(atoi(e), 1);
-    if (const char *e = getenv("SDF_MESH_PROF")) { if (atoi(e) && c->prof.ensure(512 + 4096 * 32)) return 1; }
+    if (const char *e = getenv("SDF_MESH_PROF")) { if (atoi(e) && c->prof.ensure(512 + 4096 * 32)) return 1; c->prof_mesh = atoi(e) != 2; }
     return 0;
 }
 

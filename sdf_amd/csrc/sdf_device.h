@@ -179,7 +179,12 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int *wave_sums, int &
 // passed the barrier of scan i + 1, which every thread reaches only after its reads of scan i)
 template <int BLOCK>
 __device__ __forceinline__ int block_exclusive_scan1(int v, int *wave_sums, int &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    // (the thread index is opaque here and the wave's number a scalar: what the optimiser derives from a plain `threadIdx.x` it derives
+    // ONCE, at the kernel's start -- of the sixteen lane predicates `w < wid` that this function used to test it made 30 scalar registers,
+    // which k_mesh spilled and read back, two lane reads per predicate, in every scan of every round)
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6);
     int inc = v;
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, false);
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, false);
@@ -189,11 +194,17 @@ __device__ __forceinline__ int block_exclusive_scan1(int v, int *wave_sums, int 
     inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);
     if (lane == 63) wave_sums[wid] = inc;
     __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; w++) { const int s = wave_sums[w]; if (w < wid) base += s; tot += s; }
-    total = tot;
-    return base + inc - v;
+    // the wave totals, one per lane of every row of 16 lanes: their sum, and the sum of those below this wave, by four row shifts each --
+    // a dozen instructions where reading all sixteen and adding them up under sixteen predicates took eighty
+    static_assert(BLOCK / 64 <= 16, "a row of 16 lanes holds the wave totals");
+    const int l16 = lane & 15;
+    int tot = l16 < BLOCK / 64 ? wave_sums[l16] : 0, base = l16 < wid ? tot : 0;
+    tot += __builtin_amdgcn_update_dpp(0, tot, 0x111, 0xf, 0xf, false);   base += __builtin_amdgcn_update_dpp(0, base, 0x111, 0xf, 0xf, false);
+    tot += __builtin_amdgcn_update_dpp(0, tot, 0x112, 0xf, 0xf, false);   base += __builtin_amdgcn_update_dpp(0, base, 0x112, 0xf, 0xf, false);
+    tot += __builtin_amdgcn_update_dpp(0, tot, 0x114, 0xf, 0xf, false);   base += __builtin_amdgcn_update_dpp(0, base, 0x114, 0xf, 0xf, false);
+    tot += __builtin_amdgcn_update_dpp(0, tot, 0x118, 0xf, 0xf, false);   base += __builtin_amdgcn_update_dpp(0, base, 0x118, 0xf, 0xf, false);
+    total = __builtin_amdgcn_readlane(tot, 15);                           // (lane 15: the last of the first row)
+    return __builtin_amdgcn_readlane(base, 15) + inc - v;
 }
 
 // the same for a predicate: a ballot and a masked bit count instead of six shuffles
@@ -379,15 +390,18 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
                              c = wave_sum_u32_dpp((unsigned)((v >> 42) & 0xFFFFFull));
     return a + (b << 21) + (c << 42);
 }
+// this thread's lane, worked out where it is asked for: what the optimiser derives from a plain `threadIdx.x & 63` -- the lane, the
+// predicate `lane == 0` -- it derives ONCE, at the kernel's start, and k_mesh then carries it through the interpreter of every round
+__device__ __forceinline__ int lane_now() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t & 63; }
 __device__ __forceinline__ void publish_count(unsigned long long *status, int w, int w_begin, unsigned long long total) {
-    if ((threadIdx.x & 63) == 0)
+    if (lane_now() == 0)
         __hip_atomic_store(&status[w], (w == w_begin ? MESH_FLAG_PFX : MESH_FLAG_AGG) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // this lane's word of the first look-back window of work item w (the 64 items in front of it).  The
 // caller issues it EARLY -- before the cell counting, whose work then hides the round trip to the
 // device-coherent level -- and hands it to ordered_base afterwards.
 __device__ __forceinline__ unsigned long long lookback_prefetch(const unsigned long long *status, int w, int w_begin) {
-    const int j = w - 1 - (int)(threadIdx.x & 63);
+    const int j = w - 1 - lane_now();
     return j >= w_begin ? __hip_atomic_load(&status[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : MESH_FLAG_PFX;
 }
 // the exclusive prefix of work item w; ~0 on timeout; with max_spins small: MESH_NOT_READY when a
@@ -399,7 +413,7 @@ __device__ __forceinline__ unsigned long long lookback_prefetch(const unsigned l
 // (6 k cycles per batch).  The lanes add up what they see; ONE wave reduction at the end.
 __device__ __forceinline__ unsigned long long ordered_base(unsigned long long *status, int w, int w_begin, unsigned long long total,
                                                            unsigned max_spins, unsigned long long first) {
-    const int lane = threadIdx.x & 63;
+    const int lane = lane_now();
     if (w == w_begin) return 0;
     unsigned long long acc = 0;   // this lane's share of the exclusive prefix
     int idx = w - 1;
@@ -707,8 +721,10 @@ __device__ __forceinline__ int cull_tasks(const uint32_t *wcode, const double *c
 //   the LAST wave of the workgroup uses the time to take the next work item and bring its record and axes in (k_mesh).
 enum { MESH_SLOT_HDR = 1232, MESH_SLOT_COLINFO = 64, MESH_STAGE_BYTES = 32 * 9 * 4 };   // (a wave transposes its 64 triangles in two halves)
 
-template <typename T, bool FULL, int NP, int ND, int NS, int BLOCK, bool TWOPASS = false>
-__global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ code, const T *__restrict__ consts, MeshArgs a_byval) {
+// The body of the kernel, inlined into its two entries below: k_mesh, what a normal call launches, and k_mesh_prof (PROF), the same
+// with the per-phase cycle counters and the workgroups' timelines of SDF_MESH_PROF=1.
+template <typename T, bool FULL, int NP, int ND, int NS, int BLOCK, bool TWOPASS, bool PROF>
+__device__ __forceinline__ void mesh_rounds(const uint32_t *__restrict__ code, const T *__restrict__ consts) {
     // (the argument block is read from the kernel-argument segment where it is used -- a scalar load from constant memory, two
     // words of pointer to keep -- instead of living in ~ 80 scalar registers that the round structure then spills)
     typedef __attribute__((address_space(4))) const MeshArgs KArgs;
@@ -716,7 +732,6 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     // 16 bytes, would move it)
     static_assert(sizeof(const uint32_t *) + sizeof(const T *) == 16 && alignof(MeshArgs) <= 16, "MeshArgs sits at byte 16 of the kernel arguments");
     KArgs *ap = (KArgs *)((__attribute__((address_space(4))) const char *)__builtin_amdgcn_kernarg_segment_ptr() + 16);
-    (void)a_byval;
 #define KA (*ap)
 #define SDF_SINK (Tri16Sink{KA.out, KA.raw, KA.raw_cap, &KA.ctr->n_raw})
     typedef Vec<T, NS> V;
@@ -732,10 +747,19 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     // behind the sign bits: k_cull's record of the batch while it is sampled; the cell table and triangle list of a DENSE tile
     unsigned *wlist = reinterpret_cast<unsigned *>(smem + KA.list_off);
     // `tid` is made opaque to the optimiser at every phase boundary (SDF_FRESH): whatever a phase derives
-    // from it is worked out again there instead of being kept -- i.e. spilled -- across the interpreter
+    // from it is worked out again there instead of being kept -- i.e. spilled -- across the interpreter.  The same for the argument
+    // block: behind a boundary a field of KA is a new scalar load from the kernel-argument segment, not a register carried from the
+    // phase before, and the two LDS pointers made of such fields are made again.
     int tid = threadIdx.x;
-#define SDF_FRESH() asm volatile("" : "+v"(tid))
-    const GridDesc g = a_byval.g;
+#define SDF_FRESH() do { asm volatile("" : "+v"(tid), "+s"(ap)); \
+                         bits = reinterpret_cast<unsigned long long *>(smem + KA.bits_off); wlist = reinterpret_cast<unsigned *>(smem + KA.list_off); } while (0)
+    // The per-phase cycle counters and the workgroups' timelines (SDF_MESH_PROF=1) are compiled into k_mesh_prof only, which the
+    // launcher takes when the context has a `prof` buffer: in the kernels of a normal call neither the tests of KA.prof nor the two
+    // 64-bit clocks `tprev` / `tsub` exist.  (The first-start / last-end words of MeshCounters are product and stay in both.)
+#define SDF_PROF_ON (PROF && KA.prof)
+    // (the grid descriptor too: fetched where a round needs it -- the top of a round, the last wave's early fetch -- not kept through it)
+    auto grid = [&]() { GridDesc g_; g_.X = KA.g.X; g_.Y = KA.g.Y; g_.Z = KA.g.Z; g_.nx = KA.g.nx; g_.ny = KA.g.ny; g_.nz = KA.g.nz; g_.bs = KA.g.bs;
+                        g_.nbx = KA.g.nbx; g_.nby = KA.g.nby; g_.nbz = KA.g.nbz; return g_; };
     // the triangle table in LDS: edge ids e0 | e1 << 4 | e2 << 8 of triangle j of configuration cfg at [5 cfg + j] (a
     // non-ambiguous configuration has at most 5).  The emission used to fetch them as three byte loads from the 4 KB table in
     // device memory per triangle: 4.6 % of the kernel by knock-out (r04aj)
@@ -751,14 +775,14 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
 
     for (int i = tid; i < (int)((KA.list_off - KA.bits_off) >> 3); i += BLOCK) bits[i] = 0ull;   // (every round leaves them cleared for the next)
     const int work_begin = KA.ctr->work_begin, work_end = KA.ctr->work_end;
-    if (KA.prof && tid == 0) KA.prof[64 + 4 * blockIdx.x] = wall_clock64();        // (timeline of the workgroup, 100 MHz)
+    if (SDF_PROF_ON && tid == 0) KA.prof[64 + 4 * blockIdx.x] = wall_clock64();    // (timeline of the workgroup, 100 MHz)
     if (tid == 0) {   // the kernel's start on the device's own clock (sdf_stats.ms_mesh_device, sclk_mhz)
         const unsigned long long tw = wall_clock64();
         atomicMax(&KA.ctr->t_first_inv, ~tw);
         if (blockIdx.x == 0) { KA.ctr->clk_cycles = (unsigned long long)clock64(); KA.ctr->clk_ticks = tw; }
     }
-    long long tprev = KA.prof ? clock64() : 0;
-#define SDF_PROF(K) do { if (KA.prof && tid == 0) { const long long tn = clock64(); atomicAdd(&KA.prof[K], (unsigned long long)(tn - tprev)); tprev = tn; } } while (0)
+    long long tprev = SDF_PROF_ON ? clock64() : 0;
+#define SDF_PROF(K) do { if (SDF_PROF_ON && tid == 0) { const long long tn = clock64(); atomicAdd(&KA.prof[K], (unsigned long long)(tn - tprev)); tprev = tn; } } while (0)
     // position-dependent bookkeeping of work item w_ (thread 0)
     auto settle = [&](int w_, unsigned long long excl, unsigned long long total_) {
         if (excl == ~0ull) atomicOr(&KA.ctr->overflow, 2u);           // look-back timed out (never expected)
@@ -770,7 +794,8 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     // ONE slot a workgroup that met a slow predecessor twice in a row stood still -- 12 % of the kernel's
     // cycles were spent in the look-back of the parked batch.  A batch is placed as soon as its predecessors
     // have published (checked once per batch of this workgroup, oldest first); only a full FIFO waits.
-    float *my_park = KA.park ? KA.park + (size_t)blockIdx.x * (size_t)MESH_PARK_DEPTH * (size_t)KA.park_cap * 9 : nullptr;
+    // (worked out where a batch is parked or placed -- two scalar loads and a multiplication -- not carried through the rounds)
+    auto my_park = [&]() -> float * { return KA.park ? KA.park + (size_t)blockIdx.x * (size_t)MESH_PARK_DEPTH * (size_t)KA.park_cap * 9 : nullptr; };
     int pq_head = 0, pq_count = 0;
     unsigned char *pend_base = smem + MESH_LDS_PEND;   // entry k: double xf[6] (offset[3], scale[3]), int w, int total
     auto pend_xf = [&](int k) { return reinterpret_cast<double *>(pend_base + 64 * k); };
@@ -796,7 +821,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
             if (pbase == MESH_NOT_READY) { __syncthreads(); break; }   // (bcast is reused)
             if (pbase != ~0ull && pbase + (unsigned long long)pend_total <= KA.out_cap) {
                 double *dst0 = KA.out + pbase * 9ull;
-                const float *src = my_park + (size_t)pq_head * (size_t)KA.park_cap * 9;
+                const float *src = my_park() + (size_t)pq_head * (size_t)KA.park_cap * 9;
                 const double *xf = pend_xf(pq_head);
                 const double pof0 = xf[0], pof1 = xf[1], pof2 = xf[2], psc0 = xf[3], psc1 = xf[4], psc2 = xf[5];
                 // consecutive lanes move consecutive coordinates (4-byte loads, 8-byte stores: whole cache lines per
@@ -846,8 +871,8 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     // phase -- was built and measured in r02: the time at the top of the loop did not move (it is the record / axis loads,
     // not the atomic), and the two values carried across the phases cost 6 - 9 more spilled registers: 0.288 -> 0.300 ms.
     // What does pay is below: a whole WAVE brings the item, its record and its axes into LDS during the emission.)
-    const int slot_bytes = TWOPASS ? 0 : KA.slot_bytes;
-    auto slot_base = [&](int s_) { return smem + MESH_LDS_VOL + (size_t)s_ * (size_t)slot_bytes; };
+#define SDF_SLOT_BYTES (TWOPASS ? 0 : KA.slot_bytes)   // (read where it is used, like every field of KA)
+    auto slot_base = [&](int s_) { return smem + MESH_LDS_VOL + (size_t)s_ * (size_t)SDF_SLOT_BYTES; };
     int dq_slot = -1;          // the slot of the counted batch whose triangles are still to be written (-1: none)
     bool carry = false;        // the work item in `w` was taken in the previous round (which only wrote the waiting batch)
     int w = 0;
@@ -862,7 +887,6 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     bool have = false;         // ... and its batch index / header are in bcast[9..10], record and axes in LDS
     for (;;) {
         SDF_FRESH();
-        asm volatile("" : "+s"(ap));
         dq_slot = uni(dq_slot); pq_head = uni(pq_head); pq_count = uni(pq_count);   // (uniform by construction)
         if (!carry) {
             if (nx_valid) {   // (uniform) drawn during the last round's emission; visible since that round's last barrier
@@ -909,7 +933,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
         SDF_PROF(43);
         carry = false;
         const bool finished = w >= work_end;
-        if (finished && KA.prof && tid == 0 && KA.prof[64 + 4 * blockIdx.x + 1] == 0) KA.prof[64 + 4 * blockIdx.x + 1] = wall_clock64();
+        if (finished && SDF_PROF_ON && tid == 0 && KA.prof[64 + 4 * blockIdx.x + 1] == 0) KA.prof[64 + 4 * blockIdx.x + 1] = wall_clock64();
         if (finished && dq_slot < 0) break;
         // ---- what kind of tile?  (the header word of k_cull's record: a uniform load) ----
         bool flush_only = finished;   // this round only writes the waiting batch
@@ -926,7 +950,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
             b = uni(b_v);
             const unsigned n0 = (unsigned)uni((int)n0_v) & 0xFFFFu;
             if (n0 != 0xFFFFu) ntl_cull = (int)((n0 + 7u) >> 3);
-            sparse = ntl_cull >= 0 && slot_bytes > 0 && MESH_SLOT_HDR + 256 * ntl_cull + 4 * MESH_CELL_CHUNKS * BLOCK <= slot_bytes;
+            sparse = ntl_cull >= 0 && SDF_SLOT_BYTES > 0 && MESH_SLOT_HDR + 256 * ntl_cull + 4 * MESH_CELL_CHUNKS * BLOCK <= SDF_SLOT_BYTES;
             if (!sparse && dq_slot >= 0) { flush_only = true; carry = true; }   // a dense tile takes the slots' region
         }
         const bool culled = ntl_cull >= 0;
@@ -936,7 +960,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
         unsigned char *cs = slot_base(sparse ? cur_slot : 0);
         float *smp = reinterpret_cast<float *>(cs + MESH_SLOT_HDR);
         unsigned *clist = sparse ? reinterpret_cast<unsigned *>(cs + MESH_SLOT_HDR + 256 * ntl_cull) : wlist;
-        const int lcap = sparse ? min((slot_bytes - MESH_SLOT_HDR - 256 * ntl_cull) >> 2, 16384) : KA.list_cap;
+        const int lcap = sparse ? min((SDF_SLOT_BYTES - MESH_SLOT_HDR - 256 * ntl_cull) >> 2, 16384) : KA.list_cap;
         int lx = 2, ly = 2, lz = 2, lyz = 4;
         int row_tris[RPT], row_off[RPT], row_cell0[RPT];
         unsigned row_mask[RPT];
@@ -951,6 +975,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
         // k_cull's record of the batch (cull_tasks) travels next to the axes: units and sub-group states into the work area
         // (idle until the cells of a dense tile are listed), the column words into the batch's slot
         int ox, oy, oz;
+        const GridDesc g = grid();
         batch_origin(g, b, ox, oy, oz, lx, ly, lz);
         if (have) {   // (uniform) record and axes came in during the last round's emission; the column words wait in the work area
             if (sparse) for (int i = tid; i < 289; i += BLOCK) reinterpret_cast<unsigned *>(cs + MESH_SLOT_COLINFO)[i] = wlist[CULL_COLINFO / 4 + i];
@@ -983,8 +1008,8 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
         constexpr int NWAVE = BLOCK / 64;
         // ---- 1a. sub-groups of 2^3 cells whose interval excludes the surface are not sampled: k_cull left the
         // list of units to evaluate and the sign of the decided sub-groups (cull_tasks) ----
-        long long tsub = KA.prof ? clock64() : 0;
-#define SDF_SUBPROF(K) do { if (KA.prof && tid == 0) { const long long tn = clock64(); atomicAdd(&KA.prof[K], (unsigned long long)(tn - tsub)); tsub = tn; } } while (0)
+        long long tsub = SDF_PROF_ON ? clock64() : 0;
+#define SDF_SUBPROF(K) do { if (SDF_PROF_ON && tid == 0) { const long long tn = clock64(); atomicAdd(&KA.prof[K], (unsigned long long)(tn - tsub)); tsub = tn; } } while (0)
         const unsigned short *units = reinterpret_cast<const unsigned short *>(reinterpret_cast<const unsigned char *>(wlist) + CULL_ULIST);
         const unsigned *sstate = wlist + CULL_SSTATE / 4;   // 16 x 16 words of 16 two-bit states
         int ntl = tt.ntask;
@@ -1330,10 +1355,10 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
         const bool sparse_next = !flush_only && !emit_cur;   // this batch becomes the waiting one
         // ---- parked batches are older than anything here: their predecessors have long published, place them (and make room
         // for what this round may park: the waiting batch, this batch) ----
-        { const long long tp0 = KA.prof ? clock64() : 0;
+        { const long long tp0 = SDF_PROF_ON ? clock64() : 0;
         if (flush_only && pq_count > 0 && tid < 64) pre_pend = lookback_prefetch(KA.status, pend_wt(pq_head)[0], work_begin);
         place_parked(pre_pend, false, (emit_cur ? 1 : 0) + (dq_slot >= 0 ? 1 : 0));
-        if (KA.prof && tid == 0) atomicAdd(&KA.prof[6], (unsigned long long)(clock64() - tp0)); }
+        if (SDF_PROF_ON && tid == 0) atomicAdd(&KA.prof[6], (unsigned long long)(clock64() - tp0)); }
         SDF_PROF(47);
         // (two copies of this code, one per kind of batch, rather than one loop over both: the rows' sign strings and offsets
         // that only a list built in passes needs would otherwise stay in registers through the waiting batch's emission)
@@ -1396,6 +1421,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
                     }
 #endif
                     int nox, noy, noz, nlx, nly, nlz;
+                    const GridDesc g = grid();
                     batch_origin(g, nb_, nox, noy, noz, nlx, nly, nlz);
                     if (ln < nlx) axes[ln] = g.X[nox + ln];                       // (the waiting batch's transform sits in its slot)
                     if (ln < nly) axes[33 + ln] = g.Y[noy + ln];
@@ -1422,9 +1448,9 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
                     pend_wt(park_slot)[0] = e_w; pend_wt(park_slot)[1] = e_total;
                 }
                 pq_count++;
-                if (KA.prof && tid == 0) atomicAdd(&KA.prof[7], 1ull);
+                if (SDF_PROF_ON && tid == 0) atomicAdd(&KA.prof[7], 1ull);
             }
-            if (KA.prof && tid == 0 && is_dq) atomicAdd(&KA.prof[12], 1ull);
+            if (SDF_PROF_ON && tid == 0 && is_dq) atomicAdd(&KA.prof[12], 1ull);
             for (int lo = 0; fits && lo < e_total; lo += e_lcap) {
                 const int ecn = min(e_lcap, e_total - lo);
                 SDF_UNROLL
@@ -1458,7 +1484,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
                                                // and the last wave, busy with the next work item, must not be waited for here)
                 SDF_PROF(3);
                 double *dst0 = KA.out + (parking ? 0ull : base + (unsigned long long)lo) * 9ull;
-                float *park0 = my_park + ((size_t)park_slot * (size_t)KA.park_cap + (size_t)lo) * 9;
+                float *park0 = my_park() + ((size_t)park_slot * (size_t)KA.park_cap + (size_t)lo) * 9;
                 const bool staged = is_dq && KA.stage_off > 0 && !parking;   // (uniform)
                 // (whole waves: the transposition below is wave-wide.  The waiting batch's triangles go to the waves in chunks of 64
                 // as they come for them -- the last wave joins late, it has taken the next work item first)
@@ -1543,7 +1569,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     SDF_FRESH();
     place_parked(pq_count > 0 && tid < 64 ? lookback_prefetch(KA.status, pend_wt(pq_head)[0], work_begin) : 0ull, true, 0);
     SDF_PROF(5);
-    if (KA.prof && tid == 0) KA.prof[64 + 4 * blockIdx.x + 2] = wall_clock64();
+    if (SDF_PROF_ON && tid == 0) KA.prof[64 + 4 * blockIdx.x + 2] = wall_clock64();
     if (tid == 0) {
         const unsigned long long tw = wall_clock64();
         atomicMax(&KA.ctr->t_last, tw);
@@ -1551,9 +1577,23 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     }
 #undef SDF_FRESH
 #undef SDF_PROF
+#undef SDF_PROF_ON
+#undef SDF_SLOT_BYTES
 }
 #undef KA
 #undef SDF_SINK
+
+// (the argument block is passed by value and read through the kernel-argument segment: see the head of mesh_rounds)
+template <typename T, bool FULL, int NP, int ND, int NS, int BLOCK, bool TWOPASS = false>
+__global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ code, const T *__restrict__ consts, MeshArgs a_byval) {
+    (void)a_byval;
+    mesh_rounds<T, FULL, NP, ND, NS, BLOCK, TWOPASS, false>(code, consts);
+}
+template <typename T, bool FULL, int NP, int ND, int NS, int BLOCK, bool TWOPASS = false>
+__global__ __launch_bounds__(BLOCK) void k_mesh_prof(const uint32_t *__restrict__ code, const T *__restrict__ consts, MeshArgs a_byval) {
+    (void)a_byval;
+    mesh_rounds<T, FULL, NP, ND, NS, BLOCK, TWOPASS, true>(code, consts);
+}
 
 // host-side launcher of one (T, FULL) family, defined in sdf_mesh_inst.hip (one translation
 // unit per family so the variants compile in parallel).  slots: 0 = (1,1), 1 = (2,2), 2 = (4,2), 3 = (2,4), 4 = (4,4), 5 = (8,8)
@@ -1562,5 +1602,7 @@ __global__ __launch_bounds__(BLOCK) void k_mesh(const uint32_t *__restrict__ cod
     int NAME(int slots, int shape, int twopass, int grid, size_t lds, hipStream_t stream, const uint32_t *code, const T *consts, const MeshArgs &a)
 SDF_DECLARE_MESH_LAUNCH(sdf_launch_mesh_f64, double);
 SDF_DECLARE_MESH_LAUNCH(sdf_launch_mesh_f64_full, double);
+SDF_DECLARE_MESH_LAUNCH(sdf_launch_mesh_f64_prof, double);        // (the same with the cycle counters of SDF_MESH_PROF=1: -DMESH_PROF=1)
+SDF_DECLARE_MESH_LAUNCH(sdf_launch_mesh_f64_full_prof, double);
 
 }  // namespace sdfk

@@ -106,8 +106,11 @@ static int launch_mesh(sdf_tape *t, const void *code, int precision, MeshArgs &a
         slots = c->mesh_slots;                                                        // (tuning: another file that fits)
     // (one shape per register file and scheme: 1024 threads x 3 or 2 samples per lane, the 8-slot file 1024 x 1 -- sdf_mesh_inst.hip)
     if (precision != SDF_PRECISION_F64) return fail("k_mesh: float64 only");
-    const int rc = t->full ? sdf_launch_mesh_f64_full(slots, 0, a.twopass, grid, lds, st, (const uint32_t *)code, t->d_c64, a)
-                           : sdf_launch_mesh_f64(slots, 0, a.twopass, grid, lds, st, (const uint32_t *)code, t->d_c64, a);
+    // (a context with a `prof` buffer, SDF_MESH_PROF=1, takes the instrumented instantiations of the same source: the kernels of a normal
+    // call hold neither the cycle counters nor the tests for the buffer)
+    auto launch = a.prof && c->prof_mesh ? (t->full ? sdf_launch_mesh_f64_full_prof : sdf_launch_mesh_f64_prof)
+                                         : (t->full ? sdf_launch_mesh_f64_full : sdf_launch_mesh_f64);
+    const int rc = launch(slots, 0, a.twopass, grid, lds, st, (const uint32_t *)code, t->d_c64, a);
     if (rc) return fail(std::string("k_mesh launch: ") + hipGetErrorString((hipError_t)rc));
     return 0;
 }

@@ -44,6 +44,8 @@ struct sdf_ctx {
     DevBuf ext;                       // closure points / values of sdf_eval_*extern* (L_EXTERN leaves)
     DevBuf field_vals, field_vol, field_tiles;   // sdf_chunked.hip: a chunk's sampled values (f64, sdf_generate_field), volumes (f32), tile table
     DevBuf prof;                      // SDF_MESH_PROF=1: per-phase cycle counters of k_mesh (diagnostics)
+    int prof_mesh = 1;                // ... counted by the INSTRUMENTED instantiations of k_mesh (sdf_mesh_inst.hip, -DMESH_PROF=1), which a context with the
+                                      // buffer launches.  SDF_MESH_PROF=2: the buffer and the report, but the plain kernels (their words must stay zero: a test)
     int prune = 1;                    // SDF_PRUNE=0 switches the interval prepass off (diagnostics)
     int parking = 1;                  // SDF_PARK=0: k_mesh waits for its predecessors instead of parking a batch (diagnostics)
     int cull = 1;                     // SDF_CULL=0: k_mesh samples every voxel of a batch instead of deciding cell groups by intervals

@@ -1,13 +1,23 @@
 // sdf_mesh_inst.hip -- instantiations of the fused sample+march kernel for ONE family.
 // Built twice (see build.units): -DMESH_T=double -DMESH_FULL=0|1 -DMESH_NAME=... (FULL: the tape uses the trigonometric ops),
 // so the families compile in parallel.  (float32 sampling of the meshing path was removed in round 5.)
+// -DMESH_PROF=1: the same variants WITH the per-phase cycle counters and the workgroups' timelines (k_mesh_prof), in units
+// of their own; the launchers of those are what launch_mesh takes when the context has a `prof` buffer (SDF_MESH_PROF=1).
 #include "sdf_device.h"
+
+#ifndef MESH_PROF
+#define MESH_PROF 0
+#endif
 
 namespace sdfk {
 
 template <int NP, int ND, int NS, int BLOCK, bool TWOPASS = false>
 static int launch_one(int grid, size_t lds, hipStream_t stream, const uint32_t *code, const MESH_T *consts, const MeshArgs &a) {
+#if MESH_PROF
+    auto fn = k_mesh_prof<MESH_T, (MESH_FULL != 0), NP, ND, NS, BLOCK, TWOPASS>;
+#else
     auto fn = k_mesh<MESH_T, (MESH_FULL != 0), NP, ND, NS, BLOCK, TWOPASS>;
+#endif
     static size_t lds_set[16] = {};      // per device: the dynamic-LDS limit this instantiation was last raised to
     int dev = 0;
     (void)hipGetDevice(&dev);
