@@ -708,6 +708,41 @@ int sdf_support_rays_destroy(sdf_support_rays *rays);
 /* the kernels of this thread's last sdf_mesh_support_rays, milliseconds by HIP events, summed over the directions; parts4 (or NULL):
  * classes and extents, numbering, rays, sums (tools/supports_time.py) */
 double sdf_mesh_supports_last_kernel_ms(double *parts4);
+/* Dual contouring of the field on a dense grid: a mesh with sharp creases (added under ABI 17: the version is unchanged, nothing
+ * above changes; DESIGN.md section 4u, defined by tests/dual_ref.py and reproduced bit for bit).  Samples V[nx][ny][nz] at the axes'
+ * points, s = (i * ny + j) * nz + k, inside iff v < 0.  The edge from sample s to its +1 neighbour along axis a is a crossing if
+ * both ends are finite and differ in `inside`; crossings are numbered by ascending (s, a).  Its point: t = v0 / (v0 - v1),
+ * p[a] = lo + t * (hi - lo); its normal: the field's, as sdf_mesh_vertex_normals takes it, step eps.  Every cell with a crossing
+ * among its twelve edges is active and gets one vertex: over its crossings, in the order a = 0, 1, 2 and (db, dc) = (0, 0), (1, 0),
+ * (0, 1), (1, 1) in the axes (a + 1) % 3, (a + 2) % 3, the mean m of q = p - centre and the quadric of the planes (n, n . q); the
+ * system of sdf_mesh_simplify, (A + reg w I) y = b - A m with w the trace, x = m + y; w == 0: x = m (flat); a component that is
+ * not finite: x = m (mean_fallback); else every component is clamped to the cell (clamped).  Active cells are numbered by ascending
+ * index: the vertices.  Every crossing whose four cells exist emits two triangles over their vertices, (q0, q1, q2), (q0, q2, q3)
+ * with the cells at (-1, -1), (0, -1), (0, 0), (-1, 0) in (b, c), reversed if the low end is not inside; a crossing on the grid's
+ * border emits nothing (open_edges).
+ *   *out            a mesh like sdf_mesh_simplify's: it owns its float64 soup and serves every reader; sdf_mesh_stats reports the
+ *                   triangles and, with block > 0, the blocks of block^3 cells that hold / do not hold an active cell as n_nonempty /
+ *                   n_empty (block <= 0: none are counted).
+ *   h_counters8     crossings, cells, triangles, open_edges, nonfinite_edges (ends that differ in `inside`, one of them not finite:
+ *                   no crossing), clamped, mean_fallback, flat.
+ *   parts           NULL, or where to leave a handle to the crossing points and normals (crossings x 3 float64 each), the vertices
+ *                   (cells x 3 float64) and the triangles' vertex indices (triangles x 3 int64): sdf_dual_parts_fetch copies them
+ *                   out (any pointer may be NULL), sdf_dual_parts_destroy frees the handle's one device block.
+ * Float64, the interpreter of sdf_eval_points over points made from the axes, in slabs of at most 2^22.  The grid is dense: 21 bytes
+ * of device memory per sample (and the slab) in one scratch allocation, 61 per crossing in two more, 28 per vertex; all freed before
+ * the call returns whether it fails or not.  Synchronous, on the context's stream.  An axis of fewer than 2 samples, or a grid
+ * without a crossing, gives a mesh of 0 triangles.  Refused on the host before anything is allocated or launched, with return value
+ * 2: a NULL pointer (parts aside), a tape of another context, a negative axis length, 2^31 or more samples, an eps that is not finite
+ * and positive, a reg that is negative or not finite, an axis value that is not finite, a tape with user closures
+ * (sdf_tape_extern_count > 0).  Other failures return 1 and *out is NULL. */
+typedef struct sdf_dual_parts sdf_dual_parts;
+int sdf_generate_dual(sdf_ctx *ctx, sdf_tape *tape, const double *X, int nx, const double *Y, int ny, const double *Z, int nz, double eps,
+                      double reg, int block, sdf_mesh **out, int64_t *h_counters8, sdf_dual_parts **parts);
+int sdf_dual_parts_fetch(sdf_dual_parts *parts, double *h_points, double *h_normals, double *h_vertices, int64_t *h_cells);
+int sdf_dual_parts_destroy(sdf_dual_parts *parts);
+/* the kernels of this thread's last sdf_generate_dual, milliseconds by HIP events; parts5 (or NULL): the sampling, the crossings
+ * (classify, scans, points), the normals, the cells and their vertices, the emission (tools/dual_time.py) */
+double sdf_generate_dual_last_kernel_ms(double *parts5);
 /* Pinned host memory for the results above: copies into it run at the link rate (fresh pageable memory:
  * ~10 GB/s).  Blocks are recycled through a small free list inside the library (pinning is slow), so
  * free what you allocate.  Any "host" pointer of this API may point into such a block. */

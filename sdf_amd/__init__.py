@@ -42,6 +42,7 @@ from .render import render   # (not in the reference: sphere-traced previews, DE
 from .measure import measure   # (not in the reference: volume, area, inertia and the edge census on the device, section 4g)
 from .thickness import thickness, Thickness   # (not in the reference: the wall thickness at the vertices of a mesh, probed on the device, section 4l)
 from .curvature import curvature, curvature_of_soup, Curvature   # (not in the reference: mean, Gaussian and principal curvature of the field at the vertices of a mesh, probed on the device, section 4t)
+from .dual import dual_of_grid   # (not in the reference: dual contouring of the field -- a mesh with sharp creases, `dual=` of everything that meshes, section 4u)
 from .deviation import deviation, deviation_of_soup, Deviation  # (not in the reference: a mesh held to the field -- per-triangle deviation, vertices snapped back, section 4q)
 from .shells import shells, measure_shells, Shells   # (not in the reference: the connected shells of a mesh, kept or dropped on the device, section 4h)
 from .overhang import overhangs, overhangs_of_mesh, overhangs_soup, sphere_directions, Overhangs   # (not in the reference: build directions rated on the device, section 4n)

@@ -176,7 +176,8 @@ def meshed(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False, simplify_tolerance=None, simplify_levels=5, snap=False):
+        verbose=True, sparse=True, *, keep=None, simplify=None, mend=False, to_host=False, simplify_tolerance=None, simplify_levels=5, snap=False,
+        dual=False):
     """the one path from a model to its mesh on the device: the arguments of `generate`, `keep` (only these
     connected shells, `shells.resolve_keep`: the device mesh is labelled, the kept shells are compacted into a mesh of their own
     and THAT is yielded; section 4h), `simplify` (a real number k > 0, `simplify.check_simplify`: after keep, the mesh is simplified on
@@ -190,7 +191,13 @@ def meshed(
     mend drops; eps defaults to the preview's normal_eps, tol to 1e-3 x the smallest grid step, max_move to the diagonal of one
     cluster cell, of one grid cell without simplify, iters to 4; section 4q), `mend` (False or True, `mend.check_mend`: after keep and after simplify -- simplifying is what makes the
     pairs -- duplicate triangles are dropped and oppositely wound pairs cancel on the device, `engine.Mesh.mend`, and the mended mesh
-    is what is yielded and what the closing line counts; section 4k) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
+    is what is yielded and what the closing line counts; section 4k), `dual` (False, True or a dict of eps and reg,
+    `dual.check_dual_option`: the mesh is made by dual contouring of the field in the place of marching cubes, on the same grid,
+    `engine.Engine.generate_dual` -- one vertex per grid cell that the surface crosses, placed by the quadric of the field's tangent
+    planes, so creases stay sharp; eps, the step of the normals, defaults to the preview's normal_eps, reg to 1e-3; the grid is
+    sampled densely: batch_size, sparse and workers do not steer it (batch_size only sizes the blocks that the closing line counts
+    as nonempty / empty); every stage above works on the result unchanged, and `generate.last_dual` holds its eight counters; one
+    process only; section 4u) and `to_host` (the caller wants the float64 soup on the host: the triangles then travel as
     16-byte records).  Yields a `Meshed`, which the readers below take; closes what it opened on the way out, and after a body
     that did not raise prints the two closing lines of the reference and sets `generate.last_stats`."""
     from . import engine, dist
@@ -203,6 +210,8 @@ def meshed(
     mend = check_mend(mend)      # (before the engine is asked for)
     from .deviation import check_snap_option, snap_params
     snap = check_snap_option(snap)      # (None: the call without it)
+    from .dual import check_dual_option, dual_params
+    dual = check_dual_option(dual)      # (None: the call without it)
     start = time.time()
     eng = engine.get_engine()
     tape = eng.tape_for(sdf)
@@ -227,7 +236,13 @@ def meshed(
 
     mesh = points = soup = simplify_stats = None
     try:
-        if dist.world_size() > 1:
+        if dual is not None:
+            if dist.world_size() > 1:
+                need_device_mesh(None, 'dual', 'a field is dual-contoured')
+            mesh = eng.generate_dual(tape, X, Y, Z, *dual_params(dual, bounds), batch_size=batch_size)
+            stats = mesh.stats()
+            generate.last_dual = mesh.dual_stats
+        elif dist.world_size() > 1:
             soup, stats = dist.generate_sharded_device(eng, tape, X, Y, Z, batch_size, sparse)
             if not to_host and getattr(soup, 'is_cuda', False):
                 # the gathered soup stays on the device (and alive, as `soup`, while the mesh over it is read)
@@ -284,7 +299,7 @@ def meshed(
     generate.last_stats = stats
 
 
-def pipeline_kwargs(generate_kwargs, simplify=None, simplify_tolerance=None, simplify_levels=5, mend=False, snap=False):
+def pipeline_kwargs(generate_kwargs, simplify=None, simplify_tolerance=None, simplify_levels=5, mend=False, snap=False, dual=False):
     """the keywords of `meshed` for a facade's call: its generate_kwargs and, of the pipeline's options, those that are not the
     default.  A default is left out, not passed: `meshed` is looked up at call time, and what stands in for it -- the stand-ins of
     the host tests, a caller's own wrapper -- then sees the call that was made and needs no knowledge of a keyword it was never
@@ -299,6 +314,8 @@ def pipeline_kwargs(generate_kwargs, simplify=None, simplify_tolerance=None, sim
         kw['mend'] = mend
     if snap is not False:
         kw['snap'] = snap
+    if dual is not False:
+        kw['dual'] = dual
     return kw
 
 
@@ -389,19 +406,22 @@ def generate(
         sdf,
         step=None, bounds=None, samples=SAMPLES,
         workers=WORKERS, batch_size=BATCH_SIZE,
-        verbose=True, sparse=True):
+        verbose=True, sparse=True, *, dual=False):
     """reference sdf/core.py:84-150.  `batch_size` up to 512 (the reference takes any: a larger one is refused with a message; up
     to 32 runs the fused kernels, above that the batches go through device memory -- a model with user closures then hands its
-    callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512)."""
-    with meshed(sdf, step, bounds, samples, workers, batch_size, verbose, sparse, to_host=True) as m:
+    callback one whole tile at a time, (batch_size + 1)^3 points: 4.3 GB of pinned host memory at 512).  dual: True or a dict of
+    eps and reg -- the soup of dual contouring in the place of marching cubes: sharp creases (`meshed`, DESIGN.md section 4u;
+    not in the reference; `generate.last_dual` holds its counters)."""
+    with meshed(sdf, step, bounds, samples, workers, batch_size, verbose, sparse, to_host=True, **({} if dual is False else {'dual': dual})) as m:
         return read_soup(m, workers)
 
 
 generate.last_stats = None
+generate.last_dual = None
 
 
 def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None, mend=False, simplify_tolerance=None, simplify_levels=5,
-                  snap=False, **generate_kwargs):
+                  snap=False, dual=False, **generate_kwargs):
     """the indexed mesh of `generate`: (points (U, 3) float64, cells (T, 3) int64, normals (U, 3) float64 or None) -- the soup
     welded on the device, as `save` welds it for every format but STL, and with normals=True the normalised central
     difference of the FIELD at every vertex (step normal_eps; default 1e-4 x the half-diagonal of the bounds, the preview's
@@ -413,9 +433,10 @@ def generate_mesh(sdf, normals=False, normal_eps=None, keep=None, simplify=None,
     are dropped and oppositely wound pairs cancel (`sdf_amd/mend.py`; `generate_mesh.last_mend` holds the
     statistics of the last call that mended).  snap: True or a dict of eps, tol, max_move, iters -- after simplify and before mend the
     vertices are put back on the zero set of the field (`sdf_amd/deviation.py`; `generate_mesh.last_snap` holds
-    the statistics of the last call that snapped); the normals are then the field's at the snapped vertices.  Not in the reference
-    (DESIGN.md section 4f)."""
-    with meshed(sdf, keep=keep, **pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
+    the statistics of the last call that snapped); the normals are then the field's at the snapped vertices.  dual: True or a dict of
+    eps and reg -- the mesh is made by dual contouring in the place of marching cubes, and every stage above works on it
+    (`meshed`; `generate.last_dual` holds its counters).  Not in the reference."""
+    with meshed(sdf, keep=keep, **pipeline_kwargs(generate_kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap, dual)) as m:
         got = read_export(m, bool(normals), normal_eps)
         generate_mesh.last_simplify = m.simplify_stats
         if mend:
@@ -433,7 +454,7 @@ generate_mesh.last_snap = None
 
 
 def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, simplify=None, mend=False, thickness=False,
-         simplify_tolerance=None, simplify_levels=5, snap=False, curvature=False, **kwargs):
+         simplify_tolerance=None, simplify_levels=5, snap=False, curvature=False, dual=False, **kwargs):
     """reference sdf/core.py:152-158.  `.ply` and `.obj` are also written without meshio (sdf_amd/meshfile.py), with
     normals=True carrying the field's normals at the vertices (step normal_eps, see `generate_mesh`); writer = 'native' /
     'meshio' picks one, None (default) is meshio where it imports and no normals are asked for, else native.  keep: write only
@@ -451,7 +472,9 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     'k2' or 'max' (of k1 and k2 the one of larger magnitude, signed), or a dict of `quality` (one of these, default 'mean') and `eps`
     -- the vertices of a .ply file carry that curvature of the field at the final mesh's vertices as `property float quality`
     (`sdf_amd/curvature.py`; eps defaults to the smallest grid step), through the same door and under the same
-    rules as thickness=; a file has one quality column, so thickness= and curvature= together raise ValueError."""
+    rules as thickness=; a file has one quality column, so thickness= and curvature= together raise ValueError.  dual: True or a dict
+    of eps and reg -- the file holds the mesh of dual contouring in the place of marching cubes': sharp creases (`meshed`,
+    DESIGN.md section 4u); every option above works on it."""
     from . import meshfile
     path = os.fspath(path)
     how = meshfile.choose_writer(path, writer, normals, bool(thickness), bool(curvature))
@@ -468,7 +491,7 @@ def save(path, *args, normals=False, normal_eps=None, writer=None, keep=None, si
     if curvature:                 # (refused before anything is meshed, too)
         from .curvature import default_eps, quality_of, read_curvature, save_option
         which, curvature_eps = save_option(curvature)
-    with meshed(*args, keep=keep, **pipeline_kwargs(kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap)) as m:
+    with meshed(*args, keep=keep, **pipeline_kwargs(kwargs, simplify, simplify_tolerance, simplify_levels, mend, snap, dual)) as m:
         if curvature:
             got = read_export(m, bool(normals), normal_eps)
             quality = quality_of(read_curvature(m, default_eps(grid_steps(m, call), curvature_eps), with_mesh=False)[2], which)

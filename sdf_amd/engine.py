@@ -245,6 +245,11 @@ ABI = {
     'sdf_support_rays_fetch': (ctypes.c_int, [_vp, _c_i64, ctypes.POINTER(ctypes.c_int32), _f64p, _u8p, ctypes.POINTER(ctypes.c_int32), _f64p]),
     'sdf_support_rays_destroy': (ctypes.c_int, [_vp]),
     'sdf_mesh_supports_last_kernel_ms': (ctypes.c_double, [_f64p]),
+    'sdf_generate_dual': (ctypes.c_int, [_vp, _vp, _f64p, ctypes.c_int, _f64p, ctypes.c_int, _f64p, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), ctypes.POINTER(_vp)]),
+    'sdf_dual_parts_fetch': (ctypes.c_int, [_vp, _f64p, _f64p, _f64p, ctypes.POINTER(_c_i64)]),
+    'sdf_dual_parts_destroy': (ctypes.c_int, [_vp]),
+    'sdf_generate_dual_last_kernel_ms': (ctypes.c_double, [_f64p]),
     'sdf_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_vp)]),
     'sdf_host_free': (ctypes.c_int, [_vp]),
     'sdf_mesh_kinds': (ctypes.c_int, [_vp, _u8p]),
@@ -1258,6 +1263,43 @@ class Engine:
         m = Mesh(self, h)
         m._tape = dt          # keep the device tape alive as long as the mesh
         m.emitted = bool(emitted.value)
+        return m
+
+    def generate_dual(self, sdf, X, Y, Z, eps, reg=1e-3, batch_size=32, parts=False):
+        """dual-contour the field on the dense grid X x Y x Z (sdf_generate_dual, csrc/sdf_dual.hip; defined
+        by tests/dual_ref.py and reproduced bit for bit): one vertex in every grid cell that the surface crosses, placed by the
+        quadric of the field's tangent planes at the cell's edge crossings (normals by central differences of step eps, the
+        system regularised by reg towards the crossings' mean, the vertex clamped to its cell), two triangles per crossing edge.
+        Returns a `Mesh` that owns its float64 soup and serves every reader; `mesh.dual_stats` holds the eight counters
+        (crossings, cells, triangles, open_edges, nonfinite_edges, clamped, mean_fallback, flat) and `mesh.stats()` counts, as
+        nonempty / empty, the blocks of batch_size^3 cells that hold / do not hold a vertex (batch_size steers nothing else).
+        parts=True: `mesh.dual_parts` is the dict of points, normals (crossings x 3), vertices (cells x 3) and cells
+        (triangles x 3 int64, indices into vertices) on the host.  Raises ValueError, before any device work, for an eps that is
+        not positive and finite, a reg that is negative or not finite, an axis that is not finite, 2^31 or more samples, an engine in
+        float32 precision and a model with user closures (the normals kernel serves neither)."""
+        from .dual import STAT_KEYS, check_axes, check_params
+        eps, reg = check_params(eps, reg)
+        X, Y, Z = check_axes(X, Y, Z)
+        dt = self._probe_tape(sdf, 'generate_dual contours the field')[0]
+        h, p = _vp(), _vp()
+        counters = np.zeros(8, np.int64)
+        _check(self.lib, self.lib.sdf_generate_dual(self.ctx, dt.handle, _dp(X, _f64p), len(X), _dp(Y, _f64p), len(Y), _dp(Z, _f64p), len(Z),
+                                                    eps, reg, int(batch_size), ctypes.byref(h), _dp(counters, ctypes.POINTER(_c_i64)),
+                                                    ctypes.byref(p) if parts else None))
+        m = Mesh(self, h)
+        m._tape = dt          # keep the device tape alive as long as the mesh
+        m.emitted = False
+        m.dual_stats = dict(zip(STAT_KEYS, (int(v) for v in counters)))
+        if parts:
+            try:
+                c, k, t = (m.dual_stats[key] for key in ('crossings', 'cells', 'triangles'))
+                got = {'points': np.zeros((c, 3), np.float64), 'normals': np.zeros((c, 3), np.float64),
+                       'vertices': np.zeros((k, 3), np.float64), 'cells': np.zeros((t, 3), np.int64)}
+                _check(self.lib, self.lib.sdf_dual_parts_fetch(p, _dp(got['points'], _f64p), _dp(got['normals'], _f64p), _dp(got['vertices'], _f64p),
+                                                               _dp(got['cells'], ctypes.POINTER(_c_i64))))
+                m.dual_parts = got
+            finally:
+                self.lib.sdf_dual_parts_destroy(p)
         return m
 
 
