@@ -647,6 +647,9 @@ static inline void mc_vertex(const float *v, int64_t s0, int64_t s1, int i0, int
     double tt = whi / (wlo + whi);
     double pos[3] = {(double)(i0 + off[0]), (double)(i1 + off[1]), (double)(i2 + off[2])};
     pos[axis] = (double)(axis == 0 ? i0 : (axis == 1 ? i1 : i2)) + tt;
+    /* skimage weights all three coordinates: (c w_lo + c w_hi) / (w_lo + w_hi) is c for the two that are constant along the
+     * edge -- unless a sample is NaN, or both are infinite (0 / 0): then the whole vertex is NaN */
+    if (tt != tt) pos[0] = pos[1] = pos[2] = tt;
     o[0] = (float)pos[0]; o[1] = (float)pos[1]; o[2] = (float)pos[2];
 }
 

@@ -248,7 +248,8 @@ __device__ __forceinline__ unsigned cell_config(const unsigned long long *rb, in
 #endif
 // The coordinate of a marching-cubes vertex along its edge: samples vlo (at grid index ibase) and vhi (at ibase + 1).
 // skimage's placement: with w = 1/(eps+|v|), t = w_hi / (w_lo + w_hi), evaluated in float64 on the
-// float32 samples, stored as float32.
+// float32 samples, stored as float32.  TILE_INDEX: the caller vouches for ibase <= 255 (k_mesh: a tile's indices are <= 32).
+template <bool TILE_INDEX>
 __device__ __forceinline__ float mc_edge_pos(double vlo, double vhi, double ibase) {
     const double eps = 2.220446049250313e-16;
     const double a = eps + fabs(vlo), b = eps + fabs(vhi);
@@ -256,10 +257,16 @@ __device__ __forceinline__ float mc_edge_pos(double vlo, double vhi, double ibas
 #if SDF_FAST_VERTEX
     // skimage's t = whi / (wlo + whi) with wlo = 1 / a, whi = 1 / b is a / (a + b) up to its three roundings (<= 5e-16
     // absolute, t <= 1), and only float32(i + t) is kept.  ONE division by reciprocal + Newton steps instead of three
-    // correctly rounded ones (33 of the ~115 instructions of a vertex); the candidate q = i + t' is within 1e-14 of the
-    // reference's float64 sum, so wherever float32(q - D) == float32(q + D) for D = 2^-44 = 5.7e-14 -- rounding is
-    // monotone -- that float IS the reference's.  Otherwise (a float32 rounding boundary inside the 1e-13 window:
-    // ~1e-6 of the vertices; NaN / infinite samples) the three divisions run.  Bit-identical by construction.
+    // correctly rounded ones (33 of the ~115 instructions of a vertex).  The candidate t' is within 1e-15 of t; the
+    // float64 sums q = fl(i + t') and s = fl(i + t) each add half an ulp of the sum, 2^-46 while i + 1 <= 256.  So
+    // |q - s| <= 1e-15 + 2^-45 = 2.9e-14 THERE, and D = 2^-44 = 5.7e-14 covers it with the roundings of q -+ D (2^-46
+    // each) to spare: wherever float32(q - D) == float32(q + D) -- rounding is monotone -- that float IS the
+    // reference's.  Otherwise (a float32 rounding boundary inside the window: ~1e-6 of the vertices; NaN / infinite
+    // samples) the three divisions run.  Bit-identical by construction FOR ibase <= 255, and for no larger index: an
+    // ulp of the sum is 2^-44 from 256, 2^-43 from 512 and 2^-42 from 1024 on, where q -+ D rounds back to q and the
+    // test passes whatever q is (tools/find_mc_near_ties.py finds sample pairs on which one division and three then
+    // end in different floats; the device did, on every pair that needs a correctly rounded quotient to: profiles/
+    // mc_edges01.md).  A caller-supplied volume has such indices: from 256 on the three divisions run.
     const double sab = a + b;
     double r = __builtin_amdgcn_rcp(sab);
     r = fma(fma(-sab, r, 1.0), r, r);
@@ -269,7 +276,7 @@ __device__ __forceinline__ float mc_edge_pos(double vlo, double vhi, double ibas
     const double q = ibase + tq;
     const float f_lo = (float)(q - 0x1p-44), f_hi = (float)(q + 0x1p-44);
     pf = f_lo;
-    if (__builtin_expect(!(f_lo == f_hi), 0))
+    if (__builtin_expect(!(f_lo == f_hi) || (!TILE_INDEX && ibase >= 256.0), 0))
 #endif
     {
         const double wlo = 1.0 / a, whi = 1.0 / b;
@@ -279,7 +286,9 @@ __device__ __forceinline__ float mc_edge_pos(double vlo, double vhi, double ibas
     return pf;
 }
 // One marching-cubes vertex on edge e of the cell at (i0,i1,i2); v points at the cell's corner 0
-// in a volume with strides (s0, s1, 1).
+// in a volume with strides (s0, s1, 1).  skimage interpolates all THREE coordinates with the two weights (the constant ones
+// come out as (c w_lo + c w_hi) / (w_lo + w_hi) = c): a NaN sample, or the 0 / 0 of two infinite ones, makes the whole
+// vertex NaN.  pf - pf is +0 for every other pf (a finite index plus t in [0, 1]) and leaves the constant coordinates alone.
 __device__ __forceinline__ void mc_vertex(const float *v, int s0, int s1, int i0, int i1, int i2, int e, float *o) {
     const int axis = e >> 2, oa = (e >> 1) & 1, ob = e & 1;
     int o0, o1, o2, stride;
@@ -287,8 +296,9 @@ __device__ __forceinline__ void mc_vertex(const float *v, int s0, int s1, int i0
     else if (axis == 1) { o0 = oa; o1 = 0; o2 = ob; stride = s1; }
     else { o0 = oa; o1 = ob; o2 = 0; stride = 1; }
     const int base = o0 * s0 + o1 * s1 + o2;
-    const float pf = mc_edge_pos((double)v[base], (double)v[base + stride], (double)(axis == 0 ? i0 : (axis == 1 ? i1 : i2)));
-    o[0] = axis == 0 ? pf : (float)(i0 + o0); o[1] = axis == 1 ? pf : (float)(i1 + o1); o[2] = axis == 2 ? pf : (float)(i2 + o2);
+    const float pf = mc_edge_pos<false>((double)v[base], (double)v[base + stride], (double)(axis == 0 ? i0 : (axis == 1 ? i1 : i2)));
+    const float nn = pf - pf;
+    o[0] = axis == 0 ? pf : (float)(i0 + o0) + nn; o[1] = axis == 1 ? pf : (float)(i1 + o1) + nn; o[2] = axis == 2 ? pf : (float)(i2 + o2) + nn;
 }
 
 // ---- the tile of one batch as the marching phases of k_mesh see it -----------------------------
@@ -323,8 +333,9 @@ __device__ __forceinline__ void mc_vertex_view(const TileView &vw, int i0, int i
     const int o0 = axis == 0 ? 0 : oa, o1 = axis == 0 ? oa : (axis == 1 ? 0 : ob), o2 = axis == 2 ? 0 : ob;
     const int x = i0 + o0, y = i1 + o1, z = i2 + o2;
     const float vlo = vw.at(x, y, z), vhi = vw.at(x + (axis == 0 ? 1 : 0), y + (axis == 1 ? 1 : 0), z + (axis == 2 ? 1 : 0));
-    const float pf = mc_edge_pos((double)vlo, (double)vhi, (double)(axis == 0 ? i0 : (axis == 1 ? i1 : i2)));
-    o[0] = axis == 0 ? pf : (float)x; o[1] = axis == 1 ? pf : (float)y; o[2] = axis == 2 ? pf : (float)z;
+    const float pf = mc_edge_pos<true>((double)vlo, (double)vhi, (double)(axis == 0 ? i0 : (axis == 1 ? i1 : i2)));
+    const float nn = pf - pf;                      // NaN when pf is: the whole vertex is NaN then, like skimage's (mc_vertex)
+    o[0] = axis == 0 ? pf : (float)x + nn; o[1] = axis == 1 ? pf : (float)y + nn; o[2] = axis == 2 ? pf : (float)z + nn;
 }
 
 // compact output: triangle number `pos` of the shard's slab from its nine local floats

@@ -84,7 +84,7 @@ def test_meshing_with_the_interval_passes_on_and_off(name, ns, eng):
     assert s0['n_pruned_instrs'] == 0 and s0['n_sampled_voxels'] == s0['n_eval_voxels']
     assert np.array_equal(k1, k0) and np.array_equal(k1, ref.kinds)
     assert p1.shape == p0.shape == ref.points.shape
-    assert np.array_equal(p1, p0, equal_nan=True)      # (a NaN sample next to a finite one: vertices with a NaN coordinate, like the reference's)
+    assert np.array_equal(p1, p0, equal_nan=True)      # (a NaN sample next to a finite one: vertices NaN in all three coordinates, like the reference's)
     if is_trig(t):     # (the device's libm against glibc: the rule of test_gpu.py::test_interval_passes_identity_and_oracle_for_every_fixture)
         if len(p1):
             assert np.abs(p1 - ref.points).max() <= 1e-5 * 3.2 and (p1 == ref.points).mean() > 0.999

@@ -175,9 +175,9 @@ def test_checker_marches_a_volume_with_nan_like_the_reference(ns, golden_params,
     """extrude_to(.., 0) is positive everywhere but NaN on the plane z = 0.  The reference's `generate` (recorded) marches
     such a batch -- volume.min() is NaN, so skimage's range check passes; a NaN sample counts as inside -- and returns
     triangles of NaN.  The checker's `generate` must classify the batch and count its triangles the same way (it used
-    to take the minimum over the other samples and call the batch empty, while the device meshed it).  Known
-    difference, pinned here as it is: skimage interpolates all three coordinates of a vertex with the NaN weight, the
-    checker and the device only the one along the cell edge -- every vertex is NaN in both, in one coordinate or in three."""
+    to take the minimum over the other samples and call the batch empty, while the device meshed it).  skimage
+    interpolates all three coordinates of a vertex with the NaN weight: the whole vertex is NaN, and so is the checker's
+    (it used to be NaN in the coordinate along the cell edge alone; tests/test_mc_edges_host.py has more of this)."""
     from sdf_amd import core
     name = 'extrude_to_zero'
     bounds = tuple(map(tuple, golden_params['g_%s_bounds' % name]))
@@ -186,5 +186,4 @@ def test_checker_marches_a_volume_with_nan_like_the_reference(ns, golden_params,
     want = golden_params['g_%s_points' % name]
     assert len(want) > 0 and np.isnan(want).all()
     assert np.array_equal(r.kinds, golden_params['g_%s_kinds' % name])
-    assert r.points.shape == want.shape and np.isnan(r.points).any(axis=1).all()
-    assert np.isnan(r.points).sum(axis=1).max() == 1 and np.isnan(r.points[:, 2]).all()
+    assert r.points.shape == want.shape and np.isnan(r.points).all()
